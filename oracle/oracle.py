@@ -54,6 +54,7 @@ def lib():
         _lib.vo_conv_update.argtypes = [C.POINTER(State), C.c_double]
         _lib.vo_bar_ease.argtypes = [C.POINTER(State), C.c_int]
         _lib.vo_apply_dof.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_double, C.c_double, _f32p]
+        _lib.vo_apply_dof_dense.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_double, C.c_double, _f32p]
         _lib.vo_color_grade.argtypes = [_f32p, C.c_size_t, C.c_double, C.c_double, C.c_double, _f32p]
         _lib.vo_sharpen.argtypes = [_u8p, C.c_int, C.c_int, C.c_double, _u8p]
         _lib.vo_shape_depth_for_pop.argtypes = [_f32p, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float,
@@ -271,6 +272,16 @@ def apply_dof(rgb, depth, focal_depth, max_sigma=2.0):
     _, H, W = rgb.shape
     out = np.empty_like(rgb)
     lib().vo_apply_dof(pr, pd, H, W, float(focal_depth), float(max_sigma), out.ctypes.data_as(_f32p))
+    return out
+
+
+def apply_dof_dense(rgb, depth, focal_depth, max_sigma=2.0):
+    """apply_dof with the Gaussian levels in the reference's dense k x k association (the render path's dof_dense_conv)."""
+    rgb, pr = _f(rgb)
+    depth, pd = _f(depth)
+    _, H, W = rgb.shape
+    out = np.empty_like(rgb)
+    lib().vo_apply_dof_dense(pr, pd, H, W, float(focal_depth), float(max_sigma), out.ctypes.data_as(_f32p))
     return out
 
 

@@ -903,8 +903,172 @@ def gen_aten_any_size():
     save("aten_any_size.npz", **out)
 
 
+# ------------------------------------------------------------------------------------------
+# The seeded sweeps of tests/test_oracle_vs_live_reference.py (cases.py draws them): the reference's outputs, recorded with
+# cases.LIVE_THREADS torch threads.  Every frame / plane the oracle reproduces exactly (in its N-thread ATen mode where the default mode is
+# only within bars, with the dense DOF order where the default is separable) is stored as SHA-256 (16 hex digits) + row sums, like
+# aten_any_size.npz; only what the oracle matches within a bar alone (the curvature planes, the hand-off planes) is stored whole.
+# ------------------------------------------------------------------------------------------
+def _reference_function(path, name, namespace):
+    """One function of a reference module that cannot be imported here as a whole (core/render_depth.py pulls in diffusers,
+    onnxruntime, tkinter ...): its ``def`` is located with ``ast`` in the file where it lies and compiled on its own."""
+    import ast
+    src = open(path).read()
+    node = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == name)
+    ns = dict(namespace)
+    exec(compile(ast.Module(body=[node], type_ignores=[]), path, "exec"), ns)
+    return ns[name]
+
+
+def _digest(out, key, frames):
+    """SHA-256 + row sums of each frame (or plane) of `frames`."""
+    out[f"{key}__shape"] = np.array(np.shape(frames[0]), dtype=np.int64)
+    out[f"{key}__n"] = np.int64(len(frames))
+    for i, fr in enumerate(frames):
+        fr = np.ascontiguousarray(fr)
+        out[f"{key}__sha_{i}"] = np.frombuffer(sha(fr).encode(), dtype=np.uint8)
+        rs = (fr.astype(np.float64) if fr.dtype.kind == "f" else fr.astype(np.int64)).reshape(fr.shape[0], -1).sum(axis=1)
+        out[f"{key}__rowsum_{i}"] = rs if fr.dtype.kind == "f" else rs.astype(np.int32)
+
+
+def _live_shift(ih, iw, H, W, fg, mg_, bg, kw, frame_idx, return_shift_map=True):
+    bgr, d = synth.synth_frame(frame_idx, ih, iw)
+    rl.reset_state()
+    with torch.no_grad():
+        res = r.pixel_shift_cuda(r.frame_to_tensor(bgr), torch.from_numpy(d[None].copy()), W, H, fg, mg_, bg, return_shift_map=return_shift_map, **kw)
+    return [np.asarray(res[0]), np.asarray(res[1])] + ([res[2].numpy().astype(np.float32)] if return_shift_map else []), np.float64(r.floating_window_tracker.prev_offset)
+
+
+def _live_letterbox_loop(sh, sw, n, top, bottom, label, kw):
+    frames, depth_bgr = synth.letterbox_clip(n, sh, sw, top, bottom)
+    ref_stubs._Clip.clips["in.mp4"] = frames
+    ref_stubs._Clip.clips["depth.mp4"] = depth_bgr
+    rl.reset_state()
+    args = dict(input_path="in.mp4", depth_path="depth.mp4", output_path="out.avi", selected_codec="XVID", fps=24.0,
+                output_width=sw, selected_aspect_ratio=_Aspect(label), aspect_ratios=r.aspect_ratios,
+                suspend_flag=threading.Event(), cancel_flag=threading.Event())
+    args.update(kw)
+    with contextlib.redirect_stdout(io.StringIO()) as so:
+        r.render_sbs_3d(**args)
+    if "crashed" in so.getvalue():
+        raise RuntimeError(so.getvalue()[-300:])
+    return np.stack(ref_stubs._Clip.written["out.avi"])
+
+
+def record_live(only=None):
+    """The contents of live_sweeps.npz.  `only` ({group: seeds}, e.g. {"shiftrand": range(100, 400)}): record just those groups and seeds
+    (the offline sweeps of tools/sweep_live_reference.py replay them through the same tests)."""
+    import cases as C
+    from PIL import Image
+    import torch.nn.functional as F
+
+    def seeds(group, default):
+        return default if only is None else only.get(group, [])
+    prev = torch.get_num_threads()
+    torch.set_num_threads(C.LIVE_THREADS)
+    assert torch.get_num_threads() == C.LIVE_THREADS
+    out, drawn = {}, {}
+    try:
+        labels = list(r.aspect_ratios)
+        out["aspect_ratios_json"] = np.frombuffer(json.dumps(r.aspect_ratios).encode(), dtype=np.uint8)
+        for seed in seeds("shiftrand", C.SHIFT_RANDOM_SEEDS):
+            c = C.shift_random_case(seed)
+            planes, out[f"shiftrand{seed}__prev_offset"] = _live_shift(*c, seed)
+            for nm, pl in zip("LRS", planes):
+                _digest(out, f"shiftrand{seed}_{nm}", [pl])
+            drawn[f"shiftrand{seed}"] = c
+        for seed in seeds("shiftutl", C.SHIFT_UNTAILED_SEEDS):
+            c = C.shift_untailed_case(seed)
+            planes, out[f"shiftutl{seed}__prev_offset"] = _live_shift(*c, seed)
+            for nm, pl in zip("LRS", planes):
+                _digest(out, f"shiftutl{seed}_{nm}", [pl])
+            drawn[f"shiftutl{seed}"] = c
+        for seed in seeds("shift1080p", C.SHIFT_1080P_SEEDS):
+            c = C.shift_1080p_case(seed)
+            planes, out[f"shift1080p{seed}__prev_offset"] = _live_shift(*c, seed)
+            for nm, pl in zip("LRS", planes):
+                _digest(out, f"shift1080p{seed}_{nm}", [pl])
+            drawn[f"shift1080p{seed}"] = c
+        if seeds("full1080", [0]):
+            kw = dict(blur_ksize=9, feather_strength=10.0, use_subject_tracking=True, enable_floating_window=True, max_pixel_shift_percent=0.02,
+                      enable_edge_masking=True, enable_feathering=True)
+            planes, out["full1080__prev_offset"] = _live_shift(540, 960, 1080, 1920, 10.0, -2.5, -5.0, kw, 0)
+            for nm, pl in zip("LRS", planes):
+                _digest(out, f"full1080_{nm}", [pl])
+        for k in seeds("evenblur", C.EVEN_BLUR_KS):
+            for H, W in ((40, 64), (80, 128)):
+                planes, _ = _live_shift(40, 64, H, W, 10.0, -2.5, -5.0, dict(blur_ksize=k, feather_strength=10.0), k, return_shift_map=False)
+                for nm, pl in zip("LR", planes):
+                    _digest(out, f"evenblur{k}_{H}_{nm}", [pl])
+        loops = [("looprand", C.LOOP_RANDOM_SEEDS, C.loop_random_case), ("dof", C.DOF_SLIDER_SEEDS, C.dof_slider_case),
+                 ("every", C.EVERY_CONTROL_SEEDS, C.every_control_case), ("anysize", C.ANY_SIZE_SEEDS, C.any_size_loop_case),
+                 ("feather0", C.FEATHER0_CASES, C.feather0_case)]
+        for tag, default_seeds, draw in loops:
+            for seed in seeds(tag, default_seeds):
+                c = draw(seed)
+                name = f"_live_{tag}{seed}"
+                LOOP_CASES[name] = c
+                try:
+                    written = np.stack(run_loop(name))
+                finally:
+                    del LOOP_CASES[name]
+                _digest(out, f"{tag}{seed}", written)
+                drawn[f"{tag}{seed}"] = c
+                print(f"  live {tag}{seed}: {c[3]['output_format']}, {len(written)} frames of {written[0].shape}")
+        for tag, default_seeds, draw in (("blankrand", C.BLANK_RANDOM_SEEDS, C.blank_random_case), ("blankx", C.BLANK_EXACT_SEEDS, C.blank_exact_case)):
+            for seed in seeds(tag, default_seeds):
+                c = draw(seed)
+                name = f"_live_{tag}{seed}"
+                BLANK_CASES[name] = c
+                try:
+                    written = np.stack(run_blank_loop(name))
+                finally:
+                    del BLANK_CASES[name]
+                _digest(out, f"{tag}{seed}", written)
+                drawn[f"{tag}{seed}"] = c
+        for seed in seeds("letterbox", C.LETTERBOX_SEEDS):
+            c = C.letterbox_case(seed, labels)
+            _digest(out, f"letterbox{seed}", _live_letterbox_loop(*c))
+            drawn[f"letterbox{seed}"] = c
+        for seed in seeds("helpers", C.HELPER_SEEDS):
+            h, w, quant, gamma, mid, focal, ms, sat, con, bri = c = C.helper_case(seed)
+            d, d2, bgr = C.helper_planes(seed, h, w, quant)
+            dt = torch.from_numpy(d.copy())[None]
+            k = f"helpers{seed}__"
+            out[k + "subject_depth"] = np.float64(r.estimate_subject_depth(dt).item())
+            out[k + "dyn_scale"] = np.float64(r.compute_dynamic_parallax_scale(dt, 0.90, 1.15))
+            out[k + "motion"] = np.float64(r.compute_motion_metric(dt, torch.from_numpy(d2.copy())[None]))
+            c_ref = torch.clamp(r.enhance_curvature(dt, strength=0.08), 0, 1)[0].numpy()
+            out[k + "curv"] = c_ref
+            s0 = r.estimate_subject_depth(torch.from_numpy(c_ref.copy())[None])
+            out[k + "s0"] = np.float64(float(s0))
+            _digest(out, k + "shaped", [r.shape_depth_for_pop(torch.from_numpy(c_ref.copy())[None], s0, stretch_lo=0.05, stretch_hi=0.95, depth_mid=mid, gamma=gamma)[0].numpy()])
+            dof_ref = r.apply_dof_cuda(r.frame_to_tensor(bgr), dt, focal, max_sigma=ms, focus_width=0.35)
+            _digest(out, k + "dof", [dof_ref.numpy()])
+            _digest(out, k + "graded", [r.tensor_to_frame(r.apply_color_grade(dof_ref, sat, con, bri))])
+            drawn[f"helpers{seed}"] = c
+        conv = _reference_function(os.path.join(rl.REF_ROOT, "core", "render_depth.py"), "convert_depth_to_grayscale",
+                                   {"np": np, "torch": torch, "Image": Image, "print": lambda *a, **k: None})
+        for i, (h, w, pred) in enumerate(C.handoff_cases() if seeds("handoff", [0]) else []):
+            out[f"handoff{i}__u8"] = np.asarray(conv(torch.from_numpy(pred.copy())))
+        for i, (H, W, pred) in enumerate(C.bicubic_cases() if seeds("bicubic", [0]) else []):
+            up = F.interpolate(torch.from_numpy(pred.copy())[None, None], size=(H, W), mode="bicubic", align_corners=False)[0, 0]
+            out[f"bicubic{i}__u8"] = np.asarray(conv(up))
+    finally:
+        torch.set_num_threads(prev)
+    out["threads"] = np.int64(C.LIVE_THREADS)
+    out["cases_json"] = np.frombuffer(json.dumps(drawn).encode(), dtype=np.uint8)
+    return out
+
+
+def gen_live():
+    save("live_sweeps.npz", **record_live())
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["kat", "shift", "helpers", "loops", "widen", "previews", "blank", "heal", "attrib", "real1080", "real1080_formats", "real4k", "real4k_formats", "real4k_dof", "real1080_random", "real4k_random", "real1080_letterbox", "gui_defaults", "aten_any_size", "shift_small"]
+    which = sys.argv[1:] or ["kat", "shift", "helpers", "loops", "widen", "previews", "blank", "heal", "attrib", "real1080", "real1080_formats", "real4k", "real4k_formats", "real4k_dof", "real1080_random", "real4k_random", "real1080_letterbox", "gui_defaults", "aten_any_size", "shift_small", "live"]
+    if "live" in which:
+        gen_live()
     if "aten_any_size" in which:
         gen_aten_any_size()
     if "shift_small" in which:

@@ -130,3 +130,23 @@ def test_emitted_last_stdout_line_parses_and_is_the_compact_one(tmp_path, capsys
     # the full record: an earlier line (wrapped) and the file
     assert json.loads(lines[-2])["bench_full_record"]["sub_records"]["4k-dibr"]["note"] == "n" * 1500
     assert json.load(open(tmp_path / "full.json"))["value"] == res["value"]
+
+
+def test_dump_outputs_writes_float32_frames_within_the_cap(tmp_path):
+    """--dump-outputs: the frames of the last timed step as float32 -- whole while they fit, else the same seeded pixel positions of every frame
+    (all channels), the same from call to call, under the 64 MB cap."""
+    import numpy as np
+    import torch
+    import bench
+    small = torch.randint(0, 256, (2, 36, 64, 3), dtype=torch.uint8)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    a = np.load(tmp_path / "s" / "frames.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, small.numpy().astype(np.float32))
+    big = torch.randint(0, 256, (16, 1080, 1920, 3), dtype=torch.uint8)
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    b1, b2 = np.load(tmp_path / "b1" / "frames.npy"), np.load(tmp_path / "b2" / "frames.npy")
+    assert b1.dtype == np.float32 and b1.shape[0] == 16 and b1.shape[2] == 3 and np.array_equal(b1, b2)
+    assert os.path.getsize(tmp_path / "b1" / "frames.npy") <= 64 << 20 and b1.nbytes > (48 << 20)
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(1080 * 1920, size=b1.shape[1], replace=False))
+    assert np.array_equal(b1, big.reshape(16, -1, 3).numpy()[:, pos].astype(np.float32))

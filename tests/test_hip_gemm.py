@@ -186,8 +186,9 @@ def test_attention_x3_known_answers(R):
 @pytest.mark.parametrize("B,H,W,Cin,Cout", [(1, 16, 32, 16, 64), (2, 37, 66, 128, 128), (1, 50, 45, 96, 128), (3, 19, 33, 64, 64), (1, 74, 132, 128, 64),
                                               (1, 1, 1, 32, 64), (2, 17, 31, 48, 128), (2, 45, 70, 64, 32), (1, 16, 32, 16, 32)])
 def test_conv3x3_x2_is_float32_faithful(R, B, H, W, Cin, Cout):
-    """vd3d_conv3x3_x2 (the DPT neck / head convolutions in the fp16x2 arithmetic) against a float64 convolution, beside the float32 library convolution on the same
-    operands: RMS error <= 1.5 x, maximum <= 2.5 x the library's.  Sizes that are not multiples of the 16 x 32 tile, a one-pixel image (every tap but the centre is
+    """vd3d_conv3x3_x2 (the DPT neck / head convolutions in the fp16x2 arithmetic) against a float64 convolution, beside a float32 library convolution on the same
+    operands: RMS error <= 1.5 x, maximum <= 2.5 x the library's.  The float32 yardstick is PyTorch's CPU convolution: MIOpen's float32 result depends on the
+    solver a box picks (the one-pixel case measured RMS 1.4e-7 on one box and 5.0e-8 on another), which made the bar move from run to run.  Sizes that are not multiples of the 16 x 32 tile, a one-pixel image (every tap but the centre is
     padding), the neck's 96-channel input; post-ReLU inputs with a few large channels, like the maps the fusion stage sees."""
     g = torch.Generator(device="cuda").manual_seed(B * 100 + H)
     x = torch.relu(torch.randn(B, Cin, H, W, device="cuda", generator=g)) * torch.exp(torch.randn(1, Cin, 1, 1, device="cuda", generator=g))
@@ -198,7 +199,7 @@ def test_conv3x3_x2_is_float32_faithful(R, B, H, W, Cin, Cout):
     y = R.conv3x3_x2(x, img, Cout)
     assert y.shape == (B, Cout, H, W) and y.is_contiguous(memory_format=torch.channels_last) and bool(torch.isfinite(y).all())
     ref = F.conv2d(x.double(), w.double(), None, 1, 1)
-    y32 = F.conv2d(x, w, None, 1, 1)
+    y32 = F.conv2d(x.cpu(), w.cpu(), None, 1, 1).to(x.device)
     scale = F.conv2d(x.abs().double(), w.abs().double(), None, 1, 1) + 1e-30
     e3, e32 = float(((y.double() - ref).abs() / scale).max()), float(((y32.double() - ref).abs() / scale).max())
     r3 = float((y.double() - ref).pow(2).mean().sqrt() / ref.pow(2).mean().sqrt())

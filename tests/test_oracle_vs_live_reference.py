@@ -1,74 +1,100 @@
-"""CPU-only cross-check of the oracle against the LIVE reference (``/root/reference`` imported through tests/golden/ref_loader.py
-with the cv2 / torchvision / tkinter stand-ins of ref_stubs.py) over a seeded random sweep of ``pixel_shift_cuda`` parameters
-and sizes.  Complements the committed goldens: the fixtures pin fixed cases everywhere, this sweep widens the pinned region
-wherever the reference tree is present (the development container).  Skipped when it is not (the GPU box: by rule nothing there
-may read /root/reference)."""
+"""CPU-only cross-check of the oracle against the reference over seeded random sweeps of ``pixel_shift_cuda`` parameters, render-loop
+controls and sizes.  The reference's outputs for exactly these draws (tests/golden/cases.py) were recorded by running the reference itself
+(tests/golden/make_golden.py live -> tests/golden/live_sweeps.npz, with cases.LIVE_THREADS torch intra-op threads); each test draws its
+case again, checks that it is the recorded one, runs the oracle and compares.  Complements the fixed cases of the other goldens: these
+sweeps widen the pinned region.  The recording keeps SHA-256 + row sums of every output the oracle reproduces EXACTLY -- in its default
+mode, or in the N-thread ATen mode / dense DOF order where the default mode is held to bars: the tests first check that exact output
+against the digest, then measure the default mode against it (the reference's output, bit for bit)."""
+import hashlib
+import json
 import os
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import b2_max_bound, u8_diff_stats
-from visiondepth3d_amd import synth
-from visiondepth3d_amd._abi import ShiftParams, State
-
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-import ref_loader  # noqa: E402
+import cases as C  # noqa: E402
+from conftest import b2_max_bound, load_golden, u8_diff_stats  # noqa: E402
+from visiondepth3d_amd import synth  # noqa: E402
+from visiondepth3d_amd._abi import ShiftParams, State  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
-
-
-def _sweep(n):
-    """Seeds of the exact live sweeps: n with the suite; VD3D_SWEEP_SEEDS="a:b" runs seeds a .. b-1 instead (offline runs, e.g. with -n 8)."""
-    e = os.environ.get("VD3D_SWEEP_SEEDS")
-    if e:
-        a, b = (int(v) for v in e.split(":"))
-        return range(a, b)
-    return range(n)
+THREADS = C.LIVE_THREADS     # the N of the N-thread ATen mode: the recording reference process's torch.get_num_threads()
 
 
 @pytest.fixture(scope="module")
-def ref():
-    import torch
-    torch.set_num_threads(4)
-    return ref_loader.load()
+def live():
+    g = load_golden("live_sweeps.npz")
+    assert int(g["threads"]) == THREADS
+    return g
 
 
-@pytest.mark.parametrize("seed", list(range(24)) + [101, 112, 159, 239, 248, 261, 310, 426, 594, 873])   # + the worst of a 940-seed offline sweep
-def test_pixel_shift_random_parameters(ref, oracle, seed):
-    import torch
-    rng = np.random.default_rng(5000 + seed)
-    ih, iw = int(rng.integers(24, 80)), int(rng.integers(32, 130))
-    if rng.integers(0, 3) == 0:
-        H, W = ih, iw
-    else:
-        H, W = int(rng.integers(24, 120)), int(rng.integers(32, 200))
-    kw = dict(blur_ksize=int(rng.integers(0, 6)) * 2 + 1, feather_strength=float(rng.uniform(0, 20)),   # odd k: even k changes the plane size in torch
-              use_subject_tracking=bool(rng.integers(0, 2)), enable_floating_window=bool(rng.integers(0, 2)),
-              max_pixel_shift_percent=float(rng.uniform(0.005, 0.06)), zero_parallax_strength=float(rng.uniform(0, 0.03)),
-              enable_edge_masking=bool(rng.integers(0, 3) > 0), enable_feathering=bool(rng.integers(0, 3) > 0),
-              convergence_strength=float([0.0, 3.0, -2.0][int(rng.integers(0, 3))]), enable_dynamic_convergence=bool(rng.integers(0, 2)),
-              depth_pop_gamma=float(rng.uniform(0.6, 1.3)), depth_pop_mid=float(rng.uniform(0.35, 0.65)),
-              parallax_balance=float(rng.uniform(0.5, 1.0)))
-    fg, mg, bg = float(rng.uniform(0, 30)), float(rng.uniform(-10, 5)), float(rng.uniform(-25, 0))
+def _recorded(live, key, case):
+    """The recorded case `key`, after checking that the reference ran on the case this test draws."""
+    drawn = json.loads(bytes(live["cases_json"]).decode())[key]
+    assert drawn == json.loads(json.dumps(case)), (key, drawn, case)
+    return lambda field: live[f"{key}__{field}"]
+
+
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:16]
+
+
+def _digest_mismatch(live, key, frames):
+    """None if every frame (plane) of `frames` has the recorded SHA-256, else where the first one differs (row sums locate it)."""
+    frames = list(frames)
+    if len(frames) != int(live[f"{key}__n"]) or tuple(frames[0].shape) != tuple(int(v) for v in live[f"{key}__shape"]):
+        return ("shape", len(frames), frames[0].shape, int(live[f"{key}__n"]), tuple(live[f"{key}__shape"]))
+    for i, fr in enumerate(frames):
+        if _sha(fr) != bytes(live[f"{key}__sha_{i}"]).decode():
+            rs = (fr.astype(np.float64) if fr.dtype.kind == "f" else fr.astype(np.int64)).reshape(fr.shape[0], -1).sum(axis=1)
+            rows = np.nonzero(rs != live[f"{key}__rowsum_{i}"])[0]
+            return ("frame", i, "rows whose sums differ", rows[:10].tolist(), len(rows))
+    return None
+
+
+def _exact_loop(live, oracle, key, case, params, blank=()):
+    """The oracle's loop frames in the N-thread ATen mode, checked against the digest of the reference's: the reference's frames, bit for bit."""
+    _recorded(live, key, case)
+    sh, sw, n = case[:3]
+    frames = _oracle_loop(oracle, sh, sw, n, params, blank)
+    bad = _digest_mismatch(live, key, frames)
+    assert bad is None, (key, bad, case)
+    return frames
+
+
+def _aspect_ratios(live):
+    return json.loads(bytes(live["aspect_ratios_json"]).decode())
+
+
+def _oracle_loop(oracle, sh, sw, n, params, blank=()):
+    frames, depths = synth.synth_clip(n, sh, sw)
+    ro = oracle.RenderOracle(params)
+    ro.new_clip()
+    return np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1, **({"blank": True} if i in blank else {}))
+                     for i, (f, d) in enumerate(list(zip(frames, depths))[1:])])
+
+
+@pytest.mark.parametrize("seed", C.SHIFT_RANDOM_SEEDS)
+def test_pixel_shift_random_parameters(live, oracle, seed):
+    ih, iw, H, W, fg, mg, bg, kw = case = C.shift_random_case(seed)
+    ref = _recorded(live, f"shiftrand{seed}", case)
     bgr, d = synth.synth_frame(seed, ih, iw)
     ft = oracle.frame_to_tensor(bgr)
-    ref_loader.reset_state(ref)
-    with torch.no_grad():
-        rl, rr, rs = ref.pixel_shift_cuda(torch.from_numpy(ft), torch.from_numpy(d[None].copy()), W, H, fg, mg, bg, return_shift_map=True, **kw)
     # Round 5: the N-thread ATen mode (aten_threads = the reference process's torch.get_num_threads()) restates the two size-dependent ATen code paths these odd
     # sizes hit -- libm on the scalar tails of pow / sigmoid, the premultiplied-weight bilinear kernel for outputs with H + W <= 128 -- and is EXACT here: tracker,
     # shift map, both eyes (offline: 400 of 400 seeds at 1, 3, 4 and 8 threads).
     st_a = State()
-    oa = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(fg, mg, bg, aten_threads=torch.get_num_threads(), **kw), st_a, want_shift=True)
-    assert st_a.fw_prev_offset == ref.floating_window_tracker.prev_offset, (seed, kw)
-    assert np.array_equal(oa["shift"].view(np.uint32), rs.numpy().view(np.uint32)), (seed, (ih, iw, H, W), kw)
-    assert np.array_equal(oa["left"], np.asarray(rl)) and np.array_equal(oa["right"], np.asarray(rr)), (seed, (ih, iw, H, W), kw)
+    oa = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(fg, mg, bg, aten_threads=THREADS, **kw), st_a, want_shift=True)
+    assert st_a.fw_prev_offset == float(ref("prev_offset")), (seed, kw)
+    for nm, got in (("S", oa["shift"]), ("L", oa["left"]), ("R", oa["right"])):
+        bad = _digest_mismatch(live, f"shiftrand{seed}_{nm}", [got])
+        assert bad is None, (seed, nm, (ih, iw, H, W), bad, kw)
+    rl, rr, rs = oa["left"], oa["right"], oa["shift"]    # = the reference's eyes and shift map, bit for bit
     # ... and the default, thread-independent mode (aten_threads = 0: SLEEF values and the nested bilinear form everywhere) stays within the bounds below
     st = State()
     o = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(fg, mg, bg, **kw), st, want_shift=True)
-    assert st.fw_prev_offset == ref.floating_window_tracker.prev_offset, (seed, kw)
+    assert st.fw_prev_offset == float(ref("prev_offset")), (seed, kw)
     # shift map: on these odd-sized planes ATen runs its SCALAR loop on the last n mod 32 elements (std::pow in double there, not the
     # SLEEF value the oracle restates), so up to 31 elements can differ by an ULP of a layer weight (6e-8), amplified by
     # amp = (1.2 fg + |mg| + 1.1 |bg|) / (W/2) -- above 1 only for the tiny widths of this sweep.  4e-7 * max(1, amp) in normalised
@@ -79,83 +105,41 @@ def test_pixel_shift_random_parameters(ref, oracle, seed):
     # nested form it uses for every real frame size (and the oracle uses); a depth edge amplifies that: 1e-6 (worst of 940: 7.3e-7).
     amp = (1.2 * fg + abs(mg) + 1.1 * abs(bg)) / (W / 2)
     tol = (4e-7 if H * W >= 4200 else 1e-6) * max(1.0, amp)
-    assert np.max(np.abs(o["shift"] - rs.numpy())) < tol, (seed, amp, kw)
+    assert np.max(np.abs(o["shift"] - rs)) < tol, (seed, amp, kw)
     for got, exp, eye in ((o["left"], rl, "L"), (o["right"], rr, "R")):
-        mx, frac, _ = u8_diff_stats(got, np.asarray(exp))
+        mx, frac, _ = u8_diff_stats(got, exp)
         # <= 1 LSB everywhere (the B1 bar); how MANY samples sit on a truncation cliff depends on the content: 940-seed sweep max 0.82 %
         assert mx <= 1 and frac < 1e-2, (seed, eye, mx, frac, kw)
 
 
-@pytest.mark.parametrize("seed", range(24))
-def test_pixel_shift_random_parameters_exact_on_untailed_planes(ref, oracle, seed):
+
+
+@pytest.mark.parametrize("seed", C.SHIFT_UNTAILED_SEEDS)
+def test_pixel_shift_random_parameters_exact_on_untailed_planes(live, oracle, seed):
     """The same sweep on planes whose element count is a multiple of 32 and >= 4200 (every real frame size is): with torch-CPU's
     pow / sigmoid (SLEEF) and sqrt (MKL VML) restated bit for bit in the oracle, the shift map AND both eyes equal the reference's
     EXACTLY.  What the sweep above still tolerates is confined to sizes no video has: ATen's scalar loop on the last n mod 32 elements
     of a worker's chunk (std::pow in double there) and its premultiplied bilinear variant below ~4 K elements."""
-    import torch
-    rng = np.random.default_rng(5000 + seed)
-    ih, iw = int(rng.integers(24, 80)), int(rng.integers(32, 130))
-    if rng.integers(0, 3) == 0:
-        H, W = ih, iw
-    else:
-        H, W = int(rng.integers(24, 120)), int(rng.integers(32, 200))
-    kw = dict(blur_ksize=int(rng.integers(0, 6)) * 2 + 1, feather_strength=float(rng.uniform(0, 20)),
-              use_subject_tracking=bool(rng.integers(0, 2)), enable_floating_window=bool(rng.integers(0, 2)),
-              max_pixel_shift_percent=float(rng.uniform(0.005, 0.06)), zero_parallax_strength=float(rng.uniform(0, 0.03)),
-              enable_edge_masking=bool(rng.integers(0, 3) > 0), enable_feathering=bool(rng.integers(0, 3) > 0),
-              convergence_strength=float([0.0, 3.0, -2.0][int(rng.integers(0, 3))]), enable_dynamic_convergence=bool(rng.integers(0, 2)),
-              depth_pop_gamma=float(rng.uniform(0.6, 1.3)), depth_pop_mid=float(rng.uniform(0.35, 0.65)),
-              parallax_balance=float(rng.uniform(0.5, 1.0)))
-    fg, mg, bg = float(rng.uniform(0, 30)), float(rng.uniform(-10, 5)), float(rng.uniform(-25, 0))
-    same = (H, W) == (ih, iw)
-    W = (W + 31) // 32 * 32
-    iw = W if same else (iw + 31) // 32 * 32
-    if H * W < 4200:
-        H = 4200 // W + 1
-    if same:
-        ih = H
+    ih, iw, H, W, fg, mg, bg, kw = case = C.shift_untailed_case(seed)
+    ref = _recorded(live, f"shiftutl{seed}", case)
     bgr, d = synth.synth_frame(seed, ih, iw)
     ft = oracle.frame_to_tensor(bgr)
-    ref_loader.reset_state(ref)
-    with torch.no_grad():
-        rl, rr, rs = ref.pixel_shift_cuda(torch.from_numpy(ft), torch.from_numpy(d[None].copy()), W, H, fg, mg, bg, return_shift_map=True, **kw)
     st = State()
     o = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(fg, mg, bg, **kw), st, want_shift=True)
-    assert st.fw_prev_offset == ref.floating_window_tracker.prev_offset, (seed, kw)
-    assert np.array_equal(o["shift"], rs.numpy()), (seed, kw)
-    assert np.array_equal(o["left"], np.asarray(rl)) and np.array_equal(o["right"], np.asarray(rr)), (seed, kw)
+    assert st.fw_prev_offset == float(ref("prev_offset")), (seed, kw)
+    for nm, got in (("S", o["shift"]), ("L", o["left"]), ("R", o["right"])):
+        bad = _digest_mismatch(live, f"shiftutl{seed}_{nm}", [got])
+        assert bad is None, (seed, nm, bad, kw)
 
 
-@pytest.mark.parametrize("seed", list(range(8)) + [114, 136, 151, 153])   # + the worst of a 60-seed offline sweep
-def test_render_loop_random_configurations(ref, oracle, seed):
-    """The real ``render_sbs_3d`` loop of the live reference (fake VideoCapture / VideoWriter of ref_stubs) vs the oracle on
+@pytest.mark.parametrize("seed", C.LOOP_RANDOM_SEEDS)
+def test_render_loop_random_configurations(live, oracle, seed):
+    """The real ``render_sbs_3d`` loop of the reference (fake VideoCapture / VideoWriter of ref_stubs) vs the oracle on
     random configurations; bars of the committed B2 goldens (tests/test_oracle_vs_golden.py)."""
-    import make_golden as mg   # importable: generation only runs under __main__
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(7000 + seed)
-    fmt = ["Half-SBS", "Full-SBS", "Passive Interlaced", "Red-Cyan Anaglyph"][int(rng.integers(0, 4))]
-    sh = int(rng.integers(40, 100)) // 2 * 2
-    sw = int(round(sh * [16 / 9, 16 / 9, 4 / 3, 2.0][int(rng.integers(0, 4))])) // 2 * 2
-    kw = dict(output_format=fmt, output_height=sh, fg_shift=float(rng.uniform(2, 20)), mg_shift=float(rng.uniform(-6, 2)),
-              bg_shift=float(rng.uniform(-15, 0)), sharpness_factor=float(rng.uniform(0.0, 0.4)),
-              dof_strength=float([0.0, 1.0, 2.0][int(rng.integers(0, 3))]), feather_strength=float(rng.uniform(0, 15)),
-              blur_ksize=int(rng.integers(0, 5)) * 2 + 1, use_subject_tracking=bool(rng.integers(0, 2)),
-              use_floating_window=bool(rng.integers(0, 2)), ipd_factor=float([1.0, 1.0, 1.2][int(rng.integers(0, 3))]),
-              color_saturation=float(rng.uniform(0.9, 1.3)), color_contrast=float(rng.uniform(0.95, 1.1)),
-              color_brightness=float(rng.uniform(-0.03, 0.03)))
-    if fmt == "Full-SBS":
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 4
-    name = f"_live_{seed}"
-    mg.LOOP_CASES[name] = (sh, sw, n, kw)
-    try:
-        written = np.stack(mg.run_loop(name))
-    finally:
-        del mg.LOOP_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, **kw))
-    ro.new_clip()
-    got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1) for f, d in list(zip(frames, depths))[1:]])
+    sh, sw, n, kw = case = C.loop_random_case(seed)
+    written = _exact_loop(live, oracle, f"looprand{seed}", case, render_kwargs_to_params(sw, sh, aten_sum_threads=THREADS, **kw))
+    got = _oracle_loop(oracle, sh, sw, n, render_kwargs_to_params(sw, sh, **kw))
     assert got.shape == written.shape, (got.shape, written.shape, kw)
     mx, frac, frac_gt1 = u8_diff_stats(got, written)
     # >= 99.5 % of the samples within 1 LSB; the maximum is bounded by what grade / sharpen / anaglyph can make of 1 LSB (conftest)
@@ -176,85 +160,38 @@ def _cliff_bars(kw):
     return 1.5e-2, 5e-3
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_letterbox_aspect_loops_random_configurations(ref, oracle, seed):
+@pytest.mark.parametrize("seed", C.LETTERBOX_SEEDS)
+def test_letterbox_aspect_loops_random_configurations(live, oracle, seed):
     """Random letterbox bars x auto_crop_black_bars on / off x the reference's seven aspect-ratio labels x formats x output heights
     through the real loop (40-seed offline sweep: one configuration exceeded the old fixed maximum of 8 -- 1 LSB at the warp output
     turned into 2 by the identity grade's own truncation, then x 8 by the sharpen; b2_max_bound now states that bound)."""
-    import contextlib
-    import io
-    import threading
-    import make_golden as mg
-    import ref_stubs
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(13000 + [29, 0, 1, 2, 3, 4][seed])
-    labels = list(ref.aspect_ratios)
-    fmt = ["Half-SBS", "Passive Interlaced", "Red-Cyan Anaglyph", "Full-SBS"][int(rng.integers(0, 4))]
-    sh = int(rng.integers(60, 130)) // 2 * 2
-    sw = int(round(sh * [16 / 9, 2.0, 4 / 3, 2.39][int(rng.integers(0, 4))])) // 2 * 2
-    oh = [sh, int(rng.integers(40, 110)) // 2 * 2][int(rng.integers(0, 2))]
-    label = labels[int(rng.integers(0, len(labels)))]
-    top, bottom = int(rng.integers(0, sh // 5)), int(rng.integers(0, sh // 5))
-    auto = bool(rng.integers(0, 2))
-    kw = dict(output_format=fmt, output_height=oh, fg_shift=float(rng.uniform(2, 20)), mg_shift=float(rng.uniform(-6, 2)),
-              bg_shift=float(rng.uniform(-15, 0)), sharpness_factor=float(rng.uniform(0.0, 0.4)),
-              dof_strength=float([0.0, 2.0][int(rng.integers(0, 2))]), feather_strength=float(rng.uniform(0, 15)),
-              blur_ksize=int(rng.integers(0, 5)) * 2 + 1, use_subject_tracking=bool(rng.integers(0, 2)),
-              use_floating_window=bool(rng.integers(0, 2)), auto_crop_black_bars=auto)
-    if fmt == "Full-SBS":
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 4
+    aspect_ratios = _aspect_ratios(live)
+    sh, sw, n, top, bottom, label, kw = case = C.letterbox_case(seed, list(aspect_ratios))
+    _recorded(live, f"letterbox{seed}", case)
     frames, depth_bgr = synth.letterbox_clip(n, sh, sw, top, bottom)
-    ref_stubs._Clip.clips["in.mp4"] = frames
-    ref_stubs._Clip.clips["depth.mp4"] = depth_bgr
-    ref_loader.reset_state(ref)
-    args = dict(input_path="in.mp4", depth_path="depth.mp4", output_path="out.avi", selected_codec="XVID", fps=24.0,
-                output_width=sw, selected_aspect_ratio=mg._Aspect(label), aspect_ratios=ref.aspect_ratios,
-                suspend_flag=threading.Event(), cancel_flag=threading.Event())
-    args.update(kw)
-    with contextlib.redirect_stdout(io.StringIO()) as so:
-        ref.render_sbs_3d(**args)
-    assert "crashed" not in so.getvalue(), so.getvalue()[-300:]
-    written = np.stack(ref_stubs._Clip.written["out.avi"])
-    ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, target_ratio=ref.aspect_ratios[label], **kw))
-    ro.new_clip()
-    got = np.stack([ro.render(f, d, 1) for f, d in list(zip(frames, depth_bgr))[1:]])
+
+    def render(**extra):
+        ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, target_ratio=aspect_ratios[label], **extra, **kw))
+        ro.new_clip()
+        return np.stack([ro.render(f, d, 1) for f, d in list(zip(frames, depth_bgr))[1:]])
+    written = render(aten_sum_threads=THREADS)     # the reference's frames, bit for bit:
+    bad = _digest_mismatch(live, f"letterbox{seed}", written)
+    assert bad is None, (seed, bad, kw, label)
+    got = render()
     assert got.shape == written.shape, (got.shape, written.shape, kw, label)
     mx, frac, frac_gt1 = u8_diff_stats(got, written)
     assert mx <= b2_max_bound(kw) and frac_gt1 < 5e-3 and frac < 1.5e-2, (seed, mx, b2_max_bound(kw), frac, frac_gt1, kw, label)
 
 
-@pytest.mark.parametrize("seed", [0, 1, 2, 3, 14, 36])   # 14, 36: the worst of a 40-seed offline sweep (small-sigma DOF cliffs)
-def test_blank_frame_loops_random_configurations(ref, oracle, seed):
-    """skip_blank_frames in the real loop of the live reference (blackdetect list injected) on random configurations, incl. output
+@pytest.mark.parametrize("seed", C.BLANK_RANDOM_SEEDS)
+def test_blank_frame_loops_random_configurations(live, oracle, seed):
+    """skip_blank_frames in the real loop of the reference (blackdetect list injected) on random configurations, incl. output
     heights that differ from the source (the blank frame keeps the SOURCE size): blank frames bit-exact, the others within the bars."""
-    import make_golden as mg
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(11000 + seed)
-    fmt = ["Half-SBS", "Full-SBS", "Passive Interlaced", "Red-Cyan Anaglyph"][int(rng.integers(0, 4))]
-    sh = int(rng.integers(40, 100)) // 2 * 2
-    sw = int(round(sh * [16 / 9, 16 / 9, 4 / 3, 2.0][int(rng.integers(0, 4))])) // 2 * 2
-    oh = [sh, sh, int(rng.integers(40, 110)) // 2 * 2][int(rng.integers(0, 3))]
-    kw = dict(output_format=fmt, output_height=oh, fg_shift=float(rng.uniform(2, 20)), mg_shift=float(rng.uniform(-6, 2)),
-              bg_shift=float(rng.uniform(-15, 0)), sharpness_factor=float(rng.uniform(0.0, 0.4)),
-              dof_strength=float([0.0, 1.0, 2.0][int(rng.integers(0, 3))]), feather_strength=float(rng.uniform(0, 15)),
-              blur_ksize=int(rng.integers(0, 5)) * 2 + 1, use_subject_tracking=bool(rng.integers(0, 2)),
-              use_floating_window=bool(rng.integers(0, 2)), ipd_factor=float([1.0, 0.0, 1.2][int(rng.integers(0, 3))]),
-              skip_blank_frames=True)
-    if fmt == "Full-SBS":
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 7
-    blank = sorted(set(int(v) for v in rng.integers(0, n - 1, size=int(rng.integers(1, 4)))))
-    name = f"_live_blank_{seed}"
-    mg.BLANK_CASES[name] = (sh, sw, n, blank, kw)
-    try:
-        written = np.stack(mg.run_blank_loop(name))
-    finally:
-        del mg.BLANK_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, **kw))
-    ro.new_clip()
-    got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1, blank=(i in blank)) for i, (f, d) in enumerate(list(zip(frames, depths))[1:])])
+    sh, sw, n, blank, kw = case = C.blank_random_case(seed)
+    written = _exact_loop(live, oracle, f"blankrand{seed}", case, render_kwargs_to_params(sw, sh, aten_sum_threads=THREADS, **kw), blank)
+    got = _oracle_loop(oracle, sh, sw, n, render_kwargs_to_params(sw, sh, **kw), blank)
     assert got.shape == written.shape, (got.shape, written.shape, kw)
     fb, fb1 = _cliff_bars(kw)
     for i in range(len(got)):
@@ -265,133 +202,89 @@ def test_blank_frame_loops_random_configurations(ref, oracle, seed):
             assert mx <= b2_max_bound(kw) and frac_gt1 < fb1 and frac < fb, (seed, i, mx, frac, frac_gt1, kw)
 
 
-@pytest.mark.parametrize("seed", range(10))
-def test_helpers_random_inputs(ref, oracle, seed):
-    """Leaf functions of the path on random planes / parameters against the live reference: order statistics, subject depth,
+@pytest.mark.parametrize("seed", C.HELPER_SEEDS)
+def test_helpers_random_inputs(live, oracle, seed):
+    """Leaf functions of the path on random planes / parameters against the reference: order statistics, subject depth,
     dynamic parallax scale and motion metric exact; shaping exact in the N-thread ATen mode (random plane sizes: ATen's scalar tail loop calls libm's pow on
     the last n mod 32 elements; within 1 ULP in the default mode), DOF and grade within 1 LSB (separable vs dense summation)."""
     import torch
-    rng = np.random.default_rng(9000 + seed)
-    h, w = int(rng.integers(20, 70)), int(rng.integers(30, 110))
-    d = synth.synth_frame(seed, h, w)[1]
-    if seed % 3 == 0:     # a quantised plane (an 8-bit depth video): many ties in the order statistics
-        d = (np.floor(d * 255) / 255).astype(np.float32)
+    h, w, quant, gamma, mid, focal, ms, sat, con, bri = case = C.helper_case(seed)
+    ref = _recorded(live, f"helpers{seed}", case)
+    d, d2, bgr = C.helper_planes(seed, h, w, quant)
     dt = torch.from_numpy(d.copy())[None]
-    # order statistics / subject depth: exact
+    # order statistics (torch.quantile itself) / subject depth: exact
     for q in (0.02, 0.05, 0.5, 0.95, 0.98):
         assert np.float32(oracle.quantile(d, q)) == np.float32(torch.quantile(dt.flatten(), q).item()), (seed, q)
-    assert np.float32(oracle.subject_depth(d)) == np.float32(ref.estimate_subject_depth(dt).item()), seed
+    assert np.float32(oracle.subject_depth(d)) == np.float32(ref("subject_depth")), seed
     # reductions: EXACT since round 5 -- torch.mean is ATen's float32 cascade sum / n, restated for any thread count (vo_sum_aten_2d; torch.var accumulates
     # in float64 and equals the rounded exact variance); the order-free exact mean (aten_threads = 0, the library's default) stays within one float32 ULP
-    thr = torch.get_num_threads()
-    got = oracle.dynamic_parallax_scale(d, 0.90, 1.15, aten_threads=thr)
-    exp = ref.compute_dynamic_parallax_scale(dt, 0.90, 1.15)
+    got = oracle.dynamic_parallax_scale(d, 0.90, 1.15, aten_threads=THREADS)
+    exp = float(ref("dyn_scale"))
     assert got == exp, (seed, got, exp)
     assert abs(oracle.dynamic_parallax_scale(d, 0.90, 1.15) - exp) < 2e-6
-    d2 = synth.synth_frame(seed + 50, h, w)[1]
-    mm = oracle.motion_metric(d, d2, aten_threads=thr)
-    assert mm == ref.compute_motion_metric(dt, torch.from_numpy(d2.copy())[None]), seed
+    mm = oracle.motion_metric(d, d2, aten_threads=THREADS)
+    assert mm == float(ref("motion")), seed
     assert abs(oracle.motion_metric(d, d2) - mm) < 2e-6
     # curvature + shaping: exact except the (n mod 32)-element tail, where torch calls libm's pow -> <= 1 ULP of values in [0,1]
     c = oracle.curvature_clamp(d, 0.08)
-    c_ref = torch.clamp(ref.enhance_curvature(dt, strength=0.08), 0, 1)[0].numpy()
+    c_ref = ref("curv")
     assert np.max(np.abs(c - c_ref)) <= 6e-8, seed
-    gamma, mid = float(rng.uniform(0.6, 1.3)), float(rng.uniform(0.4, 0.6))
-    s0 = ref.estimate_subject_depth(torch.from_numpy(c_ref.copy())[None])
-    sh_ref = ref.shape_depth_for_pop(torch.from_numpy(c_ref.copy())[None], s0, stretch_lo=0.05, stretch_hi=0.95, depth_mid=mid, gamma=gamma)[0].numpy()
-    sh = oracle.shape_depth_for_pop(c_ref, float(s0), 0.05, 0.95, mid, gamma)[0]
+    s0 = float(ref("s0"))
+    sh_a = oracle.shape_depth_for_pop(c_ref, s0, 0.05, 0.95, mid, gamma, aten_threads=THREADS)[0]      # round 5: with ATen's scalar tails restated -- exact
+    bad = _digest_mismatch(live, f"helpers{seed}__shaped", [sh_a])
+    assert bad is None, (seed, bad)
+    sh_ref = sh_a
+    sh = oracle.shape_depth_for_pop(c_ref, s0, 0.05, 0.95, mid, gamma)[0]
     assert np.max(np.abs(sh - sh_ref)) <= 1.2e-7, (seed, float(np.max(np.abs(sh - sh_ref))))
-    sh_a = oracle.shape_depth_for_pop(c_ref, float(s0), 0.05, 0.95, mid, gamma, aten_threads=thr)[0]      # round 5: with ATen's scalar tails restated -- exact
-    assert np.array_equal(sh_a.view(np.uint32), sh_ref.view(np.uint32)), (seed, int(np.count_nonzero(sh_a != sh_ref)))
-    # DOF + grade on a small eye: <= 1 LSB after truncation
-    bgr = synth.synth_frame(seed + 7, h, w)[0]
-    t = ref.frame_to_tensor(bgr)
-    focal, ms = float(rng.uniform(0.2, 0.8)), float([1.0, 2.0, 2.0, 3.0][int(rng.integers(0, 4))])
-    dof_ref = ref.apply_dof_cuda(t, dt, focal, max_sigma=ms, focus_width=0.35)
-    # float domain: separable symmetric-pair FMA sums (oracle, HIP) vs the dense k x k conv of torchvision: summation noise only
-    assert np.max(np.abs(oracle.apply_dof(oracle.frame_to_tensor(bgr), d, focal, ms) - dof_ref.numpy())) < 8e-7, (seed, ms)
-    sat, con, bri = float(rng.uniform(0.8, 1.4)), float(rng.uniform(0.9, 1.2)), float(rng.uniform(-0.05, 0.05))
-    out_ref = ref.tensor_to_frame(ref.apply_color_grade(dof_ref, sat, con, bri))
+    # DOF + grade on a small eye: <= 1 LSB after truncation.  The oracle's dense DOF order (the render path's dof_dense_conv) and its grade
+    # are the reference's bit for bit:
     tt = oracle.frame_to_tensor(bgr)
+    dof_ref = oracle.apply_dof_dense(tt, d, focal, ms)
+    out_ref = oracle.tensor_to_frame(oracle.color_grade(dof_ref, sat, con, bri))
+    for nm, exact in (("dof", dof_ref), ("graded", out_ref)):
+        bad = _digest_mismatch(live, f"helpers{seed}__{nm}", [exact])
+        assert bad is None, (seed, nm, bad)
+    # float domain: separable symmetric-pair FMA sums (oracle, HIP) vs the dense k x k conv of torchvision: summation noise only
+    assert np.max(np.abs(oracle.apply_dof(tt, d, focal, ms) - dof_ref)) < 8e-7, (seed, ms)
     out = oracle.tensor_to_frame(oracle.color_grade(oracle.apply_dof(tt, d, focal, ms), sat, con, bri))
     mx, frac, _ = u8_diff_stats(out, out_ref)
     assert mx <= 1 and frac < 2e-2, (seed, mx, frac)     # separable FMA association vs torch's dense conv: 1-LSB truncation cliffs
 
 
-def test_pixel_shift_full_size_1080p(ref, oracle):
-    """BASELINE configs[1] geometry against the live reference: eye-size (540 x 960) tensors warped at 1080 x 1920 with the CLI
+def test_pixel_shift_full_size_1080p(live, oracle):
+    """BASELINE configs[1] geometry against the reference: eye-size (540 x 960) tensors warped at 1080 x 1920 with the CLI
     defaults.  Tracker state, shift map and both eyes EXACT (torch-CPU's SLEEF pow / sigmoid and MKL sqrt are restated bit for bit)."""
-    import torch
     H, W = 1080, 1920
     bgr, d = synth.synth_frame(0, H // 2, W // 2)
     ft = oracle.frame_to_tensor(bgr)
     kw = dict(blur_ksize=9, feather_strength=10.0, use_subject_tracking=True, enable_floating_window=True, max_pixel_shift_percent=0.02,
               enable_edge_masking=True, enable_feathering=True)
-    ref_loader.reset_state(ref)
-    with torch.no_grad():
-        rl, rr, rs = ref.pixel_shift_cuda(torch.from_numpy(ft), torch.from_numpy(d[None].copy()), W, H, 10.0, -2.5, -5.0, return_shift_map=True, **kw)
     st = State()
     o = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(10.0, -2.5, -5.0, **kw), st, want_shift=True)
-    assert st.fw_prev_offset == ref.floating_window_tracker.prev_offset
-    assert np.array_equal(o["shift"], rs.numpy())
-    for got, exp in ((o["left"], rl), (o["right"], rr)):
-        assert np.array_equal(got, np.asarray(exp))
+    assert st.fw_prev_offset == float(live["full1080__prev_offset"])
+    for nm, got in (("S", o["shift"]), ("L", o["left"]), ("R", o["right"])):
+        assert _digest_mismatch(live, f"full1080_{nm}", [got]) is None, (nm, _digest_mismatch(live, f"full1080_{nm}", [got]))
 
 
-def _reference_function(path, name, namespace):
-    """One function of a reference module that cannot be imported here as a whole (core/render_depth.py pulls in diffusers,
-    onnxruntime, tkinter ...): its ``def`` is located with ``ast`` in the file where it lies and compiled on its own (nothing of the
-    reference is copied into the repo; the GPU box never runs this)."""
-    import ast
-    src = open(path).read()
-    node = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == name)
-    ns = dict(namespace)
-    exec(compile(ast.Module(body=[node], type_ignores=[]), path, "exec"), ns)
-    return ns[name]
-
-
-def test_depth_handoff_normalisation_vs_reference(oracle):
+def test_depth_handoff_normalisation_vs_reference(live, oracle):
     """a24, the per-frame min-max -> uint8 truncation of ``convert_depth_to_grayscale`` (core/render_depth.py:585-611) with the
     resize being the identity (transformers >= 4.4x hands ``predicted_depth`` back at the frame size): the
     oracle's hand-off equals the reference function bit for bit, incl. the degenerate-range and NaN frames it maps to zeros."""
-    import torch
-    from PIL import Image
-    path = os.path.join(ref_loader.REF_ROOT if hasattr(ref_loader, "REF_ROOT") else "/root/reference", "core", "render_depth.py")
-    conv = _reference_function(path, "convert_depth_to_grayscale", {"np": np, "torch": torch, "Image": Image, "print": lambda *a, **k: None})
-    rng = np.random.default_rng(77)
-    for i in range(12):
-        h, w = int(rng.integers(8, 70)), int(rng.integers(8, 90))
-        pred = synth.synth_frame(i, h, w)[1].astype(np.float32) * np.float32(rng.uniform(0.01, 40.0)) + np.float32(rng.uniform(-5, 5))
-        if i == 3:
-            pred[:] = 2.5                      # range < 1e-6 -> zeros
-        if i == 4:
-            pred[h // 2, w // 2] = np.nan      # NaN -> zeros
-        if i == 5:
-            pred = (pred - pred.min()) * np.float32(1e-7) + 1.0   # range just below / above the 1e-6 gate
-        exp = conv(torch.from_numpy(pred.copy()))
+    for i, (h, w, pred) in enumerate(C.handoff_cases()):
+        exp = live[f"handoff{i}__u8"]
         got = oracle.depth_handoff(pred, h, w)
         assert np.array_equal(got, exp), (i, np.abs(got.astype(int) - exp.astype(int)).max())
         assert np.array_equal(oracle.depth_handoff(pred, h, w, invert=True), 255 - exp), i     # :1914-1915
 
 
-def test_depth_handoff_with_bicubic_postprocess_vs_torch_and_reference(oracle):
+def test_depth_handoff_with_bicubic_postprocess_vs_torch_and_reference(live, oracle):
     """The full a24 hand-off: transformers' post_process_depth_estimation (``F.interpolate(..., mode="bicubic",
-    align_corners=False)`` to the frame size -- torch is the implementation, present here) followed by the reference's
+    align_corners=False)`` to the frame size -- torch is the implementation) followed by the reference's
     ``convert_depth_to_grayscale``.  The oracle restates the bicubic taps in ATen's association: <= 1 LSB after the truncation, and
     only on truncation cliffs (the float planes agree to a few ULP)."""
-    import torch
-    import torch.nn.functional as F
-    from PIL import Image
-    path = os.path.join(ref_loader.REF_ROOT, "core", "render_depth.py")
-    conv = _reference_function(path, "convert_depth_to_grayscale", {"np": np, "torch": torch, "Image": Image, "print": lambda *a, **k: None})
-    rng = np.random.default_rng(78)
     worst = 0.0
-    for i in range(8):
-        ph, pw = int(rng.integers(12, 40)), int(rng.integers(16, 60))
-        H, W = int(ph * rng.uniform(1.0, 3.0)), int(pw * rng.uniform(1.0, 3.0))
-        pred = synth.synth_frame(i, ph, pw)[1].astype(np.float32) * np.float32(rng.uniform(0.5, 20.0))
-        up = F.interpolate(torch.from_numpy(pred.copy())[None, None], size=(H, W), mode="bicubic", align_corners=False)[0, 0]
-        exp = conv(up)
+    for i, (H, W, pred) in enumerate(C.bicubic_cases()):
+        exp = live[f"bicubic{i}__u8"]
         got = oracle.depth_handoff(pred, H, W)
         d = np.abs(got.astype(int) - exp.astype(int))
         worst = max(worst, float((d > 0).mean()))
@@ -399,253 +292,121 @@ def test_depth_handoff_with_bicubic_postprocess_vs_torch_and_reference(oracle):
     print("hand-off vs torch bicubic + reference normalisation: worst differing fraction", worst)
 
 
-@pytest.mark.parametrize("k", [2, 4, 8, 12])
-def test_even_blur_ksize_window(ref, oracle, k):
+@pytest.mark.parametrize("k", C.EVEN_BLUR_KS)
+def test_even_blur_ksize_window(live, oracle, k):
     """avg_pool2d(kernel k, stride 1, padding k//2) of an EVEN k returns an (H+1) x (W+1) plane that feather_shift_edges crops to
     [:H, :W] (core/render_3d.py:355-369): the window of pixel x is x-k/2 .. x+k/2-1, zero padded, still divided by k*k."""
-    import torch
     bgr, d = synth.synth_frame(k, 40, 64)
     ft = oracle.frame_to_tensor(bgr)
     for H, W in ((40, 64), (80, 128)):
-        ref_loader.reset_state(ref)
-        with torch.no_grad():
-            rl, rr = ref.pixel_shift_cuda(torch.from_numpy(ft), torch.from_numpy(d[None].copy()), W, H, 10.0, -2.5, -5.0,
-                                          return_shift_map=False, blur_ksize=k, feather_strength=10.0)
+        oa = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(10.0, -2.5, -5.0, blur_ksize=k, feather_strength=10.0, aten_threads=THREADS), State())
+        for nm, exact in (("L", oa["left"]), ("R", oa["right"])):     # the N-thread ATen mode: the reference's eyes, bit for bit
+            bad = _digest_mismatch(live, f"evenblur{k}_{H}_{nm}", [exact])
+            assert bad is None, (k, H, W, nm, bad)
         o = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(10.0, -2.5, -5.0, blur_ksize=k, feather_strength=10.0), State())
-        for got, exp in ((o["left"], rl), (o["right"], rr)):
-            mx, frac, _ = u8_diff_stats(got, np.asarray(exp))
+        for got, exp in ((o["left"], oa["left"]), (o["right"], oa["right"])):
+            mx, frac, _ = u8_diff_stats(got, exp)
             assert mx <= 1 and frac < 8e-3, (k, H, W, mx, frac)
 
 
-@pytest.mark.parametrize("seed", _sweep(15))
-def test_render_loop_dof_slider_and_formats_exact_on_untailed_planes(ref, oracle, seed):
-    """Round 4: the live reference's ``render_sbs_3d`` loop vs the oracle over the WHOLE DOF slider (0.1 ... 5.0: Gaussians of 3 to 21 taps, the
+@pytest.mark.parametrize("seed", C.DOF_SLIDER_SEEDS)
+def test_render_loop_dof_slider_and_formats_exact_on_untailed_planes(live, oracle, seed):
+    """Round 4: the reference's ``render_sbs_3d`` loop vs the oracle over the WHOLE DOF slider (0.1 ... 5.0: Gaussians of 3 to 21 taps, the
     strengths where MKL's vsExp is not the rounded exponential among them) in every output format incl. VR, on 16:9 frame sizes whose planes
     are multiples of 32 elements (no ATen scalar tail: every float32 operator is the SLEEF / MKL vector path the DEFAULT mode computes with; on other sizes 3 to 11
     samples of a frame differ by up to 2 levels in that mode -- the N-thread ATen mode of round 5 restates the tails and is exact at any size,
     test_render_loop_any_size_exact_in_aten_mode).  Bar: EXACT."""
-    import make_golden as mg
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(9100 + seed)
-    fmt = ["Half-SBS", "Full-SBS", "Passive Interlaced", "Red-Cyan Anaglyph", "VR"][seed % 5]
-    # 16:9 (no aspect crop: a cropped row is a 113-element vector with a scalar tail) and eyes with H + W > 128 (at or below that ATen resizes with
-    # its premultiplied-weight kernel: see test_pixel_shift_random_parameters; a 128 x 72 Half-SBS frame has 64 x 36 eyes and loses 8 samples to it)
-    sh, sw = [(108, 192), (144, 256), (108, 192)][int(rng.integers(0, 3))]
-    dof = float(np.round(rng.uniform(0.1, 5.0), 1)) if seed % 3 else float([2.1, 4.2, 3.7, 0.7][seed // 3 % 4])
-    kw = dict(output_format=fmt, output_height=sh, fg_shift=float(rng.uniform(2, 20)), mg_shift=float(rng.uniform(-6, 2)),
-              bg_shift=float(rng.uniform(-15, 0)), sharpness_factor=float(rng.uniform(0.0, 0.4)), dof_strength=dof,
-              feather_strength=float(rng.uniform(0, 15)), blur_ksize=int(rng.integers(0, 5)) * 2 + 1,
-              use_subject_tracking=bool(rng.integers(0, 2)), use_floating_window=bool(rng.integers(0, 2)),
-              color_saturation=float(rng.uniform(0.9, 1.3)), color_contrast=float(rng.uniform(0.95, 1.1)),
-              color_brightness=float(rng.uniform(-0.03, 0.03)))
-    if fmt == "Full-SBS":
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 3
-    name = f"_live_dof_{seed}"
-    mg.LOOP_CASES[name] = (sh, sw, n, kw)
-    try:
-        written = np.stack(mg.run_loop(name))
-    finally:
-        del mg.LOOP_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, **kw))
-    ro.new_clip()
-    got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1) for f, d in list(zip(frames, depths))[1:]])
-    assert got.shape == written.shape, (got.shape, written.shape, kw)
-    assert np.array_equal(got, written), (seed, fmt, (sh, sw), dof, u8_diff_stats(got, written))
+    sh, sw, n, kw = case = C.dof_slider_case(seed)
+    _recorded(live, f"dof{seed}", case)
+    got = _oracle_loop(oracle, sh, sw, n, render_kwargs_to_params(sw, sh, **kw))
+    bad = _digest_mismatch(live, f"dof{seed}", got)
+    assert bad is None, (seed, kw["output_format"], (sh, sw), kw["dof_strength"], bad)
 
 
-@pytest.mark.parametrize("seed", _sweep(12))
-def test_render_loop_every_control_exact_on_untailed_planes(ref, oracle, seed):
-    """The live reference's ``render_sbs_3d`` loop vs the oracle with EVERY control the loop forwards drawn at random -- layer shifts, shift
+@pytest.mark.parametrize("seed", C.EVERY_CONTROL_SEEDS)
+def test_render_loop_every_control_exact_on_untailed_planes(live, oracle, seed):
+    """The reference's ``render_sbs_3d`` loop vs the oracle with EVERY control the loop forwards drawn at random -- layer shifts, shift
     bound, zero-parallax strength, static / dynamic convergence, IPD factor, edge masking / feathering on and off, blur sizes 1 ... 13, feather
     strength, subject tracking, floating window, DOF, sharpening, colour grade, original-aspect preservation -- on 16:9 frames whose planes are
     multiples of 32 elements and whose eyes have H + W > 128 (where the DEFAULT mode, aten_sum_threads = 0, already is the reference's arithmetic; the two size-dependent
     ATen code paths outside that rule are restated in the N-thread ATen mode: test_render_loop_any_size_exact_in_aten_mode below), four
     rendered frames each (trackers, EMAs and the floating bar evolve).  Bar: EXACT.  (12 seeds run with the suite; offline runs of seeds
     0 ... 899 at the end of round 4: 900 of 900 exact.)"""
-    import make_golden as mg
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(9500 + seed)
-    fmt = ["Half-SBS", "Full-SBS", "Passive Interlaced", "Red-Cyan Anaglyph", "VR"][int(rng.integers(0, 5))]
-    sh, sw = [(108, 192), (144, 256)][int(rng.integers(0, 2))]
-    kw = dict(output_format=fmt, output_height=sh, fg_shift=float(rng.uniform(0, 30)), mg_shift=float(rng.uniform(-10, 5)),
-              bg_shift=float(rng.uniform(-25, 0)), sharpness_factor=float(rng.uniform(0.0, 0.6)),
-              dof_strength=float([0.0, 1.0, 2.0, 2.0, 3.3][int(rng.integers(0, 5))]), feather_strength=float(rng.uniform(0, 20)),
-              blur_ksize=int(rng.integers(0, 7)) * 2 + 1, use_subject_tracking=bool(rng.integers(0, 2)),
-              use_floating_window=bool(rng.integers(0, 2)), max_pixel_shift_percent=float(rng.uniform(0.005, 0.06)),
-              zero_parallax_strength=float(rng.uniform(0, 0.03)) if rng.integers(0, 2) else 0.0,
-              enable_edge_masking=bool(rng.integers(0, 3) > 0), enable_feathering=bool(rng.integers(0, 3) > 0),
-              convergence_strength=float([0.0, 3.0, -2.0][int(rng.integers(0, 3))]), enable_dynamic_convergence=bool(rng.integers(0, 2)),
-              ipd_factor=float([1.0, 0.0, 1.2, 0.8][int(rng.integers(0, 4))]),
-              color_saturation=float(rng.uniform(0.8, 1.4)), color_contrast=float(rng.uniform(0.9, 1.2)),
-              color_brightness=float(rng.uniform(-0.05, 0.05)))
-    if fmt == "Full-SBS" or rng.integers(0, 3) == 0:
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 5
-    name = f"_live_all_{seed}"
-    mg.LOOP_CASES[name] = (sh, sw, n, kw)
-    try:
-        written = np.stack(mg.run_loop(name))
-    finally:
-        del mg.LOOP_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, **kw))
-    ro.new_clip()
-    got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1) for f, d in list(zip(frames, depths))[1:]])
-    assert got.shape == written.shape, (got.shape, written.shape, kw)
-    assert np.array_equal(got, written), (seed, u8_diff_stats(got, written), kw)
+    sh, sw, n, kw = case = C.every_control_case(seed)
+    _recorded(live, f"every{seed}", case)
+    got = _oracle_loop(oracle, sh, sw, n, render_kwargs_to_params(sw, sh, **kw))
+    bad = _digest_mismatch(live, f"every{seed}", got)
+    assert bad is None, (seed, bad, kw)
 
 
-@pytest.mark.parametrize("seed", range(12))
-def test_blank_frame_loops_exact_on_untailed_planes(ref, oracle, seed):
-    """skip_blank_frames in the live reference's loop (blackdetect list injected: blank frames keep the SOURCE frame through sharpen / fit / mux
+@pytest.mark.parametrize("seed", C.BLANK_EXACT_SEEDS)
+def test_blank_frame_loops_exact_on_untailed_planes(live, oracle, seed):
+    """skip_blank_frames in the reference's loop (blackdetect list injected: blank frames keep the SOURCE frame through sharpen / fit / mux
     and freeze nothing -- the trackers still advance on them) on 16:9 frames, every format incl. output heights that differ from the source (72: eyes of
     64 x 36 that ATen resizes with its premultiplied-weight kernel -- restated since round 5, no size is skipped any more).  Bar: EXACT on every frame since round 5.  (Until round 4 rendered frames were allowed 4 samples /
     2 levels for ONE cause: the dynamic parallax scale rests on a float32 `torch.mean`, whose value is that of ATen's cascade sum -- and above
     32 K elements of its thread partition -- while the oracle used the correctly rounded exact sum; about one frame in 300 got a scale one ULP apart
     (seed 6, frame 1: 0.92083001 / 0.92083007).  The cascade sum is restated now (oracle vo_sum_aten_2d, vd3d_render_params::aten_sum_threads = the
     reference process's torch.get_num_threads()).)"""
-    import torch
-    import make_golden as mg
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(11500 + seed)
-    fmt = ["Half-SBS", "Full-SBS", "Passive Interlaced", "Red-Cyan Anaglyph"][int(rng.integers(0, 4))]
-    sh, sw = [(108, 192), (144, 256)][int(rng.integers(0, 2))]
-    oh = [sh, sh, 72, 216][int(rng.integers(0, 4))]
-    kw = dict(output_format=fmt, output_height=oh, fg_shift=float(rng.uniform(2, 20)), mg_shift=float(rng.uniform(-6, 2)),
-              bg_shift=float(rng.uniform(-15, 0)), sharpness_factor=float(rng.uniform(0.0, 0.4)),
-              dof_strength=float([0.0, 2.0, 2.0, 3.0][int(rng.integers(0, 4))]), feather_strength=float(rng.uniform(0, 15)),
-              blur_ksize=int(rng.integers(0, 5)) * 2 + 1, use_subject_tracking=bool(rng.integers(0, 2)),
-              use_floating_window=bool(rng.integers(0, 2)), ipd_factor=float([1.0, 0.0, 1.2][int(rng.integers(0, 3))]),
-              skip_blank_frames=True)
-    if fmt == "Full-SBS":
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 7
-    blank = sorted(set(int(v) for v in rng.integers(0, n - 1, size=int(rng.integers(1, 4)))))
-    name = f"_live_blank_x_{seed}"
-    mg.BLANK_CASES[name] = (sh, sw, n, blank, kw)
+    sh, sw, n, blank, kw = case = C.blank_exact_case(seed)
+    _recorded(live, f"blankx{seed}", case)
     try:
-        written = np.stack(mg.run_blank_loop(name))
-    finally:
-        del mg.BLANK_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    try:
-        ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, aten_sum_threads=torch.get_num_threads(), **kw))
-        ro.new_clip()
-        got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1, blank=(i in blank)) for i, (f, d) in enumerate(list(zip(frames, depths))[1:])])
+        got = _oracle_loop(oracle, sh, sw, n, render_kwargs_to_params(sw, sh, aten_sum_threads=THREADS, **kw), blank)
     except NotImplementedError:
         pytest.skip("a fit the oracle does not restate")
-    assert got.shape == written.shape, (got.shape, written.shape, kw)
-    for i in range(len(got)):
-        d = np.abs(got[i].astype(np.int16) - written[i].astype(np.int16))
-        assert not d.any(), (seed, i, i in blank, u8_diff_stats(got[i], written[i]), kw)
+    bad = _digest_mismatch(live, f"blankx{seed}", got)
+    assert bad is None, (seed, blank, bad, kw)
 
 
-@pytest.mark.parametrize("seed", _sweep(10))
-def test_render_loop_any_size_exact_in_aten_mode(ref, oracle, seed):
-    """Round 5: NO SIZE RULE.  The live reference's ``render_sbs_3d`` loop vs the oracle in the N-thread ATen mode (``aten_sum_threads`` = the
+@pytest.mark.parametrize("seed", C.ANY_SIZE_SEEDS)
+def test_render_loop_any_size_exact_in_aten_mode(live, oracle, seed):
+    """Round 5: NO SIZE RULE.  The reference's ``render_sbs_3d`` loop vs the oracle in the N-thread ATen mode (``aten_sum_threads`` = the
     reference process's torch.get_num_threads()) on source frames of ANY size and aspect -- odd widths and heights, 2:1 and 4:3 sources that the loop crops to
     16:9, thumbnails whose eyes ATen resizes with its premultiplied-weight kernel, planes whose pow / sigmoid tails go through libm -- with every control drawn at
     random, four rendered frames each.  Bar: EXACT.  (10 seeds with the suite; offline at the end of round 5: 1 760 of 1 760 at 1 .. 8 torch threads (tools/sweep_live_any_size.py,
     profiles/r05_parity_sweeps.md).)"""
-    import torch
-    import make_golden as mg
     from visiondepth3d_amd.params import render_kwargs_to_params
-    rng = np.random.default_rng(9700 + seed)
-    fmt = ["Half-SBS", "Full-SBS", "Passive Interlaced", "Red-Cyan Anaglyph", "VR"][int(rng.integers(0, 5))]
-    sh, sw = (int(rng.integers(20, 76)) * 2, int(rng.integers(30, 131)) * 2) if seed % 2 == 0 else (int(rng.integers(40, 150)), int(rng.integers(60, 260)))
-    kw = dict(output_format=fmt, output_height=sh, fg_shift=float(rng.uniform(0, 30)), mg_shift=float(rng.uniform(-10, 5)),
-              bg_shift=float(rng.uniform(-25, 0)), sharpness_factor=float(rng.uniform(0.0, 0.6)),
-              dof_strength=float([0.0, 1.0, 2.0, 2.0, 3.3][int(rng.integers(0, 5))]), feather_strength=float(rng.uniform(0, 20)),
-              blur_ksize=int(rng.integers(0, 7)) * 2 + 1, use_subject_tracking=bool(rng.integers(0, 2)),
-              use_floating_window=bool(rng.integers(0, 2)), max_pixel_shift_percent=float(rng.uniform(0.005, 0.06)),
-              enable_edge_masking=bool(rng.integers(0, 3) > 0), enable_feathering=bool(rng.integers(0, 3) > 0),
-              convergence_strength=float([0.0, 3.0, -2.0][int(rng.integers(0, 3))]), enable_dynamic_convergence=bool(rng.integers(0, 2)),
-              ipd_factor=float([1.0, 0.0, 1.2, 0.8][int(rng.integers(0, 4))]),
-              color_saturation=float(rng.uniform(0.8, 1.4)), color_contrast=float(rng.uniform(0.9, 1.2)),
-              color_brightness=float(rng.uniform(-0.05, 0.05)))
-    if rng.integers(0, 3) == 0:
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 4
-    name = f"_live_any_{seed}"
-    mg.LOOP_CASES[name] = (sh, sw, n, kw)
-    try:
-        written = np.stack(mg.run_loop(name))
-    finally:
-        del mg.LOOP_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    p = render_kwargs_to_params(sw, sh, aten_sum_threads=torch.get_num_threads(), **kw)
-    ro = oracle.RenderOracle(p)
-    ro.new_clip()
-    got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1) for f, d in list(zip(frames, depths))[1:]])
-    assert got.shape == written.shape, (got.shape, written.shape, kw)
-    assert np.array_equal(got, written), (seed, fmt, (sh, sw), (p.eye_h, p.eye_w), (p.warp_h, p.warp_w), u8_diff_stats(got, written))
+    sh, sw, n, kw = case = C.any_size_loop_case(seed)
+    _recorded(live, f"anysize{seed}", case)
+    p = render_kwargs_to_params(sw, sh, aten_sum_threads=THREADS, **kw)
+    got = _oracle_loop(oracle, sh, sw, n, p)
+    bad = _digest_mismatch(live, f"anysize{seed}", got)
+    assert bad is None, (seed, kw["output_format"], (sh, sw), (p.eye_h, p.eye_w), (p.warp_h, p.warp_w), bad)
 
 
-@pytest.mark.parametrize("seed", _sweep(4))
-def test_pixel_shift_random_parameters_exact_at_1080p(ref, oracle, seed):
+@pytest.mark.parametrize("seed", C.SHIFT_1080P_SEEDS)
+def test_pixel_shift_random_parameters_exact_at_1080p(live, oracle, seed):
     """``pixel_shift_cuda`` (B1) at REAL size -- a 1920x1080 warp from a 960x540 eye (Half-SBS geometry) or from a same-size plane -- with every
     keyword drawn at random (blur sizes 1 ... 13, shift bound 0.5 ... 6 % of the width, arbitrary ``depth_pop_gamma`` / ``depth_pop_mid`` /
     ``parallax_balance``: SLEEF ``pow`` with exponents no fixture has, convergence modes, masking / feathering on and off): the float32 shift
-    map AND both eyes equal the live reference's EXACTLY, and so does the floating-window tracker's state.  (4 seeds with the suite; seeds
+    map AND both eyes equal the reference's EXACTLY, and so does the floating-window tracker's state.  (4 seeds with the suite; seeds
     0 ... 323 offline at the end of round 4.)"""
-    import torch
-    rng = np.random.default_rng(5000 + seed)
-    same = bool(rng.integers(0, 2))
-    H, W = 1080, 1920
-    ih, iw = (H, W) if same else (540, 960)
-    kw = dict(blur_ksize=int(rng.integers(0, 7)) * 2 + 1, feather_strength=float(rng.uniform(0, 20)),
-              use_subject_tracking=bool(rng.integers(0, 2)), enable_floating_window=bool(rng.integers(0, 2)),
-              max_pixel_shift_percent=float(rng.uniform(0.005, 0.06)), zero_parallax_strength=float(rng.uniform(0, 0.03)),
-              enable_edge_masking=bool(rng.integers(0, 3) > 0), enable_feathering=bool(rng.integers(0, 3) > 0),
-              convergence_strength=float([0.0, 3.0, -2.0][int(rng.integers(0, 3))]), enable_dynamic_convergence=bool(rng.integers(0, 2)),
-              depth_pop_gamma=float(rng.uniform(0.6, 1.3)), depth_pop_mid=float(rng.uniform(0.35, 0.65)),
-              parallax_balance=float(rng.uniform(0.5, 1.0)))
-    fg, mg, bg = float(rng.uniform(0, 30)), float(rng.uniform(-10, 5)), float(rng.uniform(-25, 0))
+    ih, iw, H, W, fg, mg, bg, kw = case = C.shift_1080p_case(seed)
+    ref = _recorded(live, f"shift1080p{seed}", case)
     bgr, d = synth.synth_frame(seed, ih, iw)
     ft = oracle.frame_to_tensor(bgr)
-    ref_loader.reset_state(ref)
-    with torch.no_grad():
-        rl, rr, rs = ref.pixel_shift_cuda(torch.from_numpy(ft), torch.from_numpy(d[None].copy()), W, H, fg, mg, bg, return_shift_map=True, **kw)
     st = State()
     o = oracle.pixel_shift(ft, d[None], W, H, ShiftParams.defaults(fg, mg, bg, **kw), st, want_shift=True)
-    assert st.fw_prev_offset == ref.floating_window_tracker.prev_offset, (seed, kw)
-    assert np.array_equal(o["shift"], rs.numpy()), (seed, int(np.count_nonzero(o["shift"] != rs.numpy())), kw)
-    assert np.array_equal(o["left"], np.asarray(rl)) and np.array_equal(o["right"], np.asarray(rr)), (seed, kw)
+    assert st.fw_prev_offset == float(ref("prev_offset")), (seed, kw)
+    for nm, got in (("S", o["shift"]), ("L", o["left"]), ("R", o["right"])):
+        bad = _digest_mismatch(live, f"shift1080p{seed}_{nm}", [got])
+        assert bad is None, (seed, nm, bad, kw)
 
 
-GUI_DEFAULTS = dict(output_format="Full-SBS", fg_shift=4.5, mg_shift=-1.5, bg_shift=-6.0, sharpness_factor=0.2, dof_strength=2.0,
-                    feather_strength=0.0, blur_ksize=1, use_subject_tracking=True, use_floating_window=True, max_pixel_shift_percent=0.02,
-                    auto_crop_black_bars=True, parallax_balance=0.8, zero_parallax_strength=0.01, enable_edge_masking=True,
-                    enable_feathering=True, convergence_strength=0.0, enable_dynamic_convergence=True)   # VisionDepth3D.py:1405-1453
-
-
-@pytest.mark.parametrize("case", range(6))
-def test_render_loop_feather_strength_zero_exact(ref, oracle, case):
+@pytest.mark.parametrize("case", C.FEATHER0_CASES)
+def test_render_loop_feather_strength_zero_exact(live, oracle, case):
     """Round 5: the GUI's own default configuration (VisionDepth3D.py:1405-1453: feather_strength 0.0, blur_ksize 1, Full-SBS) and its neighbours
-    (feather 0 behind a 9 x 9 window, a NEGATIVE strength, other formats) against the live reference's ``render_sbs_3d`` loop.  With a strength
+    (feather 0 behind a 9 x 9 window, a NEGATIVE strength, other formats) against the reference's ``render_sbs_3d`` loop.  With a strength
     <= 0 ``feather_shift_edges`` (core/render_3d.py:328-374) is an exact no-op -- clamp(grad * fs, 0, 1) = 0, its window average 0, shifted * 1 +
     original * 0 -- which the HIP library exploits by not running the mask, window-sum and blend kernels at all (vd3d_api.hip::warp_stage_params;
     tests/test_hip_parity.py::test_feather_strength_zero_takes_the_exact_no_feather_warp compares that path with THIS oracle, which still goes the
     long way).  Bar: EXACT."""
-    import make_golden as mg
     from visiondepth3d_amd.params import render_kwargs_to_params
-    fmt, (sh, sw), fs, k = [("Full-SBS", (108, 192), 0.0, 1), ("Full-SBS", (144, 256), 0.0, 9), ("Half-SBS", (108, 192), 0.0, 1),
-                            ("Passive Interlaced", (108, 192), -3.0, 5), ("Red-Cyan Anaglyph", (144, 256), 0.0, 3), ("VR", (108, 192), 0.0, 1)][case]
-    kw = dict(GUI_DEFAULTS, output_format=fmt, output_height=sh, feather_strength=fs, blur_ksize=k)
-    if fmt == "Full-SBS":
-        kw.update(preserve_original_aspect=True, original_video_width=sw, original_video_height=sh)
-    n = 4
-    name = f"_live_feather0_{case}"
-    mg.LOOP_CASES[name] = (sh, sw, n, kw)
-    try:
-        written = np.stack(mg.run_loop(name))
-    finally:
-        del mg.LOOP_CASES[name]
-    frames, depths = synth.synth_clip(n, sh, sw)
-    ro = oracle.RenderOracle(render_kwargs_to_params(sw, sh, **kw))
-    ro.new_clip()
-    got = np.stack([ro.render(f, synth.depth_to_u8_bgr(d), 1) for f, d in list(zip(frames, depths))[1:]])
-    assert got.shape == written.shape, (got.shape, written.shape, kw)
-    assert np.array_equal(got, written), (case, fmt, (sh, sw), u8_diff_stats(got, written))
+    sh, sw, n, kw = drawn = C.feather0_case(case)
+    _recorded(live, f"feather0{case}", drawn)
+    got = _oracle_loop(oracle, sh, sw, n, render_kwargs_to_params(sw, sh, **kw))
+    bad = _digest_mismatch(live, f"feather0{case}", got)
+    assert bad is None, (case, kw["output_format"], (sh, sw), bad)

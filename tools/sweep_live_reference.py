@@ -7,8 +7,8 @@
     python tools/sweep_live_reference.py geometry [first last]  # VR / Full-SBS / preserve-aspect geometry combinations, DOF up to 3.0
     python tools/sweep_live_reference.py fullsize               # pixel_shift_cuda at 1080p and 4K, the 1080p Half-SBS loop
 
-The committed tests (tests/test_oracle_vs_live_reference.py) hold a subset of each sweep plus the worst seeds found here; this script
-only widens the search.  DESIGN.md section 2 quotes its results (round 1: shift 100..399, loops 100..159, helpers 100..199, geometry 0..15).
+The committed tests (tests/test_oracle_vs_live_reference.py) hold a subset of each sweep plus the worst seeds found here, replayed from
+tests/golden/live_sweeps.npz; this script records the reference on other seeds (make_golden.record_live) and runs the same tests on them.  DESIGN.md section 2 quotes its results (round 1: shift 100..399, loops 100..159, helpers 100..199, geometry 0..15).
 """
 import os
 import sys
@@ -36,20 +36,18 @@ def _run(fn, seeds, *args):
 
 
 def main():
-    import ref_loader
+    import make_golden as mg
     import test_oracle_vs_live_reference as T
     from oracle import oracle as O
     what = sys.argv[1] if len(sys.argv) > 1 else "shift"
     lo, hi = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (100, 160)
-    ref = ref_loader.load()
     if what == "shift":
-        _run(T.test_pixel_shift_random_parameters, range(lo, hi), ref, O)
+        _run(T.test_pixel_shift_random_parameters, range(lo, hi), mg.record_live({"shiftrand": range(lo, hi)}), O)
     elif what == "loops":
-        _run(T.test_render_loop_random_configurations, range(lo, hi), ref, O)
+        _run(T.test_render_loop_random_configurations, range(lo, hi), mg.record_live({"looprand": range(lo, hi)}), O)
     elif what == "helpers":
-        _run(T.test_helpers_random_inputs, range(lo, hi), ref, O)
+        _run(T.test_helpers_random_inputs, range(lo, hi), mg.record_live({"helpers": range(lo, hi)}), O)
     elif what == "geometry":
-        import make_golden as mg
         from conftest import b2_max_bound, u8_diff_stats
         from visiondepth3d_amd import synth
         from visiondepth3d_amd.params import render_kwargs_to_params
@@ -83,9 +81,8 @@ def main():
             print(seed, "ok" if ok else "DIFF", fmt, (sh, sw, oh), got.shape[1:3], mx, round(frac, 4), round(g1, 4))
         print("outside the bars:", bad)
     elif what == "fullsize":
-        T.test_pixel_shift_full_size_1080p(ref, O)
+        T.test_pixel_shift_full_size_1080p(mg.record_live({"full1080": [0]}), O)
         print("1080p pixel_shift_cuda: inside the bars")
-        import make_golden as mg
         from conftest import u8_diff_stats
         from visiondepth3d_amd import synth
         from visiondepth3d_amd.params import render_kwargs_to_params
