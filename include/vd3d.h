@@ -33,7 +33,8 @@ extern "C" {
 /* 6 (round 6): new entry points vd3d_gemm_x3_* / vd3d_attention_x3_* (no struct changed); vd3d_debug_tune answers only knobs 3 and 4 unless built with
  *    -DVD3D_DEV_KNOBS; aten_threads / aten_sum_threads accept 1 .. 1024.
  * 5 (round 5): vd3d_shift_params gained aten_threads / reserved0 at its end (vd3d_render_params embeds it: its later fields moved by 8 bytes); vd3d_torch_math_aten.
- * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout). */
+ * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
+ * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32. */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -442,6 +443,13 @@ int vd3d_nhwc_bias_act_f32(vd3d_ctx* ctx, const float* y, const float* bias_or_n
                            int64_t n_pix, int C, float* out, float* relu_out_or_null);
 int vd3d_upsample_bilinear_bias_nhwc_f32(vd3d_ctx* ctx, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C);
 int vd3d_dpt_head_tail_f32(vd3d_ctx* ctx, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, float* out);
+
+/* The reassemble stage's transposed convolutions of DPT-Large (DPTReassembleLayer.resize = ConvTranspose2d(C, C, kernel_size=s, stride=s, padding=0), s = 4 / 2):
+ * kernel == stride, so the windows do not overlap and the layer is a GEMM Y[p][(i, j, co)] = sum_ci X[p][ci] W[ci][co][i][j] (vd3d_gemm_x3 with the weight
+ * permuted to [(i, j, co)][ci]) followed by this scatter: y [P = B*H*W][s][s][C] float32 -> out NHWC [B][H*s][W*s][C] float32,
+ *   out[b][y*s + i][x*s + j][c] = y[(b*H + y)*W + x][i][j][c] + bias[c]   (an exact copy and one float32 add; bias_or_null == NULL: the copy alone).
+ * C a multiple of 4 and y / bias / out 16-byte aligned, else VD3D_E_UNSUPPORTED. */
+int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* ctx, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out);
 
 /* ---- preview visualisers: generate_preview_image, core/preview_utils.py:23-84, the exactly defined types.
  * left / right: uint8 BGR [h][w][3] eyes (outputs of vd3d_pixel_shift).  out: [h][w][3], except HSBS: [h][2*(w/2)][3].

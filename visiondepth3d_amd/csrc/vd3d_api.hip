@@ -1540,6 +1540,14 @@ VD3D_EXPORT int vd3d_dpt_head_tail_f32(vd3d_ctx* c, const float* y, const float*
   HIPCHK(hipGetLastError());
   return 0;
 }
+VD3D_EXPORT int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* c, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out) {
+  if (!c || !y || !out || B < 1 || H < 1 || W < 1 || s < 1 || C < 1) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depth_to_space_bias_f32(c->stream, y, bias_or_null, B, H, W, s, C, out))
+    return set_err(VD3D_E_UNSUPPORTED, "depth_to_space_bias: C %d not a multiple of 4, y / bias / out not 16-byte aligned, or a map too large for one grid", C);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 VD3D_EXPORT int vd3d_preview_image(vd3d_ctx* c, int type, const uint8_t* left_bgr, const uint8_t* right_bgr, int h, int w, uint8_t* out_bgr) {
   if (!c || !left_bgr || !right_bgr || !out_bgr || h < 1 || w < 1) return set_err(VD3D_E_INVALID, "bad argument");

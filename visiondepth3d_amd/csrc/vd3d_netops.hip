@@ -290,3 +290,32 @@ bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, con
     default: return false;
   }
 }
+
+// k_depth_to_space_bias: the scatter half of DPT's reassemble-stage ConvTranspose2d(C, C, kernel_size=s, stride=s) -- kernel == stride, so the layer is a GEMM
+// Y[p][(i, j, c)] (vd3d_gemm_x3) whose rows land in disjoint s x s output windows.  y [P = B*H*W][s][s][C] -> out NHWC [B][H*s][W*s][C], + bias[c]: an exact
+// copy and one float32 add.  One thread = 4 channels (16 B) of one OUTPUT pixel: stores are dense rows, loads are runs of s * C floats (one window row).
+__global__ __launch_bounds__(256) void k_depth_to_space_bias(const float4* __restrict__ y, const float4* __restrict__ bias, int H, int W, int s, int c4,
+                                                             long long total, float4* __restrict__ out) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % c4);
+  long long r = idx / c4;
+  const int ow = W * s, oh = H * s;
+  const int ox = (int)(r % ow); r /= ow;
+  const int oy = (int)(r % oh);
+  const long long b = r / oh;
+  const int py = oy / s, i = oy - py * s, px = ox / s, j = ox - px * s;
+  const long long p = (b * H + py) * W + px;
+  float4 v = y[((p * s + i) * s + j) * c4 + c];
+  if (bias) { const float4 bb = bias[c]; v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
+  out[idx] = v;
+}
+bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const float* bias, int B, int H, int W, int f, int C, float* out) {
+  if (C % 4 || B < 1 || H < 1 || W < 1 || f < 1) return false;
+  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(out)) & 15) return false;
+  const long long total = (long long)B * H * f * W * f * (C / 4);
+  if ((total + 255) / 256 > 0x7fffffffLL) return false;
+  hipLaunchKernelGGL(k_depth_to_space_bias, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float4*)y, (const float4*)bias, H, W, f, C / 4,
+                     total, (float4*)out);
+  return true;
+}

@@ -118,6 +118,32 @@ def depth_to_u8(pred: torch.Tensor, invert: bool = False) -> torch.Tensor:
     return 255 - u8 if invert else u8
 
 
+def conv_transpose_gemm_weight(w: torch.Tensor) -> torch.Tensor:
+    """ConvTranspose2d weight [C_in, C_out, s, s] (kernel == stride: non-overlapping windows) -> the GEMM weight [(i, j, c_out)][c_in] of
+    Y[p][(i, j, co)] = sum_ci X[p][ci] W[ci][co][i][j]; vd3d_depth_to_space_bias_nhwc_f32 then scatters Y's rows to their s x s windows."""
+    return w.detach().permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous()
+
+
+def _head_tail_operands(conv3: torch.nn.Conv2d):
+    """() -> (w3, b3) of the head's 1x1 convolution to one channel, for vd3d_dpt_head_tail_f32.  The scalar bias is read on the host ONCE per parameter
+    version (no per-call sync); an in-place update of the parameters (load_state_dict, .copy_) bumps their version counters and is picked up at the
+    next call."""
+    tail = {"key": None, "w3": None, "b3": 0.0}
+
+    def operands():
+        w, b = conv3.weight, conv3.bias
+        try:
+            key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
+        except RuntimeError:   # inference tensors (created / loaded under torch.inference_mode()) track no version counter: immutable outside
+            key = (w.data_ptr(), b.data_ptr())   # inference mode, so the storage address identifies the value (ADVICE r5)
+        if tail["key"] != key:
+            tail["w3"] = w.detach().reshape(-1).contiguous()
+            tail["b3"] = float(b.detach().float().item())
+            tail["key"] = key
+        return tail["w3"], tail["b3"]
+    return operands
+
+
 _TUNABLE_DIR = None
 
 
@@ -156,6 +182,10 @@ class DepthPipe:
         folded into fc1's epilogue, and the attention in the same arithmetic (``vd3d_attention_x3``: both products split-bf16, float32 online softmax).
         ``"fp16x2"`` -- OPT-IN: the same kernels with every operand as TWO fp16 terms (22 significant bits, round to nearest) and three products per MAC
         -- half the matrix work of bf16x3; weights pre-scaled per row, activations must stay below 65 504 (include/vd3d.h).  gfx950 has no TF32 and its float32-input MFMA runs at 1/16 of the bf16 rate, which caps the default mode.
+        The split modes cover the DINOv2 family (Depth-Anything V1 / V2, Distill-Any-Depth) and DPT-Large (a plain-ViT ``DPTForDepthEstimation`` with
+        readout_type="project"; its readout / 1x1 projections and the transposed convolutions of the reassemble stage go on ``vd3d_gemm_x3`` too, see
+        ``_patch_dpt_vit_reassemble_head``).  Anything else -- DPT-Hybrid, BEiT / Swin backbones, ZoeDepth, DepthPro -- raises NotImplementedError; with
+        ``gemm="f32"`` a DPT model runs its stock module graph unchanged.
         ``renderer``: a ``visiondepth3d_amd.render_3d.Renderer`` on the SAME stream as the network (default stream); when given the
         image-processor front end, the residual-add + LayerNorm pairs and the DPT up-samplings run as fused HIP launches.
         ``model`` / ``processor``: an already constructed Hugging Face depth model and its image-processor constants
@@ -197,9 +227,10 @@ class DepthPipe:
         self.n_params = sum(p.numel() for p in self.model.parameters())
         self.renderer = renderer if (renderer is not None and self.device.type == "cuda") else None
         dino = self.arch == "da" and type(self.model.backbone).__name__ == "Dinov2Backbone"
-        if self.gemm != "f32" and not (dino and fuse_backbone):
-            raise NotImplementedError("gemm='bf16x3' / 'fp16x2' rewrite the fused DINOv2 backbone (Depth-Anything V1 / V2, Distill-Any-Depth with fuse_backbone=True); "
-                                      "this model runs its stock float32 graph -- nothing is substituted silently")
+        # dpt_vit: DPT-Large's rewrite runs (split modes only; arch stays "generic": gemm="f32" keeps the stock DPT module graph)
+        self.dpt_vit = False
+        if self.gemm != "f32" and self._split_scope(fuse_backbone) == "dpt-vit":
+            self._rewrite_dpt_vit()
         if dino:
             self._cache_position_embeddings()
             if fuse_backbone:
@@ -238,7 +269,8 @@ class DepthPipe:
         local-model branch, ``AutoModelForDepthEstimation.from_pretrained(checkpoint)`` + ``AutoProcessor.from_pretrained(checkpoint)``
         (core/render_depth.py:756-760).  DepthAnything / DINOv2 checkpoints (Depth-Anything V1 / V2, Distill-Any-Depth) then get the
         fused-weight rewrites (one QKV GEMM, LayerScale folded into the projections); any other depth architecture
-        (DPT / MiDaS 3.0, ZoeDepth ...) runs its stock module graph behind the same protocol."""
+        (DPT / MiDaS 3.0, ZoeDepth ...) runs its stock module graph behind the same protocol -- except that a plain-ViT DPT checkpoint
+        (Intel/dpt-large) with ``gemm="bf16x3" / "fp16x2"`` and a renderer in ``kw`` gets the split-mode rewrite (``__init__``)."""
         from transformers import AutoModelForDepthEstimation
         if not os.path.isdir(path):
             raise FileNotFoundError(f"{path}: not a local checkpoint folder (this build environment has no network)")
@@ -356,36 +388,25 @@ class DepthPipe:
                     return R.upsample_bilinear_bias(conv_nb(layer.projection, hidden_state), tgt, layer.projection.bias)
                 return layer.projection(up(hidden_state, tgt))
             layer.forward = fusion_fwd
+        if getattr(self, "dpt_vit", False):
+            self._patch_dpt_vit_reassemble_head(conv_nb, f32)
+            return
         head = self.model.head
-        tail = None
+        tail_operands = None
         if (f32 and isinstance(head.activation2, torch.nn.ReLU) and head.conv2.out_channels in (16, 32, 64) and head.conv3.kernel_size == (1, 1)
                 and head.conv2.bias is not None and head.conv3.bias is not None and head.conv1.bias is not None):
-            # conv3's scalar bias is read on the host ONCE per parameter version (no per-call sync); an in-place update of the parameters
-            # (load_state_dict, .copy_) bumps their version counters and is picked up at the next call
-            tail = {"key": None, "w3": None, "b3": 0.0}
-
-            def tail_operands():
-                w, b = head.conv3.weight, head.conv3.bias
-                try:
-                    key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
-                except RuntimeError:   # inference tensors (created / loaded under torch.inference_mode()) track no version counter: immutable outside
-                    key = (w.data_ptr(), b.data_ptr())   # inference mode, so the storage address identifies the value
-                if tail["key"] != key:
-                    tail["w3"] = w.detach().reshape(-1).contiguous()
-                    tail["b3"] = float(b.detach().float().item())
-                    tail["key"] = key
-                return tail["w3"], tail["b3"], float(head.max_depth)
+            tail_operands = _head_tail_operands(head.conv3)
 
         def head_fwd(hidden_states, patch_height, patch_width):
             x = hidden_states[head.head_in_index]
             size = (int(patch_height * head.patch_size), int(patch_width * head.patch_size))
-            if tail is not None and x.dtype == torch.float32:
+            if tail_operands is not None and x.dtype == torch.float32:
                 h = R.upsample_bilinear_bias(conv_nb(head.conv1, x.contiguous(memory_format=CL)), size, head.conv1.bias)
                 y = conv_nb(head.conv2, h)
                 if self._flop_count is not None:
                     self._flop_count[0] += 2.0 * y.numel() / y.shape[0]   # the 1x1 convolution to one channel inside the tail kernel
-                w3, b3, scale = tail_operands()
-                return R.dpt_head_tail(y, head.conv2.bias, w3, b3, scale)
+                w3, b3 = tail_operands()
+                return R.dpt_head_tail(y, head.conv2.bias, w3, b3, float(head.max_depth))
             h = up(head.conv1(x), size)
             h = head.conv3(head.activation1(head.conv2(h)))
             return (head.activation2(h) * head.max_depth).squeeze(dim=1)
@@ -400,6 +421,77 @@ class DepthPipe:
                 out.append(stage.layers[i](x))
             return out
         stage.forward = reassemble_fwd
+
+    def _patch_dpt_vit_reassemble_head(self, conv_nb, f32):
+        """DPT-Large's reassemble stage and head on the library path (split modes; called by _patch_dpt_upsampling, whose fusion-stage rewrite DPT shares):
+          * per hook, GELU(Linear_2C->C(cat(tokens, CLS))) as one linear_x3 with the GELU epilogue over the [B, T-1, 2C] rows, then the 1x1 projection
+            (C -> C_i) as a linear_x3 with its bias on the same rows -- [B, T-1, C_i] is NHWC storage, handed on as a channels_last view;
+          * resize: hooks 0 / 1 (ConvTranspose2d, kernel == stride s) as a linear_x3 with the weight permuted to [(i, j, co)][ci] + the scatter / bias
+            launch vd3d_depth_to_space_bias_nhwc_f32; hook 2 identity; hook 3 (3 x 3 stride 2) the library convolution;
+          * head: conv1 bias-free with its bias inside the align_corners up-sampling, conv2 bias-free (vd3d_conv3x3_x2 in fp16x2 where its size rule allows),
+            vd3d_dpt_head_tail_f32 (scale 1) for the rest.
+        neck.convs (3 x 3, no bias, C_i -> 256) and the fusion stage's 256 -> 256 convolutions have 256 output channels, which vd3d_conv3x3_x2 does not
+        build: they stay library float32 convolutions, as for DA-V2-Large."""
+        R, gm, CL = self.renderer, self.gemm, torch.channels_last
+        stage, head = self.model.neck.reassemble_stage, self.model.head
+        hooks = []
+        for i, lay in enumerate(stage.layers):
+            rl, ract = stage.readout_projects[i][0], stage.readout_projects[i][1]
+            gelu = isinstance(ract, torch.nn.GELU) and getattr(ract, "approximate", "none") == "none" or type(ract).__name__ == "GELUActivation"
+            pw = lay.projection.weight
+            hk = dict(readout=(R.gemm_x3_pack(rl.weight, gm), rl.out_features, rl.bias, gelu, ract),
+                      proj=(R.gemm_x3_pack(pw.reshape(pw.shape[0], -1), gm), pw.shape[0], lay.projection.bias), resize=lay.resize, ct=None)
+            if isinstance(lay.resize, torch.nn.ConvTranspose2d):
+                hk["ct"] = (R.gemm_x3_pack(conv_transpose_gemm_weight(lay.resize.weight), gm), lay.resize.kernel_size[0])
+            hooks.append(hk)
+
+        def lin(t, img, n, bias, gelu=False, conv=True):
+            if conv and self._flop_count is not None:   # flops_per_frame: the 1x1 projections and transposed convolutions (EXECUTED: P x C_out x C_in) bypass
+                self._flop_count[0] += 2.0 * t.numel() / t.shape[0] * n   # the module hooks; the readout Linear is not a convolution (not counted, as in the stock graph)
+            return R.linear_x3(t, img, n, bias, gelu=gelu, mode=gm)
+
+        def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
+            out = []
+            for hk, hs in zip(hooks, hidden_states):
+                B, T, d = hs.shape
+                if patch_height is None or patch_width is None:   # the stock stage's square grid
+                    patch_height = patch_width = int((T - 1) ** 0.5)
+                gh, gw = int(patch_height), int(patch_width)
+                if gh * gw != T - 1:
+                    raise ValueError(f"{T - 1} patch tokens do not form a {gh} x {gw} grid")
+                img, n, bias, gelu, act = hk["readout"]
+                x = torch.cat((hs[:, 1:], hs[:, :1].expand(B, T - 1, d)), -1)
+                x = lin(x, img, n, bias, gelu=True, conv=False) if gelu else act(lin(x, img, n, bias, conv=False))
+                img, n, bias = hk["proj"]
+                x = lin(x, img, n, bias)                                                          # [B, T-1, C_i]
+                if hk["ct"] is not None:
+                    ct_img, s = hk["ct"]
+                    y = lin(x, ct_img, s * s * n, None)
+                    x = R.depth_to_space_bias(y.view(B * gh * gw, s * s * n), B, gh, gw, s, hk["resize"].bias)
+                else:
+                    x = x.view(B, gh, gw, n).permute(0, 3, 1, 2)   # NHWC storage, NCHW view: channels_last
+                    x = hk["resize"](x)                             # identity, or the library's 3 x 3 stride-2 convolution
+                out.append(x)
+            return out
+        stage.forward = reassemble_fwd
+
+        if not f32:   # VD3D_NECK_GLUE=0: the head's own module graph
+            return
+        conv1, _, conv2, _, conv3, _ = list(head.head)
+        tail_operands = _head_tail_operands(conv3)
+        in_index = self.model.config.head_in_index
+
+        def head_fwd(hidden_states):
+            x = hidden_states[in_index].contiguous(memory_format=CL)
+            size = (2 * x.shape[2], 2 * x.shape[3])   # nn.Upsample(scale_factor=2, align_corners=True)
+            h = R.upsample_bilinear_bias(conv_nb(conv1, x), size, conv1.bias)
+            y = conv_nb(conv2, h)
+            if self._flop_count is not None:
+                self._flop_count[0] += 2.0 * y.numel() / y.shape[0]   # the 1x1 convolution to one channel inside the tail kernel
+            w3, b3 = tail_operands()
+            return R.dpt_head_tail(y, conv2.bias, w3, b3, 1.0)
+        head.forward = head_fwd
+
 
     @torch.no_grad()
     def _fuse_backbone_layers(self):
@@ -442,39 +534,14 @@ class DepthPipe:
             n1, n2, act = layer.norm1, layer.norm2, layer.mlp.activation
             nxt = layers[li + 1].norm1 if li + 1 < len(layers) else None
             x3 = None
-            if self.gemm != "f32":   # weights split + packed once; exact GELU only (what DINOv2's MLP uses) goes into fc1's epilogue
-                gelu_ok = isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none" or type(act).__name__ == "GELUActivation"
-                gm = self.gemm
-                x3 = dict(qkv=(R.gemm_x3_pack(wqkv, gm), wqkv.shape[0]), wo=(R.gemm_x3_pack(wo, gm), wo.shape[0]),
-                          fc1=(R.gemm_x3_pack(fc1.weight, gm), fc1.weight.shape[0]), w2=(R.gemm_x3_pack(w2, gm), w2.shape[0]), gelu=bool(gelu_ok), mode=gm)
+            if self.gemm != "f32":
+                x3 = self._split_block(stash, pad_state, wqkv, bqkv, wo, bo, fc1.weight, fc1.bias, w2, b2, nh, hd, scaling, n1, n2, act, nxt)
 
             def fwd(x, wqkv=wqkv, bqkv=bqkv, wo=wo, bo=bo, fc1=fc1, w2=w2, b2=b2, nh=nh, hd=hd, scaling=scaling, n1=n1, n2=n2,
                     act=act, nxt=nxt, x3=x3):
-                B, T, d = x.shape
-                if x3 is not None and not (x.dtype == torch.float32 and x.is_contiguous() and d in (384, 768, 1024)):
-                    raise NotImplementedError(f"gemm={x3['mode']!r}: hidden size {d} / dtype {x.dtype} not built (float32, 384 / 768 / 1024) -- refusing to fall back silently")
                 if x3 is not None:
-                    lin = lambda t, key, bias, gelu=False: R.linear_x3(t if t.is_contiguous() else t.contiguous(), x3[key][0], x3[key][1], bias, gelu=gelu,
-                                                                       mode=x3["mode"])
-                    h = stash["h"] if stash["x"] is x else R.add_layernorm(x, None, n1)[1]
-                    stash["x"] = stash["h"] = None
-                    qkv = lin(h, "qkv", bqkv)
-                    if hd == 64 and not pad_state["T"]:   # the library's split-bf16 attention (every DINOv2 size has 64-wide heads)
-                        o = R.attention_x3(qkv, nh, scaling, mode=x3["mode"])
-                    else:
-                        qkv = qkv.view(B, T, 3, nh, hd)
-                        Tk = pad_state["T"] or T
-                        q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :Tk, 1].transpose(1, 2), qkv[:, :Tk, 2].transpose(1, 2)
-                        o = F.scaled_dot_product_attention(q, k, v, scale=scaling).transpose(1, 2).reshape(B, T, d)
-                    a = lin(o, "wo", bo)
-                    x, h = R.add_layernorm(x, a, n2)
-                    hid = lin(h, "fc1", fc1.bias, gelu=True) if x3["gelu"] else act(lin(h, "fc1", fc1.bias))
-                    m = lin(hid, "w2", b2)
-                    if nxt is None:
-                        return x + m
-                    x, hn = R.add_layernorm(x, m, nxt)
-                    stash["x"], stash["h"] = x, hn
-                    return x
+                    return x3(x)
+                B, T, d = x.shape
                 hip = R is not None and x.dtype in (torch.bfloat16, torch.float32) and x.is_contiguous() and d in (384, 768, 1024)
                 if hip:   # residual add + LayerNorm pairs as single HIP launches (vd3d_add_layernorm)
                     h = stash["h"] if stash["x"] is x else R.add_layernorm(x, None, n1)[1]
@@ -498,6 +565,126 @@ class DepthPipe:
                 return x
 
             layer.forward = fwd
+
+    def _split_block(self, stash, pad_state, wqkv, bqkv, wo, bo, w1, b1, w2, b2, nh, hd, scaling, n1, n2, act, nxt):
+        """``x -> block(x)`` for one pre-LayerNorm transformer block (Dinov2Layer, DPTViTLayer) in the split arithmetic of ``self.gemm``: the weights are split and
+        packed once; q / k / v as one GEMM, vd3d_attention_x3 on its output, the output projection, fc1 with the exact GELU in its epilogue (any other
+        activation runs behind it), fc2; both residual-add + LayerNorm pairs as vd3d_add_layernorm, the NEXT block's first LayerNorm (``nxt``) computed with
+        this block's second residual add and handed over through ``stash``.  Returns the residual stream, as the stock block does."""
+        R, gm = self.renderer, self.gemm
+        gelu_ok = isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none" or type(act).__name__ == "GELUActivation"
+        x3 = dict(qkv=(R.gemm_x3_pack(wqkv, gm), wqkv.shape[0]), wo=(R.gemm_x3_pack(wo, gm), wo.shape[0]),
+                  fc1=(R.gemm_x3_pack(w1, gm), w1.shape[0]), w2=(R.gemm_x3_pack(w2, gm), w2.shape[0]), gelu=bool(gelu_ok), mode=gm)
+
+        def lin(t, key, bias, gelu=False):
+            return R.linear_x3(t if t.is_contiguous() else t.contiguous(), x3[key][0], x3[key][1], bias, gelu=gelu, mode=gm)
+
+        def fwd(x):
+            B, T, d = x.shape
+            if not (x.dtype == torch.float32 and x.is_contiguous() and d in (384, 768, 1024)):
+                raise NotImplementedError(f"gemm={gm!r}: hidden size {d} / dtype {x.dtype} not built (float32, 384 / 768 / 1024) -- refusing to fall back silently")
+            h = stash["h"] if stash["x"] is x else R.add_layernorm(x, None, n1)[1]
+            stash["x"] = stash["h"] = None
+            qkv = lin(h, "qkv", bqkv)
+            if hd == 64 and not pad_state["T"]:   # the library's split-bf16 attention (every DINOv2 size and ViT-L/16 have 64-wide heads)
+                o = R.attention_x3(qkv, nh, scaling, mode=gm)
+            else:
+                qkv = qkv.view(B, T, 3, nh, hd)
+                Tk = pad_state["T"] or T
+                q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :Tk, 1].transpose(1, 2), qkv[:, :Tk, 2].transpose(1, 2)
+                o = F.scaled_dot_product_attention(q, k, v, scale=scaling).transpose(1, 2).reshape(B, T, d)
+            a = lin(o, "wo", bo)
+            x, h = R.add_layernorm(x, a, n2)
+            hid = lin(h, "fc1", b1, gelu=True) if x3["gelu"] else act(lin(h, "fc1", b1))
+            m = lin(hid, "w2", b2)
+            if nxt is None:
+                return x + m
+            x, hn = R.add_layernorm(x, m, nxt)
+            stash["x"], stash["h"] = x, hn
+            return x
+
+        return fwd
+
+    def _split_scope(self, fuse_backbone: bool = True) -> str:
+        """Which rewrite ``gemm="bf16x3" / "fp16x2"`` applies to this model: "dinov2" (DepthAnythingForDepthEstimation on Dinov2Backbone) or "dpt-vit"
+        (DPTForDepthEstimation on its plain ViT encoder with readout_type="project": DPT-Large).  Everything else raises NotImplementedError naming the model."""
+        m, what = self.model, f"{self.name!r} ({type(self.model).__name__})"
+        if self.arch == "da" and type(m.backbone).__name__ == "Dinov2Backbone" and fuse_backbone:
+            return "dinov2"
+        if type(m).__name__ != "DPTForDepthEstimation" or not fuse_backbone:
+            raise NotImplementedError(f"gemm={self.gemm!r}: {what} -- the split modes rewrite the fused DINOv2 backbone (Depth-Anything V1 / V2, Distill-Any-Depth) and the "
+                                      "plain-ViT DPT (DPT-Large), with fuse_backbone=True; this model runs its stock float32 graph -- nothing is substituted silently")
+        cfg = m.config
+
+        def refuse(why):
+            raise NotImplementedError(f"gemm={self.gemm!r}: {what}: {why} -- not built in the split modes; gemm='f32' runs the stock float32 graph")
+        if cfg.is_hybrid:
+            refuse("DPT-Hybrid (MiDaS 3.0 hybrid, Intel/dpt-hybrid-midas: BiT stem, identity readout on hooks 0 / 1)")
+        if getattr(m, "backbone", None) is not None or cfg.backbone_config is not None:
+            bname = type(m.backbone).__name__ if getattr(m, "backbone", None) is not None else cfg.backbone_config.model_type
+            refuse(f"a {bname} backbone (e.g. Intel/dpt-beit-large-512: BEiT's relative position bias has no input in vd3d_attention_x3)")
+        if cfg.readout_type != "project":
+            refuse(f"readout_type={cfg.readout_type!r} (only 'project' is built)")
+        if list(cfg.neck_ignore_stages or []):
+            refuse(f"neck_ignore_stages={cfg.neck_ignore_stages}")
+        if m.head.projection is not None:
+            refuse("a head projection (add_projection=True)")
+        if cfg.use_batch_norm_in_fusion_residual:
+            refuse("batch norm in the fusion residual units")
+        d, nh = int(cfg.hidden_size), int(cfg.num_attention_heads)
+        if d not in (384, 768, 1024) or d // nh != 64 or d % nh:
+            refuse(f"hidden size {d} with {nh} heads (built: 384 / 768 / 1024, 64-wide heads)")
+        for lay in m.neck.reassemble_stage.layers:
+            r = lay.resize
+            if isinstance(r, torch.nn.ConvTranspose2d) and not (r.kernel_size == r.stride and r.padding == (0, 0) and r.output_padding == (0, 0)
+                                                                 and r.dilation == (1, 1) and r.groups == 1):
+                refuse(f"a reassemble ConvTranspose2d with kernel {r.kernel_size} / stride {r.stride} / padding {r.padding} (built: kernel == stride, no padding)")
+        hs = list(m.head.head)
+        if not (len(hs) == 6 and isinstance(hs[1], torch.nn.Upsample) and isinstance(hs[3], torch.nn.ReLU) and isinstance(hs[5], torch.nn.ReLU)
+                and hs[4].kernel_size == (1, 1) and hs[2].out_channels in (16, 32, 64) and hs[1].scale_factor in (2, 2.0) and hs[1].align_corners):
+            refuse("a depth head other than DPT's [conv, Upsample x2, conv -> 16 / 32 / 64, ReLU, conv 1x1, ReLU]")
+        return "dpt-vit"
+
+    def _rewrite_dpt_vit(self):
+        """The split-mode rewrite of a plain-ViT DPTForDepthEstimation (DPT-Large; _split_scope has accepted it): position embeddings memoised, the ViT
+        layers on the split kernels, the reassemble stage, neck and head on the library path (_patch_dpt_upsampling)."""
+        self.dpt_vit = True
+        self._cache_vit_position_embeddings()
+        self._fuse_vit_layers()
+        self._patch_dpt_upsampling()
+
+    def _cache_vit_position_embeddings(self):
+        """DPTViTEmbeddings re-interpolates its position embedding (bilinear, 24 x 24 -> patch grid) on every forward; for a fixed input size the result is a
+        constant.  Memoised per (grid height, grid width, dtype), like _cache_position_embeddings for DINOv2."""
+        emb = self.model.dpt.embeddings
+        orig = emb._resize_pos_embed
+        cache = {}
+
+        def cached(posemb, grid_size_height, grid_size_width, start_index=1):
+            key = (int(grid_size_height), int(grid_size_width), posemb.dtype, int(start_index))
+            if key not in cache:
+                cache[key] = orig(posemb, grid_size_height, grid_size_width, start_index).detach()
+            return cache[key]
+
+        emb._resize_pos_embed = cached
+
+    @torch.no_grad()
+    def _fuse_vit_layers(self):
+        """Every DPTViTLayer (ViT-L/16 of DPT-Large) through _split_block -- the same rewrite as _fuse_backbone_layers' split mode: layernorm_before /
+        layernorm_after are its two LayerNorms (eps 1e-12), attention.output.dense the output projection, intermediate.dense fc1 (hidden_act "gelu": exact,
+        in the epilogue), output.dense fc2; there is no LayerScale to fold.  The encoder collects each layer's return value at backbone_out_indices:
+        the residual stream, as in the stock graph."""
+        layers = list(self.model.dpt.encoder.layer)
+        stash, pad_state = {"x": None, "h": None}, {"T": None}
+        for li, layer in enumerate(layers):
+            att, ffn = layer.attention.attention, layer.intermediate
+            wqkv = torch.cat([att.query.weight, att.key.weight, att.value.weight], 0).contiguous()
+            bqkv = None if att.query.bias is None else torch.cat([att.query.bias, att.key.bias, att.value.bias], 0).contiguous()
+            out, fc2 = layer.attention.output.dense, layer.output.dense
+            nxt = layers[li + 1].layernorm_before if li + 1 < len(layers) else None
+            layer.forward = self._split_block(stash, pad_state, wqkv, bqkv, out.weight, out.bias, ffn.dense.weight, ffn.dense.bias, fc2.weight, fc2.bias,
+                                              att.num_attention_heads, att.attention_head_size, att.scaling, layer.layernorm_before, layer.layernorm_after,
+                                              ffn.intermediate_act_fn, nxt)
 
     @torch.no_grad()
     def infer_bgr_u8(self, frames_bgr: torch.Tensor, inference_size=None, raw: bool = False, at_inference_size: bool = False) -> torch.Tensor:

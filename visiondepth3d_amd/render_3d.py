@@ -715,6 +715,19 @@ class Renderer:
         _lib.check(self._L.vd3d_dpt_head_tail_f32(self._ctx, _ptr(y), _ptr(b2), _ptr(w3), float(b3), float(scale), B * h * w, Cc, _ptr(out)))
         return out
 
+    def depth_to_space_bias(self, y, B: int, H: int, W: int, s: int, bias=None):
+        """The scatter of a kernel == stride ConvTranspose2d run as a GEMM: contiguous float32 ``y`` [B*H*W, s*s*C] (columns in (i, j, c) order) ->
+        channels_last [B, C, H*s, W*s] with out[b, c, y*s+i, x*s+j] = y[(b*H+y)*W+x, (i*s+j)*C+c] + bias[c] (include/vd3d.h vd3d_depth_to_space_bias_nhwc_f32)."""
+        P, N = y.shape
+        Cc = N // (s * s)
+        if y.dtype != torch.float32 or not y.is_contiguous() or P != B * H * W or Cc * s * s != N:
+            raise ValueError("y must be contiguous float32 [B*H*W, s*s*C]")
+        out = torch.empty((B, Cc, H * s, W * s), dtype=torch.float32, device=y.device, memory_format=torch.channels_last)
+        self._enter(y, bias, out)
+        _lib.check(self._L.vd3d_depth_to_space_bias_nhwc_f32(self._ctx, _ptr(y), _ptr(bias) if bias is not None else None, int(B), int(H), int(W), int(s), Cc,
+                                                             _ptr(out)))
+        return out
+
     def detect_black_bars(self, frame_bgr: torch.Tensor):
         """detect_black_bars(frame_to_tensor(frame)) (core/render_3d.py:293-316) on a uint8 BGR frame -> (top, bottom)."""
         f = frame_bgr.to(self.device, torch.uint8).contiguous()
