@@ -34,7 +34,7 @@ extern "C" {
  *    -DVD3D_DEV_KNOBS; aten_threads / aten_sum_threads accept 1 .. 1024.
  * 5 (round 5): vd3d_shift_params gained aten_threads / reserved0 at its end (vd3d_render_params embeds it: its later fields moved by 8 bytes); vd3d_torch_math_aten.
  * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
- * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32. */
+ * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32. */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -417,6 +417,12 @@ int vd3d_gemm_x3(vd3d_ctx* ctx, const float* X, int64_t M, int K, const void* w_
  * `workspace`: vd3d_attention_x3_workspace_bytes(B, T, H, D, mode) bytes of device memory (the split images), 16-byte aligned, owned by the caller. */
 int64_t vd3d_attention_x3_workspace_bytes(int B, int T, int H, int D, int mode);
 int vd3d_attention_x3(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int D, float scale, int mode, void* workspace, int64_t workspace_bytes, float* out);
+/* The same attention in exact float32 -- the default mode's (DepthPipe(gemm="f32")): both products on v_mfma_f32_32x32x2_f32 (float32 operands, float32
+ * accumulation, bit for bit a k-ordered fmaf chain), float32 online softmax (exp2 of logits pre-scaled through q * (scale * log2 e)), one division by the
+ * row sum at the end; nothing is rounded to a 16-bit format.  The arithmetic class of PyTorch's float32 scaled_dot_product_attention: only the summation
+ * order and the exp implementation differ.  Same qkv / out layout as vd3d_attention_x3; no workspace.  VD3D_E_UNSUPPORTED for D != 64, an empty shape,
+ * B * H > 65 535 or qkv / out not 16-byte aligned. */
+int vd3d_attention_f32(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int D, float scale, float* out);
 
 /* The 3 x 3 convolutions of the DPT neck / head in the fp16x2 arithmetic (the third piece of DepthPipe(gemm="fp16x2")): stride 1, zero padding 1, no bias
  * (DepthPipe runs them bias-free with a glue launch behind each), float32 channels_last: X [B][H][W][Cin] -> Y [B][H][W][Cout], W the module's float32

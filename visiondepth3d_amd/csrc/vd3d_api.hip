@@ -1481,8 +1481,18 @@ VD3D_EXPORT int vd3d_attention_x3(vd3d_ctx* c, const float* qkv, int B, int T, i
   const long long need = vd_attn_x3_workspace_bytes(B, T, H, D, mode);
   if (need < 0) return set_err(VD3D_E_UNSUPPORTED, "attention_x3: head size %d not built (64), an unknown mode %d or an empty shape (B %d T %d H %d)", D, mode, B, T, H);
   if (workspace_bytes < need) return set_err(VD3D_E_INVALID, "attention_x3: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, need);
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_attn_x3(c->stream, qkv, B, T, H, D, scale, workspace, out, mode))
     return set_err(VD3D_E_UNSUPPORTED, "attention_x3: qkv / workspace / out must be 16-byte aligned, B * H <= 65535");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_attention_f32(vd3d_ctx* c, const float* qkv, int B, int T, int H, int D, float scale, float* out) {
+  if (!c || !qkv || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_attn_f32(c->stream, qkv, B, T, H, D, scale, out))
+    return set_err(VD3D_E_UNSUPPORTED, "attention_f32: head size %d not built (64), an empty shape (B %d T %d H %d), B * H > 65535 or qkv / out not 16-byte aligned", D, B, T, H);
   HIPCHK(hipGetLastError());
   return 0;
 }

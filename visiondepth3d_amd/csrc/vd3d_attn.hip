@@ -1,7 +1,7 @@
 // vd3d_attn.hip -- softmax(Q K^T * scale) V of the depth network's transformer blocks (boundary B3, core/render_depth.py:1106-1119: float32 through the
-// Hugging Face pipeline) with BOTH matrix products as split-bf16 MFMA work -- the attention half of the opt-in `gemm="bf16x3"` mode (round 6; the
-// default mode keeps PyTorch's scaled_dot_product_attention = AOTriton's float32 kernel, 98 TFLOP/s on gfx950, whose float32-input MFMA runs at 1/16 of
-// the bf16 rate).  Same arithmetic idea as vd3d_gemm.hip: every float32 operand (Q, K, V and the probabilities P) is split EXACTLY into three bf16
+// Hugging Face pipeline) with BOTH matrix products as split-bf16 MFMA work -- the attention half of the opt-in `gemm="bf16x3"` mode (round 6; gfx950's
+// float32-input MFMA runs at 1/16 of the bf16 rate) -- and, further down, k_attn_f32: the same attention in exact float32, the default mode's (it replaced
+// PyTorch's scaled_dot_product_attention = AOTriton's float32 kernel, 99.5 TFLOP/s, with 113.5 at the 4K DA-V2-Base shape).  Same arithmetic idea as vd3d_gemm.hip: every float32 operand (Q, K, V and the probabilities P) is split EXACTLY into three bf16
 // terms, six of the nine term products go through v_mfma_f32_32x32x16_bf16 with float32 accumulation (the dropped ones are <= 2^-23 of a product);
 // the softmax itself is float32 (running maximum / sum, exp2 of the pre-scaled logits by v_exp_f32).
 //
@@ -26,6 +26,8 @@
 // per workgroup it would be 16: the reason for the 8-wave workgroup).
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
+
+#include <mutex>
 
 typedef short at_bf8 __attribute__((ext_vector_type(8)));
 typedef float at_f16 __attribute__((ext_vector_type(16)));
@@ -356,6 +358,208 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
   }
 }
 
+// ---- exact float32: k_attn_f32 (the default mode's attention) ------------------------------------------------------------------------------------------
+// The same S^T / P^T-from-the-accumulator layout on v_mfma_f32_32x32x2_f32 (A[i = lane & 31][k = lane >> 5], B[k = lane >> 5][j = lane & 31], one float32
+// per lane; a k-ordered fmaf chain, 64 cycles issue and dependent latency), with no split and no prep pass: Q comes straight from qkv into registers, K and V
+// rows (256 bytes per token and head) stream from qkv into an LDS ring by LDS-DMA.
+//   S^T[kv 32][q 32] (M tile m)   k-step s = 0 .. 31 takes d = 32 (lane >> 5) + s: a lane's 32 q values are one 128-byte run of its query row (eight 16-byte
+//                                  loads, scaled by scale * log2 e once) and its K values four 16-byte LDS reads per M tile.  2 x 32 = 64 MFMAs per 64-row tile.
+//   O^T[d 32][q 32] (tile dm)      accumulator register r of M tile m is one K = 2 step: P^T as the B operand straight from the S^T registers, lane half k
+//                                  holding kv = 32 m + (r & 3) + 8 (r >> 2) + 4 k; the A operand is V^T with row i = lane & 31 taken as d = 2 i + dm, so one
+//                                  ds_read_b64 of V[kv][2 i .. 2 i + 1] feeds both d tiles.  2 x 32 = 64 MFMAs per tile.  In the accumulator, registers
+//                                  4 g .. 4 g + 3 of both tiles are d = 16 g + 8 k .. + 7 of one query: the epilogue stores 32 contiguous bytes per lane and g.
+// LDS: a ring of three stages (K 16 KB, V 16 KB each), tile it + 2 issued at the top of iteration it into the stage tile it - 1 left (the barrier at the end
+// of iteration it - 1 follows every wave's reads of it).  K is XOR-swizzled (16-byte chunk c of row r at chunk c ^ (r & 15): the DMA picks each lane's source
+// chunk, the LDS image stays lane-linear) so that the 16-lane groups of ds_read_b128 see 16 distinct chunks; V is linear (a ds_read_b64 of 32 lanes reads one
+// whole 256-byte row).  Every DMA source row is clamped to T - 1: no zero-padded image, nothing read past the tensor, logits of rows past T are finite before
+// they are masked to -inf (p = 0 exactly).  Per tile and wave: 128 MFMAs (8 192 matrix-pipe cycles) against ~100 VALU instructions of softmax; O is rescaled
+// only when some lane's running maximum grew (alpha = exp2(0) = 1 exactly for the others).
+#define AF_TILE (AT_BK * AT_D * 4)   // 16 384 bytes: 64 rows x 256
+#define AF_STAGE (2 * AF_TILE)       // K + V
+#define AF_LDS (AT_NSTAGE * AF_STAGE)   // 98 304
+// The two matrix products of one tile, each reading its stage of the ring through a restrict pointer: inlined, the LDS reads carry alias-scope information
+// (one scope per product, kept when the compiler pairs reads), and the compiler's wait-count pass then does not put a conservative vmcnt(0) behind every
+// LDS-DMA in front of them -- the ring is ordered by the kernel's own counted waits and barriers.
+// S^T[m] = K Q^T for the 32-row M tiles m = 0, 1 (q pre-scaled); K row r at sk + 256 r, 16-byte chunk c at position c ^ (r & 15)
+VD_DEV void af_st(const uint8_t* __restrict__ sk, const float (&qf)[32], int li, int kh, at_f16 (&s)[2]) {
+  const int kswz = (li & 15) << 4;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[m][r] = 0.f;
+#pragma unroll
+  for (int g = 0; g < 8; ++g) {
+    float4 kf[2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) kf[m] = *reinterpret_cast<const float4*>(sk + (32 * m + li) * 256 + (((8 * kh + g) << 4) ^ kswz));
+#pragma unroll
+    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].x, qf[4 * g], s[m], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].y, qf[4 * g + 1], s[m], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].z, qf[4 * g + 2], s[m], 0, 0, 0);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].w, qf[4 * g + 3], s[m], 0, 0, 0);
+  }
+}
+// O^T[dm] += V^T P^T: register r of M tile m is the K = 2 step of kv 32 m + (r & 3) + 8 (r >> 2) + 4 kh; V row kv at sv + 256 kv (linear), d = 2 li + dm
+VD_DEV void af_pv(const uint8_t* __restrict__ sv, const at_f16 (&p)[2], int li, int kh, at_f16 (&oacc)[2]) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float2 vv = *reinterpret_cast<const float2*>(sv + (32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh) * 256 + li * 8);
+      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.x, p[m][r], oacc[0], 0, 0, 0);
+      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.y, p[m][r], oacc[1], 0, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qkv, float* __restrict__ out, vd_at_args a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t at_lds[];
+  int bh, qb;   // (b, h) grouped by XCD as in k_attn_bf16x3: the workgroups of one (b, h) read the same K / V rows
+  {
+    const int wg = blockIdx.x, x = wg & 7, idx = wg >> 3;
+    const int g = idx / a.nqb;
+    qb = idx - g * a.nqb;
+    bh = g * 8 + x;
+    if (bh >= a.B * a.H) return;
+  }
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 31, kh = lane >> 5;
+  const int q0 = qb * AT_BQ + wave * 32;
+  const int b = bh / a.H, h = bh - b * a.H;
+  const size_t tok_stride = (size_t)3 * a.H * AT_D;
+  const float* base = qkv + (size_t)b * a.T * tok_stride + h * AT_D;   // q of token t at base + t tok_stride, k at + H 64, v at + 2 H 64
+
+  // one tile's DMA: thread tid fills LDS chunks tid and tid + 512 of the K and of the V image = rows tid / 16 and + 32, chunk position tid & 15
+  const int drow = tid >> 4, dpos = tid & 15, kchunk = dpos ^ (drow & 15);
+  auto dma = [&](int tile, int stage) {
+    uint8_t* dst = at_lds + stage * AF_STAGE + wave * 1024;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int tok = min(tile * AT_BK + drow + 32 * p, a.T - 1);
+      const float* src = base + (size_t)tok * tok_stride + a.H * AT_D;
+      __builtin_amdgcn_global_load_lds((at_glb_vp)(src + kchunk * 4), (at_lds_vp)(dst + p * 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((at_glb_vp)(src + a.H * AT_D + dpos * 4), (at_lds_vp)(dst + AF_TILE + p * 8192), 16, 0, 0);
+    }
+  };
+
+  // Q of the wave's 32 queries (rows past T read row T - 1 and are never stored), pre-scaled by scale * log2 e
+  float qf[32];
+  {
+    const float4* qp = reinterpret_cast<const float4*>(base + (size_t)min(q0 + li, a.T - 1) * tok_stride + 32 * kh);
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      const float4 v = qp[g];
+      qf[4 * g] = v.x * a.c; qf[4 * g + 1] = v.y * a.c; qf[4 * g + 2] = v.z * a.c; qf[4 * g + 3] = v.w * a.c;
+    }
+  }
+  dma(0, 0);
+  if (a.nkv > 1) {
+    dma(1, 1);
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // tile 0 (and Q) landed, tile 1 in flight
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+
+  at_f16 oacc[2];
+#pragma unroll
+  for (int dm = 0; dm < 2; ++dm)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oacc[dm][r] = 0.f;
+  float m_run = -INFINITY, l_half = 0.f;
+  int cur = 0;
+  for (int it = 0; it < a.nkv; ++it) {
+    const bool ahead = it + 2 < a.nkv;
+    if (ahead) dma(it + 2, cur == 0 ? 2 : cur - 1);
+    const uint8_t* sk = at_lds + cur * AF_STAGE;
+    const uint8_t* sv = sk + AF_TILE;
+    // ---- S^T = K Q^T (pre-scaled logits)
+    at_f16 s[2];
+    af_st(sk, qf, li, kh, s);
+    if ((it + 1) * AT_BK > a.T) {   // last tile: rows past T (a uniform branch off the hot path)
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (it * AT_BK + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh >= a.T) s[m][r] = -INFINITY;
+    }
+    // ---- online softmax: running maximum over both lane halves, rescale only when it grew somewhere in the wave
+    float mx = s[0][0];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[m][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    if (__any(m_new > m_run)) {
+      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // 0 on the first tile (m_run = -inf), exactly 1 where the maximum did not grow
+#pragma unroll
+      for (int dm = 0; dm < 2; ++dm)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[dm][r] *= alpha;
+      l_half *= alpha;
+      m_run = m_new;
+    }
+    float ps = 0.f;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { s[m][r] = __builtin_amdgcn_exp2f(s[m][r] - m_run); ps += s[m][r]; }
+    l_half += ps;
+    // ---- O^T += V^T P^T
+    af_pv(sv, s, li, kh, oacc);
+    // before the barrier: this wave's reads of stage cur have returned (behind it, iteration it + 1's DMA of tile it + 3 overwrites that stage) and tile it + 1
+    // has landed (the four DMA instructions of tile it + 2 may stay in flight)
+    if (ahead) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    cur = cur == 2 ? 0 : cur + 1;
+  }
+
+  // ---- epilogue: out[b][q][h][16 g + 8 kh + 2 j + dm] = O^T_dm[register 4 g + j] / l
+  const float l_tot = l_half + __shfl_xor(l_half, 32, 64);
+  const int q = q0 + li;
+  if (q < a.T) {
+    float* op = out + (((size_t)b * a.T + q) * a.H + h) * AT_D + 8 * kh;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 lo = {oacc[0][4 * g] / l_tot, oacc[1][4 * g] / l_tot, oacc[0][4 * g + 1] / l_tot, oacc[1][4 * g + 1] / l_tot};
+      const float4 hi = {oacc[0][4 * g + 2] / l_tot, oacc[1][4 * g + 2] / l_tot, oacc[0][4 * g + 3] / l_tot, oacc[1][4 * g + 3] / l_tot};
+      *reinterpret_cast<float4*>(op + 16 * g) = lo;
+      *reinterpret_cast<float4*>(op + 16 * g + 4) = hi;
+    }
+  }
+}
+
+// the > 64 KB dynamic-LDS opt-in is a per-device function attribute: set once per (kernel, device); one context per host thread is a supported pattern, so
+// the first use of a device is serialised (as in vd3d_conv.hip / vd3d_warp.hip)
+static bool at_lds_optin(const void* fn, int lds, bool (&done)[64]) {
+  static std::mutex mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!done[dev]) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
+    done[dev] = true;
+  }
+  return true;
+}
+
+bool vd_launch_attn_f32(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, float* out) {
+  if (B < 1 || T < 1 || H < 1 || D != AT_D || (long long)B * H > 65535) return false;
+  if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return false;
+  static bool attr_set[64] = {};
+  if (!at_lds_optin(reinterpret_cast<const void*>(k_attn_f32), AF_LDS, attr_set)) return false;
+  vd_at_args a;
+  a.B = B; a.H = H; a.T = T;
+  a.nq32 = (T + 31) / 32; a.nkv = (T + AT_BK - 1) / AT_BK; a.nqb = (T + AT_BQ - 1) / AT_BQ;
+  a.c = scale * 1.44269504088896340736f;
+  const int groups = (B * H + 7) / 8;
+  hipLaunchKernelGGL(k_attn_f32, dim3((unsigned)(8 * groups * a.nqb)), dim3(AT_NT), AF_LDS, s, qkv, out, a);
+  return true;
+}
+
 static bool at_mode_ok(int mode) { return mode == 0 || mode == 1; }
 long long vd_attn_x3_workspace_bytes(int B, int T, int H, int D, int mode) {
   if (B < 1 || T < 1 || H < 1 || D != AT_D || !at_mode_ok(mode)) return -1;
@@ -366,11 +570,8 @@ long long vd_attn_x3_workspace_bytes(int B, int T, int H, int D, int mode) {
 
 template <int MODE>
 static bool at_launch(hipStream_t s, const float* qkv, int B, int T, int H, float scale, void* ws, float* out) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_attn_bf16x3<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, AT_LDS(MODE)) != hipSuccess) return false;
-    attr_set = true;
-  }
+  static bool attr_set[64] = {};
+  if (!at_lds_optin(reinterpret_cast<const void*>(k_attn_bf16x3<MODE>), AT_LDS(MODE), attr_set)) return false;
   vd_at_args a;
   a.B = B; a.H = H; a.T = T;
   a.nq32 = (T + 31) / 32; a.nkv = (T + AT_BK - 1) / AT_BK; a.nqb = (T + AT_BQ - 1) / AT_BQ;

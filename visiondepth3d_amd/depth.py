@@ -177,7 +177,8 @@ class DepthPipe:
                  tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32"):
         """``dtype``: float32 (the reference's precision, default) or bfloat16.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
-        GEMMs; ``"bf16x3"`` -- OPT-IN: the library's own split-bf16 GEMM (``vd3d_gemm_x3``: every float32 operand exactly split into three bf16
+        GEMMs and the attention (64-wide heads) is the library's exact-float32 kernel (``vd3d_attention_f32``: both products on the float32-input
+        matrix cores, float32 online softmax); ``"bf16x3"`` -- OPT-IN: the library's own split-bf16 GEMM (``vd3d_gemm_x3``: every float32 operand exactly split into three bf16
         terms, six products per MAC on the bf16 matrix cores, float32 accumulation -- float32-faithful, see include/vd3d.h), with the exact GELU
         folded into fc1's epilogue, and the attention in the same arithmetic (``vd3d_attention_x3``: both products split-bf16, float32 online softmax).
         ``"fp16x2"`` -- OPT-IN: the same kernels with every operand as TWO fp16 terms (22 significant bits, round to nearest) and three products per MAC
@@ -497,7 +498,7 @@ class DepthPipe:
     def _fuse_backbone_layers(self):
         """Inference-only rewrite of every Dinov2Layer (same math, fewer launches): q/k/v projections as ONE GEMM
         (N = 3*hidden), LayerScale folded into the output-projection / fc2 weights (lambda * (xW^T + b) == x(lambda*W)^T +
-        lambda*b), SDPA called directly.  Per layer: 4 GEMMs + attention + 2 LN + GELU + 2 adds instead of 6 GEMMs + 13
+        lambda*b), the attention called directly (float32 with a renderer: vd3d_attention_f32; otherwise SDPA).  Per layer: 4 GEMMs + attention + 2 LN + GELU + 2 adds instead of 6 GEMMs + 13
         smaller kernels."""
         layers = list(self.model.backbone.encoder.layer)
         R = self.renderer
@@ -548,10 +549,14 @@ class DepthPipe:
                     stash["x"] = stash["h"] = None
                 else:
                     h = n1(x)
-                qkv = F.linear(h, wqkv, bqkv).view(B, T, 3, nh, hd)
-                Tk = pad_state["T"] or T   # real tokens only on the key/value side
-                q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :Tk, 1].transpose(1, 2), qkv[:, :Tk, 2].transpose(1, 2)
-                o = F.scaled_dot_product_attention(q, k, v, scale=scaling).transpose(1, 2).reshape(B, T, d)
+                qkv = F.linear(h, wqkv, bqkv)
+                if R is not None and x.dtype == torch.float32 and hd == 64 and not pad_state["T"]:   # the library's exact-float32 attention
+                    o = R.attention_f32(qkv, nh, scaling)
+                else:
+                    qkv = qkv.view(B, T, 3, nh, hd)
+                    Tk = pad_state["T"] or T   # real tokens only on the key/value side
+                    q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :Tk, 1].transpose(1, 2), qkv[:, :Tk, 2].transpose(1, 2)
+                    o = F.scaled_dot_product_attention(q, k, v, scale=scaling).transpose(1, 2).reshape(B, T, d)
                 a = F.linear(o, wo, bo)
                 if not hip:
                     x = x + a
