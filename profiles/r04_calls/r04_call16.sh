@@ -12,6 +12,6 @@ DB=$(find $O/t_head -name "*_results.db" | head -1)
   python $R/tools/steady_state.py $DB 4 70; echo '```'; } > $O/r04_4k_dav2b_f32_steady.md; rm -rf $O/t_head
 head -30 $O/r04_4k_dav2b_f32_steady.md
 cd $R
-timeout 600 python bench.py --workload 1080p-dav2s-dibr --no-cpu-baseline --no-sub-records 2>/dev/null | tail -1 > $O/bench_1080p.json
+timeout 600 python bench.py --full --workload 1080p-dav2s-dibr --no-cpu-baseline --no-sub-records 2>/dev/null | tail -1 > $O/bench_1080p.json
 python -c "
 import json; d=json.load(open('$O/bench_1080p.json')); print('1080p-dav2s', d['value'], d['ms_per_step'])"

@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 R=$PWD; O=$R/gpurun_out/c21; mkdir -p $O
 timeout 900 python -m pytest tests/test_hip_edge_cases.py tests/test_hip_widen.py tests/test_hip_parity.py tests/test_hip_fuzz.py -m gpu -x -q 2>&1 | tail -5 | tee $O/pytest.log
-timeout 300 python bench.py --workload 4k-dibr-dof3 --steps 4 --warmup 2 --no-cpu-baseline 2>$O/dof3.err | tail -1 > $O/dof3.json
+timeout 300 python bench.py --full --workload 4k-dibr-dof3 --steps 4 --warmup 2 --no-cpu-baseline 2>$O/dof3.err | tail -1 > $O/dof3.json
 python -c "
 import json; d=json.load(open('$O/dof3.json')); print('4k-dibr-dof3', d['value'], d['ms_per_step'], d.get('stage_ms'))"
 cd /tmp

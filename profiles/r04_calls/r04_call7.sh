@@ -12,4 +12,4 @@ timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt -o p -- python $R/tools/pr
 python $R/tools/rocpd_summary.py $(find $O/kt -name "*_results.db" | head -1) 16 > $O/kt_dof3.md 2>&1; rm -rf $O/kt
 grep -E "k_chain|k_shift|k_warp|k_finish|k_e2w|k_dof|k_sharp" $O/kt_dof3.md | awk -F'|' '{printf "%-40s calls %s avg %s min %s vgpr %s lds %s grid %s\n", substr($2,1,40), $3, $5, $6, $9, $12, $14}'
 cd $R
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json; tail -3 $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 600 $O/bench_default.json; tail -3 $O/bench_default.err

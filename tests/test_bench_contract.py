@@ -150,3 +150,74 @@ def test_dump_outputs_writes_float32_frames_within_the_cap(tmp_path):
     assert os.path.getsize(tmp_path / "b1" / "frames.npy") <= 64 << 20 and b1.nbytes > (48 << 20)
     pos = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(1080 * 1920, size=b1.shape[1], replace=False))
     assert np.array_equal(b1, big.reshape(16, -1, 3).numpy()[:, pos].astype(np.float32))
+
+
+def test_full_option_exists_and_a_plain_line_carries_the_headline_fields():
+    """`--full` is an option of bench.py, off by default; the line of a plain run (no roofline pass, no CPU baseline, no sub-records) still carries
+    the fields the contract names, with the values the full line would carry."""
+    import subprocess
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    hlp = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120).stdout
+    assert "--full" in hlp and "--dump-outputs" in hlp
+    res = _synthetic_full_record()
+    plain = {k: v for k, v in res.items() if not k.startswith(("roofline", "cpu_", "sub_records", "stage_ms"))}
+    plain["full"] = False
+    c = bench.compact_record(plain, plain=True)
+    f = bench.compact_record(res, "full.json")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert c[k] == f[k] == res[k], k
+    assert c["full"] is False and "--full" in c["note"]
+    assert not any(k.startswith(("roofline", "cpu_baseline", "sub_records")) for k in c)
+    assert len(json.dumps(c, separators=(",", ":"))) < bench.COMPACT_LINE_LIMIT
+
+
+def test_prefetched_clip_equals_the_serial_one():
+    """the worker threads of synth_prefetch hand _synth_cached the frames synth_frame itself returns, and no worker outlives synth_pool_close"""
+    import threading
+    import numpy as np
+    import bench
+    from visiondepth3d_amd import synth
+    idx = [0, 1, 2, 3, 17, 17, 2]
+    bench.synth_prefetch(idx, 72, 128)
+    assert bench._CLIP_POOL[0] is not None and len(bench._CLIP_PENDING) == 5
+    got = [bench._synth_cached(synth, t, 72, 128) for t in idx]
+    bench.synth_pool_close()
+    assert bench._CLIP_POOL[0] is None and not bench._CLIP_PENDING
+    assert not [t for t in threading.enumerate() if t.name.startswith("synth")]
+    for t, (f, d) in zip(idx, got):
+        f0, d0 = synth.synth_frame(t, 72, 128)
+        assert f.dtype == np.uint8 and d.dtype == np.float32 and np.array_equal(f, f0) and np.array_equal(d, d0)
+    assert np.array_equal(bench._synth_cached(synth, 5, 72, 128)[0], synth.synth_frame(5, 72, 128)[0])   # not prefetched: generated in place
+
+
+def test_miopen_table_goes_to_a_private_directory(monkeypatch, tmp_path):
+    """miopen_setup: MIOpen gets a per-process COPY of the committed perf-db rows (it appends to its user databases: never inside the package, never
+    shared between runs); a MIOPEN_USER_DB_PATH of the caller's is left alone; --save-miopen-table writes the rows back sorted."""
+    import bench
+    table = [f for f in os.listdir(bench.MIOPEN_TABLE_DIR) if f.endswith(".udb.txt")]
+    assert table and all(f.startswith("gfx950") for f in table)
+    for k in ("MIOPEN_USER_DB_PATH", "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_BWD"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(bench, "_MIOPEN", dict(bench._MIOPEN))
+    bench.miopen_setup(use_table=True, skip_naive=True)
+    d = os.environ["MIOPEN_USER_DB_PATH"]
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", d)   # (restored after the test)
+    monkeypatch.setenv("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD", "0")
+    monkeypatch.setenv("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_BWD", "0")
+    assert os.path.isdir(d) and not os.path.abspath(d).startswith(os.path.abspath(bench.ROOT) + os.sep)
+    assert sorted(os.listdir(d)) == sorted(table) and bench._MIOPEN["perf_table"] and not bench._MIOPEN["naive_solver_in_find"]
+    src = open(os.path.join(bench.MIOPEN_TABLE_DIR, table[0])).read()
+    assert open(os.path.join(d, table[0])).read() == src
+    bench.miopen_save_table(str(tmp_path / "out"))
+    assert open(tmp_path / "out" / table[0]).read() == src          # the committed file is what the option writes: sorted rows
+    assert src.splitlines() == sorted(src.splitlines()) and len(src.splitlines()) >= 22
+    # the caller's own database directory wins; --no-miopen-table: an empty private directory
+    monkeypatch.setattr(bench, "_MIOPEN", {"db": None, "perf_table": False, "naive_solver_in_find": True})
+    bench.miopen_setup(use_table=True, skip_naive=False)
+    assert os.environ["MIOPEN_USER_DB_PATH"] == d and bench._MIOPEN["db"] is None
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH")
+    bench.miopen_setup(use_table=False, skip_naive=False)
+    d2 = os.environ["MIOPEN_USER_DB_PATH"]
+    monkeypatch.setenv("MIOPEN_USER_DB_PATH", d2)
+    assert d2 != d and os.listdir(d2) == [] and not bench._MIOPEN["perf_table"]

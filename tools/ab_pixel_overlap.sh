@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the overlapped pixel passes (vd3d_set_pixel_overlap) on one GPU box: same box, back to back.
 #   gpurun --timeout 500 -- 'bash tools/ab_pixel_overlap.sh'
-run() { python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); rf=d.get('roofline',{})
 print('$*', d['value'], d['ms_per_step'], rf.get('frac'), rf.get("in_step_frac"), d['config'].get('pixel_overlap'))"; }

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/final; mkdir -p $O
 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $O/smoke.log
-T0=$(date +%s); python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/final/bench_default.json"))

@@ -7,7 +7,7 @@ timeout 60 tools/gpu_ab.bin conv 270 480 2>&1 | tee -a $O/conv_ab.log
 timeout 60 tools/gpu_ab.bin conv 1080 1920 2>&1 | tee -a $O/conv_ab.log
 timeout 400 python -m pytest tests/test_hip_parity.py tests/test_hip_widen.py tests/test_hip_upscale.py -m gpu -x -q -k "feather_strength_zero or format_3d or upscale or conv or chunk_sharding" 2>&1 | tail -8 | tee $O/pytest.log
 for wl in 4k-dibr-gui 1080p-gui-defaults 4k-dibr-gui-hsbs 4k-dibr; do
-  timeout 200 python bench.py --workload $wl --steps 6 --warmup 2 --no-cpu-baseline 2>$O/bench_$wl.err | tail -1 > $O/bench_$wl.json
+  timeout 200 python bench.py --full --workload $wl --steps 6 --warmup 2 --no-cpu-baseline 2>$O/bench_$wl.err | tail -1 > $O/bench_$wl.json
   python - <<PY
 import json
 try:

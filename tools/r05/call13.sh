@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r05c13; mkdir -p $O
 run() { # name, flags
-  timeout 400 python bench.py --no-sub-records --no-cpu-baseline --steps 12 --warmup 4 $2 2>$O/$1.err | tail -1 > $O/$1.json
+  timeout 400 python bench.py --full --no-sub-records --no-cpu-baseline --steps 12 --warmup 4 $2 2>$O/$1.err | tail -1 > $O/$1.json
   python - <<PY
 import json
 try:

@@ -1,7 +1,7 @@
 #!/bin/bash
 export TMPDIR=/tmp
 O=gpurun_out/r05c14; mkdir -p $O
-T0=$(date +%s); python bench.py 2>$O/bench_default.err | tail -1 > $O/bench_default.json; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
+T0=$(date +%s); python bench.py --full 2>$O/bench_default.err | tail -1 > $O/bench_default.json; echo "bench.py wall: $(( $(date +%s) - T0 )) s"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r05c14/bench_default.json"))

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r05c18; mkdir -p $O
 for th in 32 16; do for wl in 4k-dibr-gui 1080p-gui-defaults 4k-dibr-gui-hsbs; do
-  VD3D_TUNE="7:$th" timeout 200 python bench.py --workload $wl --steps 6 --warmup 2 --no-cpu-baseline 2>$O/b.err | tail -1 > $O/b.json
+  VD3D_TUNE="7:$th" timeout 200 python bench.py --full --workload $wl --steps 6 --warmup 2 --no-cpu-baseline 2>$O/b.err | tail -1 > $O/b.json
   python - <<PY
 import json
 try:

@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r05c21; mkdir -p $O
 run() { # label, env, workload
-  env $2 timeout 200 python bench.py --workload $3 --steps 13 --warmup 2 --no-cpu-baseline 2>$O/b.err | tail -1 > $O/b.json
+  env $2 timeout 200 python bench.py --full --workload $3 --steps 13 --warmup 2 --no-cpu-baseline 2>$O/b.err | tail -1 > $O/b.json
   python -c "
 import json
 try:
