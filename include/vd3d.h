@@ -433,6 +433,17 @@ int vd3d_attention_f32(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int
 int64_t vd3d_conv3x3_x2_weight_bytes(int Cin, int Cout);
 int vd3d_conv3x3_x2_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
 int vd3d_conv3x3_x2(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
+/* The same convolution (3 x 3, stride 1, zero padding 1, no bias, groups 1, float32 channels_last in and out) in the bf16x3 arithmetic of vd3d_gemm_x3 in mode
+ * VD3D_X3_BF16X3 -- the convolutions of DepthPipe(gemm="bf16x3", conv="bf16x3"): every float32 operand is split EXACTLY into three bf16 terms by truncation
+ * (8 + 8 + 8 significant bits); six of the nine term products go through v_mfma_f32_32x32x16_bf16, small products first (x1 w3, x3 w1, x2 w2, x1 w2, x2 w1,
+ * x1 w1; x2 w3, x3 w2 and x3 w3 are dropped, as in the GEMM), float32 accumulation: float32-faithful (tests/test_hip_conv_x3.py vs float64).  bf16 has
+ * float32's exponent: no weight pre-scaling and no activation range limit.  NaN / Inf inputs give NaN.
+ * Cin a positive multiple of 16, Cout 32, 64, 128 or 256, H, W >= 1, 1 <= B <= 65 535, X and the image 16-byte aligned; anything else is VD3D_E_UNSUPPORTED
+ * with a message that names the rule.  The weights are split and packed once into vd3d_conv3x3_x3_weight_bytes(Cin, Cout) bytes (host-only; < 0: shape not
+ * built); the image is opaque and only valid for this library version. */
+int64_t vd3d_conv3x3_x3_weight_bytes(int Cin, int Cout);
+int vd3d_conv3x3_x3_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
+int vd3d_conv3x3_x3(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
 
 /* F.interpolate(mode="bilinear", align_corners=True) of an NHWC (channels_last) tensor [B][ih][iw][C] -> [B][oh][ow][C] of
  * `dtype`, C a multiple of 8 (bf16) / 4 (f32): the up-samplings of the DPT neck / head (a25). */

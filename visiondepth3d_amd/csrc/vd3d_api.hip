@@ -1474,6 +1474,35 @@ VD3D_EXPORT int vd3d_conv3x3_x2(vd3d_ctx* c, const float* X, int B, int H, int W
   return 0;
 }
 
+VD3D_EXPORT int64_t vd3d_conv3x3_x3_weight_bytes(int Cin, int Cout) { return (int64_t)vd_conv3x3_x3_weight_bytes(Cin, Cout); }
+
+static int conv3x3_x3_shape_err(int Cin, int Cout) {
+  return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: shape not built: C_in %d must be a positive multiple of 16 and C_out %d one of 32, 64, 128, 256", Cin, Cout);
+}
+
+VD3D_EXPORT int vd3d_conv3x3_x3_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
+  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  if (vd_conv3x3_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_x3_shape_err(Cin, Cout);
+  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: the weight image must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_conv3x3_x3_pack(c->stream, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "conv3x3_x3: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_conv3x3_x3(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
+  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
+  if (vd_conv3x3_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_x3_shape_err(Cin, Cout);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: batch %d must be 1 .. 65535 (one grid row per frame)", B);
+  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: map %d x %d must be at least 1 x 1", H, W);
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: the input and the weight image must be 16-byte aligned (the output 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_conv3x3_x3(c->stream, X, B, H, W, Cin, w_image, Cout, Y)) return set_err(VD3D_E_HIP, "conv3x3_x3: the dynamic LDS opt-in or the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 VD3D_EXPORT int64_t vd3d_attention_x3_workspace_bytes(int B, int T, int H, int D, int mode) { return (int64_t)vd_attn_x3_workspace_bytes(B, T, H, D, mode); }
 
 VD3D_EXPORT int vd3d_attention_x3(vd3d_ctx* c, const float* qkv, int B, int T, int H, int D, float scale, int mode, void* workspace, int64_t workspace_bytes, float* out) {

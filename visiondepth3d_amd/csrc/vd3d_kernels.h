@@ -214,6 +214,10 @@ bool vd_launch_gemm_x3(hipStream_t s, const float* X, long long M, int K, const 
 long long vd_conv3x3_x2_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_x2_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+// vd3d_conv3.hip: the same convolution in the bf16x3 arithmetic (three bf16 terms, six products), C_out 32 / 64 / 128 / 256
+long long vd_conv3x3_x3_weight_bytes(int Cin, int Cout);
+bool vd_launch_conv3x3_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
+bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
 // vd3d_attn.hip: softmax(Q K^T scale) V with both products as split-bf16 MFMA work
 long long vd_attn_x3_workspace_bytes(int B, int T, int H, int D, int mode);
 bool vd_launch_attn_x3(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, void* ws, float* out, int mode);

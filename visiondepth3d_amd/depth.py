@@ -168,13 +168,21 @@ def _tunable_scratch_dir() -> str:
     return _TUNABLE_DIR
 
 
+# DepthPipe(conv="bf16x3"): a 3 x 3 convolution takes vd3d_conv3x3_x3 from this many 8 x 32 output tiles (frames x tiles per frame, one workgroup each); below
+# it the float32 library convolution stays.  Measured on the DA-V2-Small / -Base / -Large neck, fusion and head shapes (tools/probe_conv_x3.py,
+# profiles/r08_conv_x3.md): every shape with 200 tiles or more ran in 0.59 - 0.97 of the library's time (MIOpen find mode on), every shape with 96 tiles or
+# fewer (the 19 x 33 and 37 x 66 maps, where the library's split-K kernels fill the chip) in 1.06 - 2.76 of it; nothing was measured in between, so the rule
+# is the smallest size that won.
+CONV_X3_MIN_TILES = 200
+
+
 class DepthPipe:
     """``pipe(images, inference_size=None) -> [{"predicted_depth": Tensor[h, w]}]`` (reference protocol) plus a
     device-resident batch path."""
 
     def __init__(self, name: str = "depth-anything-v2-small", device="cuda", dtype=torch.float32, seed: int = 0,
                  channels_last: bool = True, renderer=None, fuse_backbone: bool = True, model=None, processor: dict | None = None,
-                 tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32"):
+                 tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None):
         """``dtype``: float32 (the reference's precision, default) or bfloat16.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
         GEMMs and the attention (64-wide heads) is the library's exact-float32 kernel (``vd3d_attention_f32``: both products on the float32-input
@@ -187,6 +195,13 @@ class DepthPipe:
         readout_type="project"; its readout / 1x1 projections and the transposed convolutions of the reassemble stage go on ``vd3d_gemm_x3`` too, see
         ``_patch_dpt_vit_reassemble_head``).  Anything else -- DPT-Hybrid, BEiT / Swin backbones, ZoeDepth, DepthPro -- raises NotImplementedError; with
         ``gemm="f32"`` a DPT model runs its stock module graph unchanged.
+        ``conv``: ``None`` (default) -- the 3 x 3 convolutions of the DPT neck / fusion stage / head run as they always did per mode: library float32
+        convolutions in ``"f32"`` and ``"bf16x3"``, ``vd3d_conv3x3_x2`` where its rules allow in ``"fp16x2"``.  ``"bf16x3"`` -- OPT-IN, only with
+        ``gemm="bf16x3"`` (else ValueError): the 3 x 3 / stride 1 / padding 1 convolutions -- ``neck.convs``, the fusion stage's residual units, the head's
+        two (DA and DPT-Large alike) -- run on ``vd3d_conv3x3_x3``, the same three-term / six-product arithmetic as the GEMM (include/vd3d.h), for 32 / 64 /
+        128 / 256 output channels and input channels in multiples of 16.  Maps below the measured launch-size rule (``CONV_X3_MIN_TILES``) stay on the
+        library; nothing else falls back.  ``conv_routes`` (module name -> ("bf16x3" | "library", reason)) records, per forward, where each of these
+        convolutions ran and why.
         ``renderer``: a ``visiondepth3d_amd.render_3d.Renderer`` on the SAME stream as the network (default stream); when given the
         image-processor front end, the residual-add + LayerNorm pairs and the DPT up-samplings run as fused HIP launches.
         ``model`` / ``processor``: an already constructed Hugging Face depth model and its image-processor constants
@@ -200,9 +215,14 @@ class DepthPipe:
         self.name, self.device, self.dtype = name, torch.device(device), dtype
         if gemm not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
+        if conv not in (None, "bf16x3"):
+            raise ValueError("conv must be None or 'bf16x3'")
+        if conv == "bf16x3" and gemm != "bf16x3":
+            raise ValueError("conv='bf16x3' is the convolution half of gemm='bf16x3' and needs that mode")
         if gemm != "f32" and (dtype != torch.float32 or renderer is None or torch.device(device).type != "cuda"):
             raise ValueError("gemm='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
-        self.gemm = gemm
+        self.gemm, self.conv = gemm, conv
+        self.conv_routes = {}
         self.tuned_gemm = self.miopen_find = False
         self._flop_count = None
         if self.device.type == "cuda":
@@ -354,8 +374,38 @@ class DepthPipe:
                 return None
             return R.conv3x3_x2(x.contiguous(memory_format=CL), conv_img[key], m.out_channels)
 
+        conv3_img = {}   # conv="bf16x3": packed weights per convolution module (None = shape not built)
+        names = {id(m): n for n, m in self.model.named_modules()}
+
+        def conv_x3(m, x):
+            if (self.conv != "bf16x3" or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
+                    or x.dtype != torch.float32):
+                return None
+            key = id(m)
+            if key not in conv3_img:
+                conv3_img[key] = R.conv3x3_x3_pack(m.weight)
+            if conv3_img[key] is None:
+                self.conv_routes[names[key]] = ("library", f"shape not built: {m.in_channels} -> {m.out_channels} channels")
+                return None
+            tiles = x.shape[0] * ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)   # one workgroup per 8 x 32 output tile
+            if tiles < CONV_X3_MIN_TILES:
+                self.conv_routes[names[key]] = ("library", f"size rule: {tiles} tiles < {CONV_X3_MIN_TILES}")
+                return None
+            self.conv_routes[names[key]] = ("bf16x3", f"{tiles} tiles")
+            return R.conv3x3_x3(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
+
+        if self.conv == "bf16x3" and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
+            for m in self.model.neck.convs:
+                if m.bias is None:
+                    def neck_conv_fwd(x, m=m):
+                        y = conv_x3(m, x)
+                        return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups) if y is None else y
+                    m.forward = neck_conv_fwd
+
         def conv_nb(m, x):   # the module's convolution without its bias
             y = conv_x2(m, x)
+            if y is None:
+                y = conv_x3(m, x)
             if y is None:
                 y = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups).contiguous(memory_format=CL)
             if self._flop_count is not None:   # flops_per_frame: these calls bypass the modules' forward hooks
@@ -432,7 +482,8 @@ class DepthPipe:
           * head: conv1 bias-free with its bias inside the align_corners up-sampling, conv2 bias-free (vd3d_conv3x3_x2 in fp16x2 where its size rule allows),
             vd3d_dpt_head_tail_f32 (scale 1) for the rest.
         neck.convs (3 x 3, no bias, C_i -> 256) and the fusion stage's 256 -> 256 convolutions have 256 output channels, which vd3d_conv3x3_x2 does not
-        build: they stay library float32 convolutions, as for DA-V2-Large."""
+        build: they stay library float32 convolutions, as for DA-V2-Large -- unless the pipe was built with conv="bf16x3", whose vd3d_conv3x3_x3 builds
+        256 output channels and takes them and the head's two 3 x 3 convolutions (conv_nb / the neck.convs routing of _patch_dpt_upsampling)."""
         R, gm, CL = self.renderer, self.gemm, torch.channels_last
         stage, head = self.model.neck.reassemble_stage, self.model.head
         hooks = []
