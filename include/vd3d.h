@@ -414,6 +414,8 @@ int vd3d_gemm_x3(vd3d_ctx* ctx, const float* X, int64_t M, int K, const void* w_
  * Q, K, V and the probabilities are split like the GEMM operands of `mode` (fp16x2: q, k, v scaled by 2^4 and the probabilities by 2^10 before their split,
  * exactly, undone in the logits' scale and the final normalisation), both matrix products run on the matrix cores with float32 accumulation, the online
  * softmax is float32 (exp2 of the pre-scaled logits).  D = 64 only (every DINOv2 size), else VD3D_E_UNSUPPORTED.
+ * Range: bf16x3 has float32's exponent.  In fp16x2 the 2^4 scale leaves |q|, |k|, |v| < 65 504 / 16 = 4 094: a larger value gives Inf / NaN in the outputs
+ * that depend on it (a value: that column of its head; a key: its head) and nowhere else (tests/test_hip_operand_range.py).
  * `workspace`: vd3d_attention_x3_workspace_bytes(B, T, H, D, mode) bytes of device memory (the split images), 16-byte aligned, owned by the caller. */
 int64_t vd3d_attention_x3_workspace_bytes(int B, int T, int H, int D, int mode);
 int vd3d_attention_x3(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int D, float scale, int mode, void* workspace, int64_t workspace_bytes, float* out);

@@ -1460,6 +1460,7 @@ VD3D_EXPORT int64_t vd3d_conv3x3_x2_weight_bytes(int Cin, int Cout) { return (in
 
 VD3D_EXPORT int vd3d_conv3x3_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
   if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_conv3x3_x2_pack(c->stream, W, Cin, Cout, image))
     return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x2: C_in %d must be a positive multiple of 16 and C_out %d one of 64, 128", Cin, Cout);
   HIPCHK(hipGetLastError());
@@ -1468,6 +1469,7 @@ VD3D_EXPORT int vd3d_conv3x3_x2_pack_weights(vd3d_ctx* c, const float* W, int Ci
 
 VD3D_EXPORT int vd3d_conv3x3_x2(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
   if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_conv3x3_x2(c->stream, X, B, H, W, Cin, w_image, Cout, Y))
     return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x2: C_in %d (multiple of 16), C_out %d (64 | 128), B %d <= 65535, 16-byte aligned input and image", Cin, Cout, B);
   HIPCHK(hipGetLastError());
@@ -1530,6 +1532,7 @@ VD3D_EXPORT int64_t vd3d_gemm_x3_weight_bytes(int N, int K, int mode) { return (
 
 VD3D_EXPORT int vd3d_gemm_x3_pack_weights(vd3d_ctx* c, const float* W, int N, int K, int mode, void* image) {
   if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_gemm_x3_pack_w(c->stream, W, N, K, image, mode)) return set_err(VD3D_E_UNSUPPORTED, "gemm_x3: K %d must be a positive multiple of 16 (N %d), mode %d in {0, 1}", K, N, mode);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1538,6 +1541,7 @@ VD3D_EXPORT int vd3d_gemm_x3_pack_weights(vd3d_ctx* c, const float* W, int N, in
 VD3D_EXPORT int vd3d_gemm_x3(vd3d_ctx* c, const float* X, int64_t M, int K, const void* w_image, int N, int mode, const float* bias_or_null, int epilogue, float* Y) {
   if (!c || !X || !w_image || !Y || M < 1) return set_err(VD3D_E_INVALID, "bad argument");
   if (epilogue != VD3D_GEMM_EPI_NONE && epilogue != VD3D_GEMM_EPI_GELU) return set_err(VD3D_E_INVALID, "gemm_x3: unknown epilogue %d", epilogue);
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_gemm_x3(c->stream, X, (long long)M, K, w_image, N, bias_or_null, epilogue, Y, mode))
     return set_err(VD3D_E_UNSUPPORTED, "gemm_x3: K %d must be a positive multiple of 16, mode %d in {0, 1}, X and the weight image 16-byte aligned", K, mode);
   HIPCHK(hipGetLastError());

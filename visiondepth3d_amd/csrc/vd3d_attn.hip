@@ -532,25 +532,11 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
   }
 }
 
-// the > 64 KB dynamic-LDS opt-in is a per-device function attribute: set once per (kernel, device); one context per host thread is a supported pattern, so
-// the first use of a device is serialised (as in vd3d_conv.hip / vd3d_warp.hip)
-static bool at_lds_optin(const void* fn, int lds, bool (&done)[64]) {
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  if (!done[dev]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
-    done[dev] = true;
-  }
-  return true;
-}
-
 bool vd_launch_attn_f32(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, float* out) {
   if (B < 1 || T < 1 || H < 1 || D != AT_D || (long long)B * H > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return false;
   static bool attr_set[64] = {};
-  if (!at_lds_optin(reinterpret_cast<const void*>(k_attn_f32), AF_LDS, attr_set)) return false;
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_attn_f32), AF_LDS}}, attr_set)) return false;   // per device (vd3d_kernels.h)
   vd_at_args a;
   a.B = B; a.H = H; a.T = T;
   a.nq32 = (T + 31) / 32; a.nkv = (T + AT_BK - 1) / AT_BK; a.nqb = (T + AT_BQ - 1) / AT_BQ;
@@ -571,7 +557,7 @@ long long vd_attn_x3_workspace_bytes(int B, int T, int H, int D, int mode) {
 template <int MODE>
 static bool at_launch(hipStream_t s, const float* qkv, int B, int T, int H, float scale, void* ws, float* out) {
   static bool attr_set[64] = {};
-  if (!at_lds_optin(reinterpret_cast<const void*>(k_attn_bf16x3<MODE>), AT_LDS(MODE), attr_set)) return false;
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_attn_bf16x3<MODE>), AT_LDS(MODE)}}, attr_set)) return false;
   vd_at_args a;
   a.B = B; a.H = H; a.T = T;
   a.nq32 = (T + 31) / 32; a.nkv = (T + AT_BK - 1) / AT_BK; a.nqb = (T + AT_BQ - 1) / AT_BQ;

@@ -244,13 +244,9 @@ bool vd_launch_conv3x3_x2(hipStream_t s, const float* X, int B, int H, int W, in
   const long long nb = vd_conv3x3_x2_weight_bytes(Cin, Cout);
   if (nb < 0 || B < 1 || H < 1 || W < 1 || B > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15)) return false;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_x2<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS(64)) != hipSuccess) return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_x2<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS(128)) != hipSuccess) return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_x2<8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, C2_LDS(32)) != hipSuccess) return false;
-    attr_set = true;
-  }
+  static bool attr_set[64] = {};   // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute (vd3d_kernels.h)
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_conv3x3_x2<4, 1>), C2_LDS(64)}, {reinterpret_cast<const void*>(k_conv3x3_x2<4, 2>), C2_LDS(128)},
+                     {reinterpret_cast<const void*>(k_conv3x3_x2<8, 1>), C2_LDS(32)}}, attr_set)) return false;
   vd_c2_args a;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   a.ntx = (W + C2_TW - 1) / C2_TW; a.nty = (H + C2_TH - 1) / C2_TH; a.nchunk = Cin / 16;

@@ -245,19 +245,9 @@ bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, in
   const long long nb = vd_conv3x3_x3_weight_bytes(Cin, Cout);
   if (nb < 0 || B < 1 || H < 1 || W < 1 || B > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3)) return false;
-  static bool attr_set[64] = {};   // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute
-  static std::mutex init_mu;       // one context per host thread is a supported pattern: first use of a device is serialised
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  {
-    std::lock_guard<std::mutex> init_lock(init_mu);
-    if (!attr_set[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_x3<8, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, c3_lds(32, 4)) != hipSuccess) return false;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_x3<4, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, c3_lds(64, 4)) != hipSuccess) return false;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_x3<4, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, c3_lds(128, 4)) != hipSuccess) return false;
-      attr_set[dev] = true;
-    }
-  }
+  static bool attr_set[64] = {};   // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute (vd3d_kernels.h)
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_conv3x3_x3<8, 1, 4>), c3_lds(32, 4)}, {reinterpret_cast<const void*>(k_conv3x3_x3<4, 1, 4>), c3_lds(64, 4)},
+                     {reinterpret_cast<const void*>(k_conv3x3_x3<4, 2, 4>), c3_lds(128, 4)}}, attr_set)) return false;
   vd_c3_args a;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   a.ntx = (W + C3_TW - 1) / C3_TW; a.nty = (H + C3_TH - 1) / C3_TH; a.nchunk = Cin / 16;

@@ -367,21 +367,19 @@ bool vd_launch_gemm_x3_pack_w(hipStream_t s, const float* W, int N, int K, void*
 bool vd_launch_gemm_x3(hipStream_t s, const float* X, long long M, int K, const void* wimg, int N, const float* bias, int epilogue, float* Y, int mode) {
   if (M < 1 || vd_gemm_x3_weight_bytes(N, K, mode) < 0 || epilogue < 0 || epilogue > 1) return false;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15)) return false;
-  static bool attr_set = false;   // idempotent: a race between two first calls sets the same value twice
+  static bool attr_set[64] = {};   // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute (vd3d_kernels.h)
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_gemm_bf16x3<0, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<0, 1>), GX_LDS(1)}}, attr_set)) return false;
   static int dbg = 0;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_bf16x3<0, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, GX_LDS(0)) != hipSuccess) return false;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_bf16x3<0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, GX_LDS(1)) != hipSuccess) return false;
 #ifdef VD_GEMM_ABLATE
-    for (const void* f : {reinterpret_cast<const void*>(k_gemm_bf16x3<1, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<2, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<4, 0>),
-                          reinterpret_cast<const void*>(k_gemm_bf16x3<8, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<5, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<3, 0>),
-                          reinterpret_cast<const void*>(k_gemm_bf16x3<9, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<11, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<16, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<27, 0>),
-                          reinterpret_cast<const void*>(k_gemm_bf16x3<32, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<64, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<128, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<130, 0>), reinterpret_cast<const void*>(k_gemm_bf16x3<256, 0>)})
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, GX_LDS(0)) != hipSuccess) return false;
-    dbg = getenv("VD3D_GEMM_DBG") ? atoi(getenv("VD3D_GEMM_DBG")) : 0;
+  static bool ablate_set[64] = {};
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_gemm_bf16x3<1, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<2, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<4, 0>), GX_LDS(0)},
+                     {reinterpret_cast<const void*>(k_gemm_bf16x3<8, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<5, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<3, 0>), GX_LDS(0)},
+                     {reinterpret_cast<const void*>(k_gemm_bf16x3<9, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<11, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<16, 0>), GX_LDS(0)},
+                     {reinterpret_cast<const void*>(k_gemm_bf16x3<27, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<32, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<64, 0>), GX_LDS(0)},
+                     {reinterpret_cast<const void*>(k_gemm_bf16x3<128, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<130, 0>), GX_LDS(0)}, {reinterpret_cast<const void*>(k_gemm_bf16x3<256, 0>), GX_LDS(0)}}, ablate_set))
+    return false;
+  dbg = getenv("VD3D_GEMM_DBG") ? atoi(getenv("VD3D_GEMM_DBG")) : 0;
 #endif
-    attr_set = true;
-  }
   vd_gx_args a;
   a.M = M; a.K = K; a.N = N; a.KS = K / 16;
   a.nbm = (int)((M + GX_BM - 1) / GX_BM); a.nbn = (N + GX_BN - 1) / GX_BN;

@@ -2,7 +2,27 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+#include <mutex>
+
 #include "vd3d_work.h"
+
+// The > 64 KB dynamic-LDS opt-in (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to the DEVICE's copy of the code object: it is set once per (kernel set,
+// current device), `done` being the caller's per-device record.  One context per host thread is a supported pattern, so the first use of a device is
+// serialised.  The caller has made the context's device current (hipSetDevice in the C entry point).  false: no current device, or the runtime refused.
+struct vd_lds_fn { const void* fn; int bytes; };
+inline bool vd_lds_optin(std::initializer_list<vd_lds_fn> fns, bool (&done)[64]) {
+  static std::mutex mu;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!done[dev]) {
+    for (const vd_lds_fn& f : fns)
+      if (hipFuncSetAttribute(f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, f.bytes) != hipSuccess) return false;
+    done[dev] = true;
+  }
+  return true;
+}
 
 enum { VD_ST_A0 = 0, VD_ST_B0, VD_ST_A1, VD_ST_B1, VD_ST_A2, VD_ST_B2,
        VD_ST_AQ, VD_ST_BQ, VD_ST_BS };  // AQ/BQ: generic quantile pair, BS: bare subject depth (test entry points)

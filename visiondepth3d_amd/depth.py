@@ -190,7 +190,8 @@ class DepthPipe:
         terms, six products per MAC on the bf16 matrix cores, float32 accumulation -- float32-faithful, see include/vd3d.h), with the exact GELU
         folded into fc1's epilogue, and the attention in the same arithmetic (``vd3d_attention_x3``: both products split-bf16, float32 online softmax).
         ``"fp16x2"`` -- OPT-IN: the same kernels with every operand as TWO fp16 terms (22 significant bits, round to nearest) and three products per MAC
-        -- half the matrix work of bf16x3; weights pre-scaled per row, activations must stay below 65 504 (include/vd3d.h).  gfx950 has no TF32 and its float32-input MFMA runs at 1/16 of the bf16 rate, which caps the default mode.
+        -- half the matrix work of bf16x3; weights pre-scaled per row, activations must stay below 65 504 in front of every linear and convolution and q, k, v below 4 094 in front of the
+        attention, which scales them by 2^4 before its split (larger values give Inf / NaN, never a finite wrong number: include/vd3d.h).  gfx950 has no TF32 and its float32-input MFMA runs at 1/16 of the bf16 rate, which caps the default mode.
         The split modes cover the DINOv2 family (Depth-Anything V1 / V2, Distill-Any-Depth) and DPT-Large (a plain-ViT ``DPTForDepthEstimation`` with
         readout_type="project"; its readout / 1x1 projections and the transposed convolutions of the reassemble stage go on ``vd3d_gemm_x3`` too, see
         ``_patch_dpt_vit_reassemble_head``).  Anything else -- DPT-Hybrid, BEiT / Swin backbones, ZoeDepth, DepthPro -- raises NotImplementedError; with
