@@ -367,6 +367,28 @@ int vd3d_conv3x3_c64_f16(vd3d_ctx* ctx, const void* x_nhwc, int H, int W, const 
 int vd3d_conv3x3_head_f16(vd3d_ctx* ctx, const void* x_nhwc3, int H, int W, const float* w27x64, const float* bias, const float* slope_or_null,
                           void* y_nhwc64);
 int vd3d_esr_tail_f32(vd3d_ctx* ctx, const void* t_nhwc64, const void* x_nhwc3, int H, int W, int r, float* out_planar);
+/* The convolutions of RealESRGAN_x4plus (RRDBNet: 23 residual-in-residual dense blocks, 351 convolutions) on the matrix cores: 3x3, stride 1, zero
+ * padding 1, fp16 operands, float32 accumulate (v_mfma_f32_32x32x16_f16), one fp16 rounding at the store.
+ *   x: fp16 NHWC with a pixel stride of x_stride channels; channels [0, Cin) are read.  Cin: 64, 96, 128, 160 or 192.
+ *   y: fp16 NHWC with a pixel stride of y_stride channels; the Cout (32 or 64) channels at [y_offset, y_offset + Cout) are written, nothing else.
+ *      y may be the buffer x, provided the written slice does not meet [0, Cin): a dense block lives in one [H][W][192] buffer and needs no concatenation.
+ *   w_frag: the weight Wt[oc][ic][kh][kw] in fragment order, fp16 [Cin/32 * 18 steps][Cout/32][64 lanes][8]:
+ *           step = ((ic / 32)*9 + kh*3 + kw)*2 + kc, element [step][t][l][j] = Wt[32 t + (l & 31)][32 (ic / 32) + 16 kc + 8 (l >> 5) + j][kh][kw]
+ *           (visiondepth3d_amd.upscale.dense_weight_fragments builds it).  The steps are accumulated in this order.  For a [64][64][3][3] weight this is
+ *           NOT the order of vd3d_conv3x3_c64_f16 (tap-major there, 32-channel-chunk-major here).
+ *   epilogue, in float32: v = acc + bias[oc]; v = v >= 0 ? v : v * slope (slope 1: no activation); if r1: v = v * alpha + r1[pixel][oc];
+ *           if r2: v = v * beta + r2[pixel][oc].  r1 / r2: fp16 NHWC with pixel strides r1_stride / r2_stride (channels [0, Cout) are read), or NULL.
+ *   up2: the input is [H/2][W/2] (H, W = the OUTPUT size, both even) and tap (gy, gx) reads its pixel (gy >> 1, gx >> 1) -- nearest x2 up-sampling
+ *        folded into the convolution; padding is tested against H, W.  Built for Cin = Cout = 64.
+ * Rules (VD3D_E_UNSUPPORTED with a message that names the broken one, nothing launched): the channel counts above; every stride and y_offset a multiple of 8,
+ * x_stride >= Cin, y_offset + Cout <= y_stride, residual strides >= Cout; every pointer 16-byte aligned; the bytes written meet neither the bytes read
+ * (an intersecting slice of the same buffer would be a race between workgroups) nor a residual.  One frame per call; bit-for-bit repeatable. */
+int vd3d_conv3x3_dense_f16(vd3d_ctx* ctx, const void* x, int H, int W, int x_stride, int Cin, const void* w_frag, const float* bias, int Cout,
+                           float slope, float alpha, const void* r1_or_null, int r1_stride, float beta, const void* r2_or_null, int r2_stride,
+                           int up2, void* y, int y_stride, int y_offset);
+/* The network's tail: channels 0..2 of an fp16 NHWC [H][W][32] map (conv_last on the kernel above, weights and bias zero-padded from 3 to 32 output
+ * channels) -> the float32 planar prediction [3][H][W] that vd3d_esr_postprocess takes.  t 16-byte aligned. */
+int vd3d_nhwc_f16_to_planar3_f32(vd3d_ctx* ctx, const void* t_nhwc32, int H, int W, float* out_planar);
 
 /* ---- depth hand-off (a24): transformers' bicubic post-process to (H,W) + convert_depth_to_grayscale
  * (core/render_depth.py:585-611,1914-1916) for a batch of B predictions [B][ph][pw] float32 -> uint8 [B][H][W].

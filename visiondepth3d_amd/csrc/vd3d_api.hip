@@ -1648,6 +1648,63 @@ VD3D_EXPORT int vd3d_esr_tail_f32(vd3d_ctx* c, const void* t_nhwc64, const void*
   return 0;
 }
 
+// the RRDBNet convolutions (vd3d_conv_rdb.hip): every rule of include/vd3d.h is checked here, before anything is launched
+VD3D_EXPORT int vd3d_conv3x3_dense_f16(vd3d_ctx* c, const void* x, int H, int W, int x_stride, int Cin, const void* w_frag, const float* bias, int Cout,
+                                       float slope, float alpha, const void* r1_or_null, int r1_stride, float beta, const void* r2_or_null, int r2_stride,
+                                       int up2, void* y, int y_stride, int y_offset) {
+  if (!c || !x || !w_frag || !bias || !y) return set_err(VD3D_E_INVALID, "conv3x3_dense_f16: null argument");
+  if (H < 1 || W < 1 || H > 32768 || W > 32768) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: map %d x %d must be 1 .. 32768 on each side", H, W);
+  if (Cin != 64 && Cin != 96 && Cin != 128 && Cin != 160 && Cin != 192)
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: C_in %d must be one of 64, 96, 128, 160, 192", Cin);
+  if (Cout != 32 && Cout != 64) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: C_out %d must be 32 or 64", Cout);
+  if (x_stride < Cin || (x_stride & 7)) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: x_stride %d must be a multiple of 8 and >= C_in %d", x_stride, Cin);
+  if (y_offset < 0 || (y_offset & 7) || (y_stride & 7) || y_stride < y_offset + Cout)
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: y_offset %d and y_stride %d must be multiples of 8 with y_offset + C_out %d <= y_stride", y_offset, y_stride, Cout);
+  if ((r1_or_null && (r1_stride < Cout || (r1_stride & 7))) || (r2_or_null && (r2_stride < Cout || (r2_stride & 7))))
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: a residual's stride must be a multiple of 8 and >= C_out %d", Cout);
+  if (up2 && (Cin != 64 || Cout != 64 || (H & 1) || (W & 1)))
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: up2 is built for 64 -> 64 channels and an even output size (got %d -> %d, %d x %d)", Cin, Cout, H, W);
+  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w_frag | (uintptr_t)bias | (uintptr_t)r1_or_null | (uintptr_t)r2_or_null) & 15)
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: pointers must be 16-byte aligned");
+  const long long in_pix = up2 ? (long long)(H / 2) * (W / 2) : (long long)H * W, out_pix = (long long)H * W;
+  {   // the bytes read (channels [0, C_in) of every input pixel) and the bytes written (the output slice of every pixel) must not meet: with one base
+      // pointer and one stride that is the channel test of the header; any other overlap of the two extents is refused as well
+    const uintptr_t xb = (uintptr_t)x, xe = xb + (uintptr_t)(((in_pix - 1) * x_stride + Cin) * 2);
+    const uintptr_t yb = (uintptr_t)y + (uintptr_t)y_offset * 2, ye = (uintptr_t)y + (uintptr_t)(((out_pix - 1) * y_stride + y_offset + Cout) * 2);
+    const bool same_grid = x == y && x_stride == y_stride && !up2;
+    if (same_grid ? y_offset < Cin : (xb < ye && yb < xe))
+      return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: the output slice [%d, %d) meets the input channels [0, %d) of the same buffer (a race between workgroups)",
+                     y_offset, y_offset + Cout, Cin);
+    const void* rs[2] = {r1_or_null, r2_or_null};
+    const int rst[2] = {r1_stride, r2_stride};
+    for (int i = 0; i < 2; ++i) {
+      if (!rs[i]) continue;
+      const uintptr_t rb = (uintptr_t)rs[i], re = rb + (uintptr_t)(((out_pix - 1) * rst[i] + Cout) * 2);
+      const bool rgrid = rs[i] == y && rst[i] == y_stride;
+      if (rgrid ? y_offset < Cout : (rb < ye && yb < re))
+        return set_err(VD3D_E_UNSUPPORTED, "conv3x3_dense_f16: residual %d overlaps the output slice", i + 1);
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "conv3x3_dense");
+  if (!vd_launch_conv3x3_dense_f16(c->stream, x, H, W, x_stride, Cin, w_frag, bias, Cout, slope, alpha, r1_or_null, r1_stride, beta, r2_or_null, r2_stride,
+                                   up2 ? 1 : 0, y, y_stride, y_offset))
+    return set_err(VD3D_E_HIP, "conv3x3_dense_f16: the dynamic LDS opt-in failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_nhwc_f16_to_planar3_f32(vd3d_ctx* c, const void* t_nhwc32, int H, int W, float* out_planar) {
+  if (!c || !t_nhwc32 || !out_planar) return set_err(VD3D_E_INVALID, "nhwc_f16_to_planar3_f32: null argument");
+  if (H < 1 || W < 1 || H > 32768 || W > 32768) return set_err(VD3D_E_UNSUPPORTED, "nhwc_f16_to_planar3_f32: map %d x %d must be 1 .. 32768 on each side", H, W);
+  if (((uintptr_t)t_nhwc32 & 15) || ((uintptr_t)out_planar & 3)) return set_err(VD3D_E_UNSUPPORTED, "nhwc_f16_to_planar3_f32: t must be 16-byte and out 4-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "esr_tail");
+  vd_launch_nhwc_f16_to_planar3_f32(c->stream, t_nhwc32, H, W, out_planar);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // optional NV12 wire format at the frame I/O boundary (vd3d_nv12.hip)
 VD3D_EXPORT int vd3d_nv12_to_bgr(vd3d_ctx* c, const uint8_t* y_plane, long long y_pitch, const uint8_t* uv_plane, long long uv_pitch, int h, int w,
                                  uint8_t* out_bgr) {

@@ -498,6 +498,46 @@ class Renderer:
         _lib.check(self._L.vd3d_esr_tail_f32(self._ctx, _ptr(t), _ptr(x), H, W, int(r), _ptr(out)))
         return out
 
+    def conv3x3_dense(self, x: torch.Tensor, cin: int, w_frag: torch.Tensor, bias: torch.Tensor, cout: int, out: torch.Tensor, out_offset: int = 0,
+                      slope: float = 1.0, r1: torch.Tensor | None = None, alpha: float = 1.0, r2: torch.Tensor | None = None, beta: float = 1.0,
+                      up2: bool = False) -> torch.Tensor:
+        """One convolution of the RRDB up-scale network on the matrix cores (``vd3d_conv3x3_dense_f16``, include/vd3d.h).  ``x``, ``out``, ``r1``, ``r2``
+        are [1,C,H,W] fp16 tensors in channels_last memory, C being the pixel stride: the first ``cin`` channels of ``x`` are read, channels
+        ``out_offset .. out_offset + cout`` of ``out`` are written -- ``out`` may be ``x`` itself when that slice lies behind ``cin`` (a dense block in
+        one 192-channel buffer).  Result: ``leaky(conv + bias, slope)``, then ``* alpha + r1[:, :cout]`` and ``* beta + r2[:, :cout]`` where given, all in
+        float32.  ``up2``: ``x`` has half the size of ``out`` and is read through a nearest x2 up-sampling.  ``w_frag``:
+        ``upscale.dense_weight_fragments(weight)``; ``bias`` float32 [cout].  Returns ``out``."""
+        for t in (x, out, r1, r2):
+            if t is not None and (t.dtype != torch.float16 or t.dim() != 4 or t.shape[0] != 1 or not t.is_cuda
+                                  or not t.is_contiguous(memory_format=torch.channels_last)):
+                raise AssertionError("conv3x3_dense takes [1,C,H,W] fp16 tensors in channels_last memory")
+        H, W = int(out.shape[2]), int(out.shape[3])
+        if (int(x.shape[2]), int(x.shape[3])) != ((H // 2, W // 2) if up2 else (H, W)) or (up2 and (H % 2 or W % 2)):
+            raise AssertionError("conv3x3_dense: input and output sizes do not match")
+        for r in (r1, r2):
+            if r is not None and (int(r.shape[2]), int(r.shape[3])) != (H, W):
+                raise AssertionError("conv3x3_dense: a residual has the output's size")
+        if (tuple(w_frag.shape) != (int(cin) // 32 * 18, int(cout) // 32, 64, 8) or w_frag.dtype != torch.float16 or not w_frag.is_contiguous()
+                or bias.dtype != torch.float32 or bias.numel() != int(cout)):
+            raise AssertionError("conv3x3_dense: w_frag is dense_weight_fragments(weight) of a [cout,cin,3,3] weight, bias float32 [cout]")
+        self._enter(x, w_frag, bias, r1, r2, out)
+        _lib.check(self._L.vd3d_conv3x3_dense_f16(self._ctx, _ptr(x), H, W, int(x.shape[1]), int(cin), _ptr(w_frag), _ptr(bias), int(cout),
+                                                  float(slope), float(alpha), _ptr(r1) if r1 is not None else None, int(r1.shape[1]) if r1 is not None else 0,
+                                                  float(beta), _ptr(r2) if r2 is not None else None, int(r2.shape[1]) if r2 is not None else 0,
+                                                  int(bool(up2)), _ptr(out), int(out.shape[1]), int(out_offset)))
+        return out
+
+    def nhwc_f16_to_planar3(self, t: torch.Tensor) -> torch.Tensor:
+        """Channels 0..2 of a [1,32,H,W] fp16 channels_last map -> the float32 planar prediction [1,3,H,W] (``vd3d_nhwc_f16_to_planar3_f32``): the tail
+        behind the RRDB network's ``conv_last``, which runs on ``conv3x3_dense`` zero-padded to 32 output channels."""
+        if (t.dtype != torch.float16 or t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 32 or not t.is_contiguous(memory_format=torch.channels_last)):
+            raise AssertionError("nhwc_f16_to_planar3 takes a [1,32,H,W] fp16 tensor in channels_last memory")
+        H, W = int(t.shape[2]), int(t.shape[3])
+        out = torch.empty((1, 3, H, W), dtype=torch.float32, device=self.device)
+        self._enter(t, out)
+        _lib.check(self._L.vd3d_nhwc_f16_to_planar3_f32(self._ctx, _ptr(t), H, W, _ptr(out)))
+        return out
+
     def add_weighted_u8(self, a: torch.Tensor, alpha: float, b: torch.Tensor, beta: float, gamma: float = 0.0) -> torch.Tensor:
         """cv2.addWeighted on uint8 tensors of one shape (blend_images, core/merged_pipeline.py:231-236)."""
         a = a.to(self.device).contiguous()

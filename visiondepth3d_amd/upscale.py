@@ -120,6 +120,18 @@ def conv_weight_fragments(weight: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 3, 1, 4, 2, 5).reshape(36, 2, 64, 8).contiguous()                   # [tap][kc][t][g][i][j] -> [step][t][lane][j]
 
 
+def dense_weight_fragments(weight: torch.Tensor) -> torch.Tensor:
+    """A [Cout,Cin,3,3] convolution weight (Cout 32 or 64, Cin a multiple of 32) in the fragment order ``vd3d_conv3x3_dense_f16`` streams
+    (include/vd3d.h): fp16 [Cin/32 * 18 steps][Cout/32][64 lanes][8], element [(c*9 + kh*3 + kw)*2 + kc][t][l][j] =
+    W[32t + (l & 31)][32c + 16kc + 8(l >> 5) + j][kh][kw].  The K order is 32-channel-chunk-major (the kernel streams the channels through LDS in
+    chunks of 32), so for a [64,64,3,3] weight the image differs from ``conv_weight_fragments`` (tap-major)."""
+    co, ci = int(weight.shape[0]), int(weight.shape[1])
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or co not in (32, 64) or ci % 32 or ci < 32:
+        raise AssertionError("dense_weight_fragments takes a [32 or 64, multiple of 32, 3, 3] weight")
+    w = weight.detach().to(torch.float16).permute(2, 3, 0, 1).reshape(9, co // 32, 32, ci // 32, 2, 2, 8)   # [tap][t][i][c][kc][g][j]
+    return w.permute(3, 0, 4, 1, 5, 2, 6).reshape(ci // 32 * 18, co // 32, 64, 8).contiguous()            # [c][tap][kc][t][g][i][j] -> [step][t][lane][j]
+
+
 def head_weight_matrix(weight: torch.Tensor) -> torch.Tensor:
     """A [64,3,3,3] head convolution weight as the float32 [27,64] matrix ``vd3d_conv3x3_head_f16`` takes: row (kh*3 + kw)*3 + ic, column oc
     (the fp16 values of the checkpoint, widened)."""
@@ -315,10 +327,16 @@ class Upscaler:
     """One Real-ESRGAN network + the HIP glue.  ``renderer`` is a ``visiondepth3d_amd.render_3d.Renderer`` (its context and stream)."""
 
     def __init__(self, renderer, model_name: str = "RealESR_Gx4_fp16", net: nn.Module | None = None, dtype=torch.float16,
-                 hip_body: bool = True):
+                 hip_body: bool = True, rrdb_hip: bool = True):
         """``hip_body``: run the 64 -> 64 body layers of the compact (SRVGG) networks through the hand-written matrix-core kernel
         (``vd3d_conv3x3_c64_f16``: conv + bias + PReLU in one launch), and -- since round 3 -- the 3 -> 64 head, the 64 -> 3 r^2 tail convolution
-        (same kernel, zero-padded) and pixel-shuffle + nearest add through HIP as well: no library call is left in the compact networks."""
+        (same kernel, zero-padded) and pixel-shuffle + nearest add through HIP as well: no library call is left in the compact networks.
+
+        ``rrdb_hip``: the same for ``RRDBNet`` (RealESRGAN_x4plus).  On the GPU in fp16, an RRDBNet with scale 4, 3 input channels, 64 features and 32
+        growth channels runs every one of its 351 convolutions on ``vd3d_conv3x3_dense_f16`` (head: ``vd3d_conv3x3_head_f16``): a dense block lives in
+        one [H][W][192] buffer whose slices the convolutions read and write in place (no ``torch.cat``), the ``* 0.2 + x`` residuals are the kernel's
+        epilogue, and the two nearest x2 up-samplings are folded into the tile loads of ``conv_up1`` / ``conv_up2`` (no ``F.interpolate``).  Any other
+        RRDBNet, dtype or device keeps the module graph.  The default follows the measurement in profiles/r10_rrdb.md (3.2 - 3.4x the module graph)."""
         self.renderer = renderer
         self.device = renderer.device
         self.model_name = model_name
@@ -333,6 +351,62 @@ class Upscaler:
                 and self.net.body[0].out_channels == 64 and self.net.body[0].in_channels == 3
                 and int(getattr(self.net, "upscale", 0)) in (2, 4) and self.net.body[-1].out_channels <= 64):
             self._body = self._prepare_body()
+        self._rrdb = None
+        if (rrdb_hip and self.device.type == "cuda" and dtype == torch.float16 and isinstance(self.net, RRDBNet) and self.net.scale == 4
+                and self.net.conv_first.in_channels == 3 and self.net.conv_first.out_channels == 64 and len(self.net.body) > 0
+                and self.net.body[0].rdb1.conv1.out_channels == 32 and self.net.conv_last.out_channels == 3):
+            self._rrdb = self._prepare_rrdb()
+
+    def _prepare_rrdb(self):
+        """Device-resident operands of the RRDB network, packed once: head (weight matrix, bias), per dense block five (weight fragments, bias), the four
+        64 -> 64 convolutions behind the body, and ``conv_last`` zero-padded from 3 to 32 output channels.  Returns the list of dense blocks (3 per RRDB)."""
+        net, dev = self.net, self.device
+
+        def pack(conv):
+            return dense_weight_fragments(conv.weight).to(dev), conv.bias.detach().float().contiguous().to(dev)
+        self._rrdb_head = (head_weight_matrix(net.conv_first.weight).to(dev), net.conv_first.bias.detach().float().contiguous().to(dev))
+        blocks = [[pack(c) for c in (rdb.conv1, rdb.conv2, rdb.conv3, rdb.conv4, rdb.conv5)] for rrdb in net.body for rdb in (rrdb.rdb1, rrdb.rdb2, rrdb.rdb3)]
+        self._rrdb_mid = [pack(c) for c in (net.conv_body, net.conv_up1, net.conv_up2, net.conv_hr)]
+        wl = torch.zeros((32, 64, 3, 3), dtype=net.conv_last.weight.dtype)
+        wl[:3] = net.conv_last.weight.detach().cpu()
+        bl = torch.zeros(32, dtype=torch.float32)
+        bl[:3] = net.conv_last.bias.detach().float().cpu()
+        self._rrdb_last = (dense_weight_fragments(wl).to(dev), bl.to(dev))
+        return blocks
+
+    def _rdb(self, wb, P, out, r2=None):
+        """One dense block in the 192-channel buffer ``P`` (input in channels 0..63): conv1 .. conv4 append their 32 channels in place, conv5 writes
+        ``conv * 0.2 + x`` (and ``* 0.2 + r2`` for the last block of an RRDB) into channels 0..63 of ``out``."""
+        R = self.renderer
+        for i in range(4):
+            R.conv3x3_dense(P, 64 + 32 * i, wb[i][0], wb[i][1], 32, P, 64 + 32 * i, slope=0.2)
+        R.conv3x3_dense(P, 192, wb[4][0], wb[4][1], 64, out, 0, r1=P, alpha=0.2, r2=r2, beta=0.2)
+
+    def _forward_rrdb(self, x: torch.Tensor) -> torch.Tensor:
+        R = self.renderer
+        H, W = int(x.shape[2]), int(x.shape[3])
+        cl = torch.channels_last
+
+        def buf(c, h, w):
+            return torch.empty((1, c, h, w), dtype=torch.float16, device=self.device, memory_format=cl)
+        feat = R.conv3x3_head(x, self._rrdb_head[0], self._rrdb_head[1], None)
+        P, Q, T = buf(192, H, W), buf(192, H, W), buf(192, H, W)     # three rotating dense-block buffers: an RRDB's input survives its three RDBs
+        R.ordered_after()
+        P[:, :64].copy_(feat)
+        for i in range(0, len(self._rrdb), 3):
+            self._rdb(self._rrdb[i], P, Q)
+            self._rdb(self._rrdb[i + 1], Q, T)
+            self._rdb(self._rrdb[i + 2], T, Q, r2=P)                 # Q's channels 0..63 (the input of rdb2) are dead: the RRDB's output lands there
+            P, Q = Q, P
+        (wb, bb), (w1, b1), (w2, b2), (wh, bh) = self._rrdb_mid
+        t0 = R.conv3x3_dense(P, 64, wb, bb, 64, buf(64, H, W), r1=feat, alpha=1.0)                       # feat + conv_body(body(feat))
+        t1 = R.conv3x3_dense(t0, 64, w1, b1, 64, buf(64, 2 * H, 2 * W), slope=0.2, up2=True)
+        t2 = R.conv3x3_dense(t1, 64, w2, b2, 64, buf(64, 4 * H, 4 * W), slope=0.2, up2=True)
+        t3 = R.conv3x3_dense(t2, 64, wh, bh, 64, buf(64, 4 * H, 4 * W), slope=0.2)
+        t4 = R.conv3x3_dense(t3, 64, self._rrdb_last[0], self._rrdb_last[1], 32, buf(32, 4 * H, 4 * W))
+        out = R.nhwc_f16_to_planar3(t4)
+        R.ordered_after()
+        return out
 
     def _prepare_body(self):
         """Device-resident operands of every layer: head (weight matrix, bias, slope), body [(weight fragments, bias, PReLU slope)], tail (weight
@@ -358,7 +432,9 @@ class Upscaler:
     def _forward(self, x: torch.Tensor) -> torch.Tensor:
         """The network on ``x`` ([1,3,H,W], channels_last).  Library path: the module's own dtype; HIP path (compact networks, fp16): every
         layer hand-written -- head (``vd3d_conv3x3_head_f16``), body and tail convolution (``vd3d_conv3x3_c64_f16``, matrix cores), pixel-shuffle
-        + nearest add (``vd3d_esr_tail_f32``) -- and the result is already the float32 prediction."""
+        + nearest add (``vd3d_esr_tail_f32``) -- and the result is already the float32 prediction.  RRDB path (``rrdb_hip``): ``_forward_rrdb``."""
+        if self._rrdb is not None:
+            return self._forward_rrdb(x)
         if self._body is None:
             return self.net(x)
         R, net = self.renderer, self.net
