@@ -469,6 +469,41 @@ int64_t vd3d_conv3x3_x3_weight_bytes(int Cin, int Cout);
 int vd3d_conv3x3_x3_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
 int vd3d_conv3x3_x3(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
 
+/* The convolutions of the RIFE interpolation network (IFNet HDv3; RifeSession(conv="bf16x3")) in the same bf16x3 arithmetic: exact three-term truncation
+ * split of every float32 operand, the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 into one float32 accumulator and x1 w1 into another, summed in the epilogue
+ * (v_mfma_f32_32x32x16_bf16).  Float32 NHWC in and out, NaN / Inf inputs give NaN, no range limit, bit-for-bit repeatable.
+ *   kind VD3D_IFN_K3S1: Conv2d(3, stride 1, padding 1), output H x W.            W: [Cout][Cin][3][3]
+ *   kind VD3D_IFN_K3S2: Conv2d(3, stride 2, padding 1), output (H+1)/2 x (W+1)/2. W: [Cout][Cin][3][3]
+ *   kind VD3D_IFN_T4S2: ConvTranspose2d(4, stride 2, padding 1), output 2H x 2W, computed as four output phases of 2 x 2 taps.  W: [Cin][Cout][4][4]
+ *   X: pixels of pitch x_stride floats, channels [0, Cin) are read, Cin a positive multiple of 16.  H x W is the INPUT size, B frames.
+ *   Y: pixels of pitch y_stride floats, the Cout (32, 64 or 96) channels at [y_offset, y_offset + Cout) are written, nothing else.  A network with other
+ *      channel counts pads weights, bias and slopes with zeros (visiondepth3d_amd.rife does: 11 / 45 / 90 -> 16 / 64 / 96).
+ *   epilogue, in float32: v = acc + lo + bias[oc]; slope != NULL: v = v >= 0 ? v : slope[oc] * v (per-channel PReLU); r != NULL: v += r[pixel][oc], r being
+ *      output-sized pixels of pitch r_stride.
+ * Rules (VD3D_E_UNSUPPORTED with a message that names the broken one, nothing launched): the kinds and channel counts above; 1 <= B <= 65 535; H, W >= 1;
+ * x_stride a multiple of 4 and >= Cin; y_stride >= y_offset + Cout, y_offset >= 0; r_stride >= Cout; X and the image 16-byte aligned, bias / slope / r / Y
+ * 4-byte aligned; the bytes written meet neither the bytes read (a slice of the same buffer that intersects channels [0, Cin) would be a race between
+ * workgroups) nor the residual.  The weights are split and packed once into vd3d_conv_ifn_weight_bytes(kind, Cin, Cout) bytes (host-only; < 0: not built);
+ * the image is opaque, belongs to its kind and is only valid for this library version. */
+enum { VD3D_IFN_K3S1 = 0, VD3D_IFN_K3S2 = 1, VD3D_IFN_T4S2 = 2 };
+int64_t vd3d_conv_ifn_weight_bytes(int kind, int Cin, int Cout);
+int vd3d_conv_ifn_pack_weights(vd3d_ctx* ctx, int kind, const float* W, int Cin, int Cout, void* image);
+int vd3d_conv_ifn(vd3d_ctx* ctx, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* w_image, const float* bias,
+                  const float* slope_or_null, int Cout, const float* r_or_null, int r_stride, float* Y, int y_stride, int y_offset);
+/* The float32 glue between the blocks of that network.  x6: the network input, planar [N][6][h][w] (frame 0, frame 1, in [0, 1]); the network works on
+ * Hp x Wp = h, w rounded up to multiples of 32, the padding reads as 0.  state: NHWC [N][Hp][Wp][8] = running flow (4), mask (1), zeros (3).
+ * "warp" = grid_sample(bilinear, padding_mode="border", align_corners=True) of a frame at pixel + flow, computed in pixel units (sample position clamped to
+ * [0, Wp-1] x [0, Hp-1]).  scale in {1, 2, 4}; N <= 65 535; every pointer 16-byte aligned.
+ *   vd3d_rife_warp_pack: a block's input, NHWC [N][Hp/scale][Wp/scale][16] = F.interpolate(scale_factor=1/scale, bilinear, align_corners=False) of
+ *      [warp(frame 0, flow[0:2]) (3), warp(frame 1, flow[2:4]) (3), mask (1), flow / scale (4)], then 5 zeros.  The down-scale is the mean of the centre 2 x 2
+ *      pixels of each cell.  state_or_null == NULL: flow and mask are zero (the first block).
+ *   vd3d_rife_update: flow += up(t[..][0:4]) * scale, mask += up(t[..][4]), up = F.interpolate(scale_factor=scale, bilinear, align_corners=False);
+ *      t: NHWC [N][Hp/scale][Wp/scale] pixels of pitch t_stride >= 5 (a multiple of 4).  first != 0: the state is written, not added to.
+ *   vd3d_rife_blend: out planar [N][3][h][w] = warp(frame 0) * m + warp(frame 1) * (1 - m), m = sigmoid(mask): what vd3d_rife_postprocess takes. */
+int vd3d_rife_warp_pack(vd3d_ctx* ctx, const float* x6, const float* state_or_null, int N, int h, int w, int scale, float* out16);
+int vd3d_rife_update(vd3d_ctx* ctx, const float* t, int t_stride, int first, int N, int h, int w, int scale, float* state);
+int vd3d_rife_blend(vd3d_ctx* ctx, const float* x6, const float* state, int N, int h, int w, float* out);
+
 /* F.interpolate(mode="bilinear", align_corners=True) of an NHWC (channels_last) tensor [B][ih][iw][C] -> [B][oh][ow][C] of
  * `dtype`, C a multiple of 8 (bf16) / 4 (f32): the up-samplings of the DPT neck / head (a25). */
 int vd3d_upsample_bilinear_nhwc(vd3d_ctx* ctx, int dtype, const void* in, void* out, int B, int ih, int iw, int oh, int ow, int C);

@@ -1505,6 +1505,96 @@ VD3D_EXPORT int vd3d_conv3x3_x3(vd3d_ctx* c, const float* X, int B, int H, int W
   return 0;
 }
 
+// the convolutions of the interpolation network (vd3d_conv_ifn.hip): every rule of include/vd3d.h is checked here, before anything is launched
+VD3D_EXPORT int64_t vd3d_conv_ifn_weight_bytes(int kind, int Cin, int Cout) { return (int64_t)vd_conv_ifn_weight_bytes(kind, Cin, Cout); }
+
+static int conv_ifn_shape_err(int kind, int Cin, int Cout) {
+  return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: shape not built: kind %d must be 0 (3x3 s1), 1 (3x3 s2) or 2 (transposed 4x4 s2), C_in %d a positive multiple of 16 and C_out %d one of 32, 64, 96",
+                 kind, Cin, Cout);
+}
+
+VD3D_EXPORT int vd3d_conv_ifn_pack_weights(vd3d_ctx* c, int kind, const float* W, int Cin, int Cout, void* image) {
+  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "conv_ifn: null argument");
+  if (vd_conv_ifn_weight_bytes(kind, Cin, Cout) < 0) return conv_ifn_shape_err(kind, Cin, Cout);
+  if ((reinterpret_cast<uintptr_t>(image) & 15) || (reinterpret_cast<uintptr_t>(W) & 3)) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: the weight image must be 16-byte aligned (the weight 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_conv_ifn_pack(c->stream, kind, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "conv_ifn: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_conv_ifn(vd3d_ctx* c, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* w_image, const float* bias,
+                              const float* slope_or_null, int Cout, const float* r_or_null, int r_stride, float* Y, int y_stride, int y_offset) {
+  if (!c || !X || !w_image || !bias || !Y) return set_err(VD3D_E_INVALID, "conv_ifn: null argument");
+  if (vd_conv_ifn_weight_bytes(kind, Cin, Cout) < 0) return conv_ifn_shape_err(kind, Cin, Cout);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: batch %d must be 1 .. 65535 (one grid row per frame)", B);
+  if (H < 1 || W < 1 || H > 32768 || W > 32768) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: map %d x %d must be 1 .. 32768 on each side", H, W);
+  if (x_stride < Cin || (x_stride & 3)) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: x_stride %d must be a multiple of 4 and >= C_in %d", x_stride, Cin);
+  if (y_offset < 0 || y_stride < y_offset + Cout)
+    return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: y_offset %d must be >= 0 and y_offset + C_out %d <= y_stride %d", y_offset, Cout, y_stride);
+  if (r_or_null && r_stride < Cout) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: the residual's r_stride %d must be >= C_out %d", r_stride, Cout);
+  if (((uintptr_t)X | (uintptr_t)w_image) & 15) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: the input and the weight image must be 16-byte aligned");
+  if (((uintptr_t)bias | (uintptr_t)slope_or_null | (uintptr_t)r_or_null | (uintptr_t)Y) & 3)
+    return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: bias, slope, residual and output must be 4-byte aligned");
+  const int Ho = kind == VD3D_IFN_K3S2 ? (H + 1) / 2 : kind == VD3D_IFN_T4S2 ? 2 * H : H, Wo = kind == VD3D_IFN_K3S2 ? (W + 1) / 2 : kind == VD3D_IFN_T4S2 ? 2 * W : W;
+  {   // the bytes read (channels [0, C_in) of every input pixel) and the bytes written (the output slice of every pixel) must not meet
+    const long long in_pix = (long long)B * H * W, out_pix = (long long)B * Ho * Wo;
+    const uintptr_t xb = (uintptr_t)X, xe = xb + (uintptr_t)(((in_pix - 1) * x_stride + Cin) * 4);
+    const uintptr_t yb = (uintptr_t)Y + (uintptr_t)y_offset * 4, ye = (uintptr_t)Y + (uintptr_t)(((out_pix - 1) * y_stride + y_offset + Cout) * 4);
+    const bool same_grid = (const void*)X == (const void*)Y && x_stride == y_stride && kind == VD3D_IFN_K3S1;
+    if (same_grid ? y_offset < Cin : (xb < ye && yb < xe))
+      return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: the output slice [%d, %d) meets the input channels [0, %d) of the same buffer (a race between workgroups)",
+                     y_offset, y_offset + Cout, Cin);
+    if (r_or_null) {
+      const uintptr_t rb = (uintptr_t)r_or_null, re = rb + (uintptr_t)(((out_pix - 1) * r_stride + Cout) * 4);
+      const bool rgrid = (const void*)r_or_null == (const void*)Y && r_stride == y_stride;
+      if (rgrid ? y_offset < Cout : (rb < ye && yb < re)) return set_err(VD3D_E_UNSUPPORTED, "conv_ifn: the residual overlaps the output slice");
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "conv_ifn");
+  if (!vd_launch_conv_ifn(c->stream, kind, X, B, H, W, x_stride, Cin, w_image, bias, slope_or_null, Cout, r_or_null, r_stride, Y, y_stride, y_offset))
+    return set_err(VD3D_E_HIP, "conv_ifn: the dynamic LDS opt-in failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+static int rife_glue_err(const char* what, int N, int h, int w, int scale) {
+  return set_err(VD3D_E_UNSUPPORTED, "%s: N %d must be 1 .. 65535, the frame %d x %d 1 .. 32768 on each side, scale %d one of 1, 2, 4 and every pointer 16-byte aligned", what, N, h, w, scale);
+}
+static bool rife_glue_ok(int N, int h, int w, int scale) { return N >= 1 && N <= 65535 && h >= 1 && w >= 1 && h <= 32768 && w <= 32768 && (scale == 1 || scale == 2 || scale == 4); }
+
+VD3D_EXPORT int vd3d_rife_warp_pack(vd3d_ctx* c, const float* x6, const float* state_or_null, int N, int h, int w, int scale, float* out16) {
+  if (!c || !x6 || !out16) return set_err(VD3D_E_INVALID, "rife_warp_pack: null argument");
+  if (!rife_glue_ok(N, h, w, scale) || (((uintptr_t)x6 | (uintptr_t)state_or_null | (uintptr_t)out16) & 15)) return rife_glue_err("rife_warp_pack", N, h, w, scale);
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "rife_glue");
+  vd_launch_rife_warp_pack(c->stream, x6, state_or_null, state_or_null ? 0 : 1, N, h, w, (h + 31) / 32 * 32, (w + 31) / 32 * 32, scale, out16);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_rife_update(vd3d_ctx* c, const float* t_, int t_stride, int first, int N, int h, int w, int scale, float* state) {
+  if (!c || !t_ || !state) return set_err(VD3D_E_INVALID, "rife_update: null argument");
+  if (!rife_glue_ok(N, h, w, scale) || (((uintptr_t)t_ | (uintptr_t)state) & 15)) return rife_glue_err("rife_update", N, h, w, scale);
+  if (t_stride < 5 || (t_stride & 3)) return set_err(VD3D_E_UNSUPPORTED, "rife_update: t_stride %d must be a multiple of 4 and >= 5", t_stride);
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "rife_glue");
+  vd_launch_rife_update(c->stream, t_, t_stride, first ? 1 : 0, N, (h + 31) / 32 * 32, (w + 31) / 32 * 32, scale, state);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_rife_blend(vd3d_ctx* c, const float* x6, const float* state, int N, int h, int w, float* out) {
+  if (!c || !x6 || !state || !out) return set_err(VD3D_E_INVALID, "rife_blend: null argument");
+  if (!rife_glue_ok(N, h, w, 1) || (((uintptr_t)x6 | (uintptr_t)state | (uintptr_t)out) & 15)) return rife_glue_err("rife_blend", N, h, w, 1);
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "rife_glue");
+  vd_launch_rife_blend(c->stream, x6, state, N, h, w, (h + 31) / 32 * 32, (w + 31) / 32 * 32, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 VD3D_EXPORT int64_t vd3d_attention_x3_workspace_bytes(int B, int T, int H, int D, int mode) { return (int64_t)vd_attn_x3_workspace_bytes(B, T, H, D, mode); }
 
 VD3D_EXPORT int vd3d_attention_x3(vd3d_ctx* c, const float* qkv, int B, int T, int H, int D, float scale, int mode, void* workspace, int64_t workspace_bytes, float* out) {

@@ -238,6 +238,15 @@ bool vd_launch_conv3x3_x2(hipStream_t s, const float* X, int B, int H, int W, in
 long long vd_conv3x3_x3_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+// vd3d_conv_ifn.hip: the convolutions of the RIFE interpolation network in the bf16x3 arithmetic (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
+// bias / PReLU / residual epilogue, channel slices of strided NHWC buffers) and the float32 glue between its blocks
+long long vd_conv_ifn_weight_bytes(int kind, int Cin, int Cout);
+bool vd_launch_conv_ifn_pack(hipStream_t s, int kind, const float* W, int Cin, int Cout, void* img);
+bool vd_launch_conv_ifn(hipStream_t s, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* wimg, const float* bias,
+                        const float* slope, int Cout, const float* R, int r_stride, float* Y, int y_stride, int y_offset);
+void vd_launch_rife_warp_pack(hipStream_t s, const float* X, const float* S, int first, int N, int h, int w, int Hp, int Wp, int scale, float* out);
+void vd_launch_rife_update(hipStream_t s, const float* T, int t_stride, int first, int N, int Hp, int Wp, int scale, float* S);
+void vd_launch_rife_blend(hipStream_t s, const float* X, const float* S, int N, int h, int w, int Hp, int Wp, float* out);
 // vd3d_attn.hip: softmax(Q K^T scale) V with both products as split-bf16 MFMA work
 long long vd_attn_x3_workspace_bytes(int B, int T, int H, int D, int mode);
 bool vd_launch_attn_x3(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, void* ws, float* out, int mode);

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._abi import DEPTH_BGR_U8, DEPTH_F32, DEPTH_GRAY_U8, DT_BF16, DT_F16, DT_F32, FORMAT_IDS, FrameScalars, RenderParams, ShiftParams, State
 from .geometry import aspect_ratios  # noqa: F401  (re-exported like the reference module does)
 from .params import reference_aten_threads, render_kwargs_to_params, shift_params_from_kwargs
@@ -744,6 +744,83 @@ class Renderer:
         out = torch.empty((B, int(Cout), H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         self._enter(x, w_image, out)
         _lib.check(self._L.vd3d_conv3x3_x3(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
+        return out
+
+    def conv_ifn_pack(self, kind: int, weight: torch.Tensor):
+        """Split + pack a float32 weight for ``conv_ifn``: ``[Cout, Cin, 3, 3]`` for ``_abi.IFN_K3S1`` / ``IFN_K3S2``, ``[Cin, Cout, 4, 4]`` (ConvTranspose2d's layout) for
+        ``IFN_T4S2``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 96})."""
+        w = weight.detach().to(self.device, torch.float32).contiguous()
+        if kind == _abi.IFN_T4S2:
+            Cin, Cout, kh, kw = w.shape
+            ok = (kh, kw) == (4, 4)
+        else:
+            Cout, Cin, kh, kw = w.shape
+            ok = (kh, kw) == (3, 3)
+        nb = int(self._L.vd3d_conv_ifn_weight_bytes(int(kind), Cin, Cout)) if ok else -1
+        if nb < 0:
+            return None
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(self._L.vd3d_conv_ifn_pack_weights(self._ctx, int(kind), _ptr(w), Cin, Cout, _ptr(img)))
+        return img
+
+    def conv_ifn(self, kind: int, x: torch.Tensor, cin: int, w_image: torch.Tensor, bias: torch.Tensor, slope, cout: int, out: torch.Tensor,
+                 out_offset: int = 0, residual=None) -> torch.Tensor:
+        """One convolution of the interpolation network in the bf16x3 arithmetic (``vd3d_conv_ifn``, include/vd3d.h).  ``x``, ``out``, ``residual``: float32
+        channels_last ``[B, C, H, W]`` tensors whose C is the pixel pitch; channels ``[0, cin)`` of ``x`` are read and ``[out_offset, out_offset + cout)`` of ``out``
+        written.  ``out`` has the kind's output size (same, halved rounding up, doubled).  ``bias``: float32 ``[cout]``; ``slope``: per-channel PReLU slopes or None;
+        ``residual``: added after the activation, or None.  Returns ``out``."""
+        for t in (x, out, residual):
+            if t is not None and (t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last)):
+                raise AssertionError("conv_ifn takes float32 [B,C,H,W] tensors in channels_last memory")
+        B, _, H, W = x.shape
+        Ho, Wo = {_abi.IFN_K3S1: (H, W), _abi.IFN_K3S2: ((H + 1) // 2, (W + 1) // 2), _abi.IFN_T4S2: (2 * H, 2 * W)}[int(kind)]
+        if out.shape[0] != B or tuple(out.shape[2:]) != (Ho, Wo) or (residual is not None and (residual.shape[0] != B or tuple(residual.shape[2:]) != (Ho, Wo))):
+            raise AssertionError("conv_ifn: the output and the residual have the kind's output size")
+        if bias.dtype != torch.float32 or bias.numel() != cout or (slope is not None and (slope.dtype != torch.float32 or slope.numel() != cout)):
+            raise AssertionError("conv_ifn: bias and slope are float32 [cout]")
+        self._enter(x, w_image, bias, slope, residual, out)
+        _lib.check(self._L.vd3d_conv_ifn(self._ctx, int(kind), _ptr(x), B, H, W, int(x.shape[1]), int(cin), _ptr(w_image), _ptr(bias),
+                                         _ptr(slope) if slope is not None else None, int(cout), _ptr(residual) if residual is not None else None,
+                                         int(residual.shape[1]) if residual is not None else 0, _ptr(out), int(out.shape[1]), int(out_offset)))
+        return out
+
+    @staticmethod
+    def _rife_pad(h: int, w: int):
+        return (h + 31) // 32 * 32, (w + 31) // 32 * 32
+
+    def rife_warp_pack(self, x6: torch.Tensor, state, scale: int, out: torch.Tensor) -> torch.Tensor:
+        """The 16-channel input of one IFBlock (``vd3d_rife_warp_pack``): ``x6`` contiguous float32 ``[N, 6, h, w]``, ``state`` ``[N, Hp, Wp, 8]`` (flow, mask) or None for
+        the first block, ``out`` ``[N, Hp/scale, Wp/scale, 16]`` (NHWC memory, i.e. a channels_last ``[N, 16, ., .]`` tensor permuted)."""
+        N, _, h, w = x6.shape
+        Hp, Wp = self._rife_pad(h, w)
+        if x6.dtype != torch.float32 or x6.shape[1] != 6 or not x6.is_contiguous() or not out.is_contiguous() or tuple(out.shape) != (N, Hp // scale, Wp // scale, 16):
+            raise AssertionError("rife_warp_pack: x6 contiguous float32 [N,6,h,w], out [N,Hp/s,Wp/s,16]")
+        if state is not None and (tuple(state.shape) != (N, Hp, Wp, 8) or not state.is_contiguous()):
+            raise AssertionError("rife_warp_pack: state is [N,Hp,Wp,8]")
+        self._enter(x6, state, out)
+        _lib.check(self._L.vd3d_rife_warp_pack(self._ctx, _ptr(x6), _ptr(state) if state is not None else None, N, h, w, int(scale), _ptr(out)))
+        return out
+
+    def rife_update(self, t: torch.Tensor, state: torch.Tensor, scale: int, first: bool, h: int, w: int) -> torch.Tensor:
+        """``state[..., :4] += up(t[..., :4]) * scale; state[..., 4] += up(t[..., 4])`` (``vd3d_rife_update``; ``first``: written instead of added).  ``t``: contiguous
+        ``[N, Hp/scale, Wp/scale, C]`` (C the pitch), ``state`` ``[N, Hp, Wp, 8]`` for an ``h x w`` frame."""
+        Hp, Wp = self._rife_pad(h, w)
+        N = state.shape[0]
+        if tuple(state.shape) != (N, Hp, Wp, 8) or tuple(t.shape[:3]) != (N, Hp // scale, Wp // scale) or not t.is_contiguous() or not state.is_contiguous():
+            raise AssertionError("rife_update: t [N,Hp/s,Wp/s,C], state [N,Hp,Wp,8]")
+        self._enter(t, state)
+        _lib.check(self._L.vd3d_rife_update(self._ctx, _ptr(t), int(t.shape[3]), 1 if first else 0, N, int(h), int(w), int(scale), _ptr(state)))
+        return state
+
+    def rife_blend(self, x6: torch.Tensor, state: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """The network's output (``vd3d_rife_blend``): both frames warped by the final flow, blended by sigmoid(mask), cropped: ``out`` contiguous ``[N, 3, h, w]``."""
+        N, _, h, w = x6.shape
+        Hp, Wp = self._rife_pad(h, w)
+        if tuple(state.shape) != (N, Hp, Wp, 8) or tuple(out.shape) != (N, 3, h, w) or not out.is_contiguous() or not x6.is_contiguous() or x6.dtype != torch.float32:
+            raise AssertionError("rife_blend: x6 [N,6,h,w], state [N,Hp,Wp,8], out [N,3,h,w], float32 contiguous")
+        self._enter(x6, state, out)
+        _lib.check(self._L.vd3d_rife_blend(self._ctx, _ptr(x6), _ptr(state), N, h, w, _ptr(out)))
         return out
 
     def upsample_bilinear(self, x: torch.Tensor, size) -> torch.Tensor:
