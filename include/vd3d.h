@@ -520,6 +520,21 @@ int vd3d_nhwc_bias_act_f32(vd3d_ctx* ctx, const float* y, const float* bias_or_n
 int vd3d_upsample_bilinear_bias_nhwc_f32(vd3d_ctx* ctx, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C);
 int vd3d_dpt_head_tail_f32(vd3d_ctx* ctx, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, float* out);
 
+/* The DPT head's 3 x 3 convolution with its up-sampling in front and, optionally, the tail behind, in one exact-float32 kernel (float32 operands on
+ * v_mfma_f32_32x32x2_f32, float32 accumulation, one fixed K order -- 16-channel chunk, tap, channel -- no split-K, no atomics: identical from run to run):
+ *     y = conv3x3(up(x) + b_in)     x float32 NHWC [B][ih][iw][Cin]; up = bilinear, align_corners=True, to [oh][ow]: bit for bit what
+ *                                   vd3d_upsample_bilinear_bias_nhwc_f32 writes (ih == oh && iw == ow: the identity); zero padding 1, stride 1, no bias
+ *     b2, w3 given:  out[B][oh][ow]       = max(b3 + sum_c w3[c] * max(y[c] + b2[c], 0), 0) * scale      (vd3d_dpt_head_tail_f32's function)
+ *     b2, w3 NULL:   out[B][oh][ow][Cout] = y
+ * The intermediate maps of the three launches it replaces are never written.  Built: Cin 32 | 64 | 128 -> Cout 32 with the tail, Cin 128 -> Cout 64 plain;
+ * 1 <= B <= 65 535, oh, ow >= 2; x, b_in, the image, b2, w3 and a plain output 16-byte aligned.  Anything else is VD3D_E_UNSUPPORTED and nothing is launched.
+ * The weights [Cout][Cin][3][3] are packed once into vd3d_dpt_head_conv_weight_bytes(Cin, Cout) bytes (host-only; < 0: shape not built):
+ * [chunk Cin / 16][tap 9][quad 4][oc Cout][4 floats]. */
+int64_t vd3d_dpt_head_conv_weight_bytes(int Cin, int Cout);
+int vd3d_dpt_head_conv_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
+int vd3d_dpt_head_conv_f32(vd3d_ctx* ctx, const float* x, const float* b_in, int B, int ih, int iw, int oh, int ow, int Cin, const void* w_image, int Cout,
+                           const float* b2_or_null, const float* w3_or_null, float b3, float scale, float* out);
+
 /* The reassemble stage's transposed convolutions of DPT-Large (DPTReassembleLayer.resize = ConvTranspose2d(C, C, kernel_size=s, stride=s, padding=0), s = 4 / 2):
  * kernel == stride, so the windows do not overlap and the layer is a GEMM Y[p][(i, j, co)] = sum_ci X[p][ci] W[ci][co][i][j] (vd3d_gemm_x3 with the weight
  * permuted to [(i, j, co)][ci]) followed by this scatter: y [P = B*H*W][s][s][C] float32 -> out NHWC [B][H*s][W*s][C] float32,

@@ -1673,6 +1673,33 @@ VD3D_EXPORT int vd3d_dpt_head_tail_f32(vd3d_ctx* c, const float* y, const float*
   HIPCHK(hipGetLastError());
   return 0;
 }
+VD3D_EXPORT int64_t vd3d_dpt_head_conv_weight_bytes(int Cin, int Cout) { return (int64_t)vd_dpt_head_conv_weight_bytes(Cin, Cout); }
+VD3D_EXPORT int vd3d_dpt_head_conv_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
+  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  if (vd_dpt_head_conv_weight_bytes(Cin, Cout) < 0)
+    return set_err(VD3D_E_UNSUPPORTED, "dpt_head_conv: shape not built: %d -> %d channels (built: 32 | 64 | 128 -> 32 with the tail, 128 -> 64 plain)", Cin, Cout);
+  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "dpt_head_conv: the weight image must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_dpt_head_conv_pack(c->stream, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "dpt_head_conv: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_dpt_head_conv_f32(vd3d_ctx* c, const float* x, const float* b_in, int B, int ih, int iw, int oh, int ow, int Cin, const void* w_image, int Cout,
+                                       const float* b2_or_null, const float* w3_or_null, float b3, float scale, float* out) {
+  if (!c || !x || !b_in || !w_image || !out || (b2_or_null == nullptr) != (w3_or_null == nullptr)) return set_err(VD3D_E_INVALID, "bad argument");
+  const bool tail = b2_or_null != nullptr;
+  if (!vd_dpt_head_conv_shape_ok(B, ih, iw, oh, ow, Cin, Cout, tail))
+    return set_err(VD3D_E_UNSUPPORTED, "dpt_head_conv: shape not built: %d -> %d channels %s, batch %d, %d x %d -> %d x %d (built: 32 | 64 | 128 -> 32 with the tail, "
+                   "128 -> 64 plain; batch 1 .. 65535; output at least 2 x 2; a frame below 2^31 elements)", Cin, Cout, tail ? "with the tail" : "plain", B, ih, iw, oh, ow);
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(b_in) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) ||
+      (reinterpret_cast<uintptr_t>(out) & (tail ? 3 : 15)) || (tail && ((reinterpret_cast<uintptr_t>(b2_or_null) & 15) || (reinterpret_cast<uintptr_t>(w3_or_null) & 15))))
+    return set_err(VD3D_E_UNSUPPORTED, "dpt_head_conv: x, b_in, the weight image, b2, w3 and a plain output must be 16-byte aligned (the tail's output 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_dpt_head_conv_f32(c->stream, x, b_in, B, ih, iw, oh, ow, Cin, w_image, Cout, b2_or_null, w3_or_null, b3, scale, out))
+    return set_err(VD3D_E_HIP, "dpt_head_conv: the dynamic LDS opt-in or the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 VD3D_EXPORT int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* c, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out) {
   if (!c || !y || !out || B < 1 || H < 1 || W < 1 || s < 1 || C < 1) return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));

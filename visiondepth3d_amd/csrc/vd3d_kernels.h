@@ -238,6 +238,12 @@ bool vd_launch_conv3x3_x2(hipStream_t s, const float* X, int B, int H, int W, in
 long long vd_conv3x3_x3_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+// vd3d_conv_head.hip: conv3x3(up(x) + b_in) [+ the head's tail] in exact float32 (v_mfma_f32_32x32x2_f32); b2 == nullptr: plain NHWC output
+long long vd_dpt_head_conv_weight_bytes(int Cin, int Cout);
+bool vd_launch_dpt_head_conv_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
+bool vd_dpt_head_conv_shape_ok(int B, int ih, int iw, int oh, int ow, int Cin, int Cout, bool tail);
+bool vd_launch_dpt_head_conv_f32(hipStream_t s, const float* x, const float* b_in, int B, int ih, int iw, int oh, int ow, int Cin, const void* wimg, int Cout,
+                                 const float* b2, const float* w3, float b3, float scale, float* out);
 // vd3d_conv_ifn.hip: the convolutions of the RIFE interpolation network in the bf16x3 arithmetic (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
 // bias / PReLU / residual epilogue, channel slices of strided NHWC buffers) and the float32 glue between its blocks
 long long vd_conv_ifn_weight_bytes(int kind, int Cin, int Cout);

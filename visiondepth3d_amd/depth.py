@@ -202,7 +202,10 @@ class DepthPipe:
         two (DA and DPT-Large alike) -- run on ``vd3d_conv3x3_x3``, the same three-term / six-product arithmetic as the GEMM (include/vd3d.h), for 32 / 64 /
         128 / 256 output channels and input channels in multiples of 16.  Maps below the measured launch-size rule (``CONV_X3_MIN_TILES``) stay on the
         library; nothing else falls back.  ``conv_routes`` (module name -> ("bf16x3" | "library", reason)) records, per forward, where each of these
-        convolutions ran and why.
+        convolutions ran and why.  In the default float32 mode (``gemm="f32"``, ``conv=None``, with a renderer) the head's up-sampling, its second
+        convolution and everything behind it run as ONE exact-float32 MFMA launch (``vd3d_dpt_head_conv_f32``: 32 | 64 | 128 -> 32 channels);
+        ``conv_routes["head.conv2"]`` is then ``("f32-fused", ...)``, or ``("library", reason)`` where the three launches stay (a shape that is not
+        built, ``VD3D_HEAD_FUSED=0``).
         ``renderer``: a ``visiondepth3d_amd.render_3d.Renderer`` on the SAME stream as the network (default stream); when given the
         image-processor front end, the residual-add + LayerNorm pairs and the DPT up-samplings run as fused HIP launches.
         ``model`` / ``processor``: an already constructed Hugging Face depth model and its image-processor constants
@@ -449,10 +452,45 @@ class DepthPipe:
                 and head.conv2.bias is not None and head.conv3.bias is not None and head.conv1.bias is not None):
             tail_operands = _head_tail_operands(head.conv3)
 
+        # float32 mode: up-sampling + conv2 + tail as ONE exact-float32 MFMA launch (vd3d_dpt_head_conv_f32); VD3D_HEAD_FUSED=0: A/B switch back to the three launches
+        head_fused = self.gemm == "f32" and self.conv != "bf16x3" and self.device.type == "cuda"   # (the kernel reads device memory: a pipe on the CPU keeps its graph)
+        head_img = {}   # the packed conv2 weights per parameter version (None = shape not built)
+
+        def head_conv2_image():
+            m = head.conv2
+            if os.environ.get("VD3D_HEAD_FUSED", "1") == "0":
+                return None, "VD3D_HEAD_FUSED=0"
+            if m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1:
+                return None, "not a 3 x 3 / stride 1 / padding 1 convolution"
+            try:
+                key = (m.weight.data_ptr(), m.weight._version)
+            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
+                key = (m.weight.data_ptr(),)
+            if head_img.get("key") != key:
+                head_img["key"], head_img["img"] = key, (R.dpt_head_conv_pack(m.weight) if m.out_channels == 32 else None)
+            if head_img["img"] is None:
+                return None, f"shape not built: {m.in_channels} -> {m.out_channels} channels"
+            if head.conv1.bias.data_ptr() % 16 or m.bias.data_ptr() % 16 or tail_operands()[0].data_ptr() % 16:
+                return None, "a bias or the 1x1 weight is not 16-byte aligned"
+            return head_img["img"], f"{m.in_channels} -> {m.out_channels} channels"
+
         def head_fwd(hidden_states, patch_height, patch_width):
             x = hidden_states[head.head_in_index]
             size = (int(patch_height * head.patch_size), int(patch_width * head.patch_size))
             if tail_operands is not None and x.dtype == torch.float32:
+                img = None
+                if head_fused:
+                    img, why = head_conv2_image()
+                    if img is not None and (size[0] < 2 or size[1] < 2):
+                        img, why = None, f"output {size[0]} x {size[1]} below 2 x 2"
+                    self.conv_routes[names[id(head.conv2)]] = ("f32-fused" if img is not None else "library", why)
+                if img is not None:
+                    y1 = conv_nb(head.conv1, x.contiguous(memory_format=CL))
+                    if self._flop_count is not None:   # exactly what conv_nb(head.conv2, .) and the tail line below add
+                        n_out = float(head.conv2.out_channels) * size[0] * size[1]
+                        self._flop_count[0] += 2.0 * n_out * head.conv2.in_channels * 9 + 2.0 * n_out
+                    w3, b3 = tail_operands()
+                    return R.dpt_head_conv(y1, head.conv1.bias, size, img, head.conv2.bias, w3, b3, float(head.max_depth))
                 h = R.upsample_bilinear_bias(conv_nb(head.conv1, x.contiguous(memory_format=CL)), size, head.conv1.bias)
                 y = conv_nb(head.conv2, h)
                 if self._flop_count is not None:

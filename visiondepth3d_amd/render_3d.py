@@ -869,6 +869,44 @@ class Renderer:
         _lib.check(self._L.vd3d_dpt_head_tail_f32(self._ctx, _ptr(y), _ptr(b2), _ptr(w3), float(b3), float(scale), B * h * w, Cc, _ptr(out)))
         return out
 
+    def dpt_head_conv_pack(self, weight: torch.Tensor):
+        """Pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``dpt_head_conv``; ``None`` when the shape is not built (Cin 32 | 64 | 128 -> Cout 32
+        with the tail, Cin 128 -> Cout 64 plain)."""
+        w = weight.detach().to(self.device, torch.float32).contiguous()
+        Cout, Cin, kh, kw = w.shape
+        nb = int(self._L.vd3d_dpt_head_conv_weight_bytes(Cin, Cout)) if (kh, kw) == (3, 3) else -1
+        if nb < 0:
+            return None
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(self._L.vd3d_dpt_head_conv_pack_weights(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
+        return img
+
+    def dpt_head_conv(self, x, b_in, size, w_image, b2=None, w3=None, b3: float = 0.0, scale: float = 1.0, Cout=None):
+        """conv3x3(upsample_bilinear_bias(x, size, b_in)) in one exact-float32 kernel (include/vd3d.h vd3d_dpt_head_conv_f32), W given as
+        ``dpt_head_conv_pack(W)``.  With ``b2`` and ``w3`` (Cout 32): -> [B,h,w] = relu(b3 + sum_c w3[c] relu(y + b2[c])) * scale, ``dpt_head_tail``'s function;
+        without (Cout 64): -> channels_last [B,Cout,h,w], the convolution without a bias."""
+        self._nhwc_f32(x)
+        if (b2 is None) != (w3 is None):
+            raise ValueError("dpt_head_conv: b2 and w3 go together")
+        B, Cin, ih, iw = x.shape
+        oh, ow = int(size[0]), int(size[1])
+        tail = b2 is not None
+        Cout = int(Cout) if Cout is not None else (32 if tail else 64)
+        for name, t, n in (("b_in", b_in, Cin), ("b2", b2, Cout), ("w3", w3, Cout)):
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"dpt_head_conv: {name} must be {n} contiguous float32 values")
+        if w_image is None or w_image.numel() != int(self._L.vd3d_dpt_head_conv_weight_bytes(Cin, Cout)):
+            raise ValueError(f"dpt_head_conv: the weight image does not belong to a built {Cin} -> {Cout} convolution")
+        if tail:
+            out = torch.empty((B, oh, ow), dtype=torch.float32, device=x.device)
+        else:
+            out = torch.empty((B, Cout, oh, ow), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        self._enter(x, b_in, w_image, b2, w3, out)
+        _lib.check(self._L.vd3d_dpt_head_conv_f32(self._ctx, _ptr(x), _ptr(b_in), B, ih, iw, oh, ow, Cin, _ptr(w_image), Cout,
+                                                  _ptr(b2) if tail else None, _ptr(w3) if tail else None, float(b3), float(scale), _ptr(out)))
+        return out
+
     def depth_to_space_bias(self, y, B: int, H: int, W: int, s: int, bias=None):
         """The scatter of a kernel == stride ConvTranspose2d run as a GEMM: contiguous float32 ``y`` [B*H*W, s*s*C] (columns in (i, j, c) order) ->
         channels_last [B, C, H*s, W*s] with out[b, c, y*s+i, x*s+j] = y[(b*H+y)*W+x, (i*s+j)*C+c] + bias[c] (include/vd3d.h vd3d_depth_to_space_bias_nhwc_f32)."""
