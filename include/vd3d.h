@@ -395,6 +395,32 @@ int vd3d_nhwc_f16_to_planar3_f32(vd3d_ctx* ctx, const void* t_nhwc32, int H, int
  * Replaces the reference's 8-bit depth video on disk while keeping its quantisation. */
 int vd3d_depth_handoff(vd3d_ctx* ctx, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint8_t* out_gray);
 
+/* ---- tiled high-resolution depth (core/render_depth.py:62-66,102-194: infer_depth_tile, _normalize_to_u8).  The inference-size frame is cut into
+ * `tile`-pixel tiles on a grid of core = max(1, tile - 2*pad), each cropped with a `pad` apron, resized so that both sides are multiples of 14, run
+ * through the network, and the tile centres are blended under a Hann window; the hand-off is a 1 % - 99 % percentile normalisation.  All three
+ * enqueue on the context's stream and do not synchronise; the tables are DEVICE arrays (visiondepth3d_amd/depth_tiles.py builds them).
+ *
+ * vd3d_tile_gather_cubic_u8: n apron crops of ONE size ch x cw -> out_tiles [n][chs][cws][3], each tile = cv2.resize(crop, (cws, chs), INTER_CUBIC)
+ * bit for bit in vd3d_resize_cubic_u8's arithmetic (a copy when the sizes agree).  frames_bgr: B uint8 BGR frames of H x W, rows pitch_bytes and
+ * frames frame_stride_bytes apart; origins_dev [n][3] int32 = (frame, y, x) of each crop (clamped into the batch by the kernel).  n <= 65535. */
+int vd3d_tile_gather_cubic_u8(vd3d_ctx* ctx, const uint8_t* frames_bgr, long long pitch_bytes, long long frame_stride_bytes, int B, int H, int W,
+                              const int32_t* origins_dev, int n, int ch, int cw, int chs, int cws, uint8_t* out_tiles);
+/* vd3d_tile_blend_f32: out [B][tgt_h][tgt_w] = sum(centre * w) / max(sum(w), 1e-8) over the tiles that cover a pixel, added in row-major tile
+ * order from 0 with separate multiply / add roundings (the reference's accumulation, bit for bit; no atomics).  Tile (ty, tx) of the
+ * ceil(tgt_h / core) x ceil(tgt_w / core) grid has the entry tile_tab_dev[(ty * ntx + tx) * 8 ..] = {yc0, xc0, chs, cws, ph, pw, w_off, 0} (int32,
+ * 16-byte aligned): its prediction for frame b is the float32 plane [ph][pw] at pred_pool + pred_off_dev[b * nt + t]; the centre sample of output
+ * pixel (y, x) is element (yc0 + y - y0, xc0 + x - x0) of the chs x cws prediction -- read as is when (ph, pw) == (chs, cws), otherwise evaluated
+ * with vd3d_depth_handoff's bicubic (align_corners=False) from the [ph][pw] plane; its weight is w_pool[w_off + (y - y0) * (x1 - x0) + (x - x0)].
+ * Built for at most 4 covering tiles per axis (pad <= 3/8 tile): anything beyond returns VD3D_E_UNSUPPORTED and launches nothing. */
+int vd3d_tile_blend_f32(vd3d_ctx* ctx, const float* pred_pool, const int64_t* pred_off_dev, const int32_t* tile_tab_dev, const float* w_pool,
+                        int B, int tgt_h, int tgt_w, int tile, int pad, float* out);
+/* vd3d_depth_normalize_pclip_u8: _normalize_to_u8 without its final resize, per frame of planes [B][H][W] float32 -> out_gray [B][H][W] uint8:
+ * non-finite samples count as 0; lo / hi = numpy.percentile(d, p_lo / p_hi) (method "linear" on float32, exact order statistics by radix select);
+ * hi - lo < 1e-6 -> min-max normalisation, or 128 everywhere when the range is below 1e-6 too; else clip((d - lo) / (hi - lo), 0, 1); * 255,
+ * truncation, optional 255 - u8.  lo_hi_dev_or_null: [B][2] float32 device array that receives lo, hi (they never visit the host). */
+int vd3d_depth_normalize_pclip_u8(vd3d_ctx* ctx, const float* planes, int B, int H, int W, float p_lo, float p_hi, int invert, uint8_t* out_gray,
+                                  float* lo_hi_dev_or_null);
+
 /* element type of the depth network's activations (a25).  The reference loads its Hugging Face depth models with
  * AutoModelForDepthEstimation.from_pretrained(checkpoint) and no dtype, i.e. float32 (core/render_depth.py:758-759,823-824):
  * VD3D_DT_F32 is the like-for-like precision, VD3D_DT_BF16 the optional reduced-precision mode. */

@@ -53,6 +53,7 @@ struct vd3d_ctx {
   uint8_t *L = nullptr, *R = nullptr, *gL = nullptr, *gR = nullptr;
   uint8_t* gLR = nullptr; size_t gLR_cap = 0;   // [H][2W][3] sharpened eyes side by side (E1 in front of a fit it does not take)
   uint32_t* mm = nullptr; int mm_cap = 0;
+  uint32_t* pclip_ws = nullptr; int pclip_cap = 0;    // vd3d_depth_normalize_pclip_u8: [frames][VD_PCLIP_WS_WORDS] radix-select histograms
   uint32_t* rowflag = nullptr; int rowflag_cap = 0;   // k_autocrop: one flag per source row
   uint8_t* blank_eye = nullptr; size_t blank_cap = 0; // skip_blank_frames: the side-masked source frame (source size)
   // vd3d_render_params::aten_sum_threads > 0: piece plan of the two torch.mean sums (vd3d_atensum.hip) for the current eye size / thread count, and the
@@ -255,7 +256,7 @@ VD3D_EXPORT int vd3d_ctx_destroy(vd3d_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   prof_collect(c);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  void* ptrs[] = {c->work, c->histA, c->rgb_eye, c->tdf, c->dn[0], c->dn[1], c->D, c->S, c->e2L, c->e2R, c->E2, c->bL, c->bR, c->L, c->R, c->gL, c->gR, c->gLR, c->mm, c->dc, c->rowflag, c->etab, c->crop_tab, c->blank_eye, c->fmt_eyes, c->aten_plan, c->aten_scratch, c->pm_rgb, c->pm_dd};
+  void* ptrs[] = {c->work, c->histA, c->rgb_eye, c->tdf, c->dn[0], c->dn[1], c->D, c->S, c->e2L, c->e2R, c->E2, c->bL, c->bR, c->L, c->R, c->gL, c->gR, c->gLR, c->mm, c->dc, c->rowflag, c->etab, c->crop_tab, c->blank_eye, c->fmt_eyes, c->aten_plan, c->aten_scratch, c->pm_rgb, c->pm_dd, c->pclip_ws};
   for (const auto& e : c->aten_cache) { (void)hipFree(e.plan); (void)hipFree(e.scratch); }
   for (auto& t : c->w2_tabs) (void)hipFree(t.dev);
   for (auto& t : c->wk_tabs) (void)hipFree(t.dev);
@@ -1429,6 +1430,69 @@ VD3D_EXPORT int vd3d_depth_handoff(vd3d_ctx* c, const float* pred, int B, int ph
   if (B > c->mm_cap) { HIPCHK(re_alloc(&c->mm, (size_t)3 * B)); c->mm_cap = B; }
   StageTimer t(c, "handoff");
   vd_launch_depth_handoff(c->stream, pred, B, ph, pw, H, W, invert ? 1 : 0, c->mm, out_gray);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// tiled high-resolution depth (vd3d_tiles.hip): infer_depth_tile's crops and blend, _normalize_to_u8 (core/render_depth.py:102-194)
+VD3D_EXPORT int vd3d_tile_gather_cubic_u8(vd3d_ctx* c, const uint8_t* frames_bgr, long long pitch_bytes, long long frame_stride_bytes, int B, int H, int W,
+                                          const int32_t* origins_dev, int n, int ch, int cw, int chs, int cws, uint8_t* out_tiles) {
+  if (!c || !frames_bgr || !origins_dev || !out_tiles || B < 1 || H < 1 || W < 1 || n < 1 || ch < 1 || cw < 1 || chs < 1 || cws < 1)
+    return set_err(VD3D_E_INVALID, "bad argument");
+  if (ch > H || cw > W || pitch_bytes < 3ll * W || (B > 1 && frame_stride_bytes < pitch_bytes * H))
+    return set_err(VD3D_E_INVALID, "tile_gather: crop %dx%d of a %dx%d frame, pitch %lld, frame stride %lld", cw, ch, W, H, pitch_bytes, frame_stride_bytes);
+  if ((long long)n * chs * cws * 3 >= (1ll << 31)) return set_err(VD3D_E_INVALID, "tile batch too large");
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "tile_gather");
+  if (!vd_launch_tile_gather(c->stream, frames_bgr, pitch_bytes, frame_stride_bytes, B, H, W, origins_dev, n, ch, cw, chs, cws, out_tiles))
+    return set_err(VD3D_E_UNSUPPORTED, "tile_gather: %d tiles in one launch (<= 65535)", n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_tile_blend_f32(vd3d_ctx* c, const float* pred_pool, const int64_t* pred_off_dev, const int32_t* tile_tab_dev, const float* w_pool,
+                                    int B, int tgt_h, int tgt_w, int tile, int pad, float* out) {
+  if (!c || !pred_pool || !pred_off_dev || !tile_tab_dev || !w_pool || !out || B < 1 || B > 65535 || tgt_h < 1 || tgt_w < 1 || tile < 1 || pad < 0)
+    return set_err(VD3D_E_INVALID, "bad argument");
+  if ((reinterpret_cast<uintptr_t>(tile_tab_dev) & 15) != 0) return set_err(VD3D_E_INVALID, "tile_blend: the tile table must be 16-byte aligned");
+  if ((long long)tgt_h * tgt_w >= (1ll << 31)) return set_err(VD3D_E_INVALID, "plane too large");
+  const int core = tile - 2 * pad > 1 ? tile - 2 * pad : 1;
+  if ((tile + core - 1) / core > 4)
+    return set_err(VD3D_E_UNSUPPORTED, "tile_blend: tile %d with pad %d puts %d tiles over a pixel per axis (built for <= 4: pad <= 3/8 tile)", tile, pad,
+                   (tile + core - 1) / core);
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "tile_blend");
+  vd_launch_tile_blend(c->stream, pred_pool, reinterpret_cast<const long long*>(pred_off_dev), tile_tab_dev, w_pool, B, tgt_h, tgt_w, tile, core, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_depth_normalize_pclip_u8(vd3d_ctx* c, const float* planes, int B, int H, int W, float p_lo, float p_hi, int invert, uint8_t* out_gray,
+                                              float* lo_hi_dev_or_null) {
+  if (!c || !planes || !out_gray || B < 1 || B > 65535 || H < 1 || W < 1 || !(p_lo >= 0.f && p_lo <= p_hi && p_hi <= 100.f))
+    return set_err(VD3D_E_INVALID, "bad argument");
+  const long long n = (long long)H * W;
+  if (n >= (1ll << 31)) return set_err(VD3D_E_INVALID, "plane too large");
+  HIPCHK(hipSetDevice(c->device));
+  if (B > c->pclip_cap) { HIPCHK(re_alloc(&c->pclip_ws, (size_t)B * VD_PCLIP_WS_WORDS)); c->pclip_cap = B; }
+  // numpy.percentile, method "linear", on a float32 array: q = float32(p) / float32(100), virtual index = (n - 1) * q in float32, its floor and
+  // the index after it, gamma = the fraction; at or beyond the last index both neighbours are the last element
+  uint32_t rank[VD_PCLIP_NR];
+  float g[2];
+  const float pc[2] = {p_lo, p_hi};
+  const float last = (float)(n - 1);
+  for (int k = 0; k < 2; ++k) {
+    const float q = pc[k] / 100.0f;
+    const float vi = last * q;
+    uint32_t k0, k1;
+    if (vi >= last) { k0 = k1 = (uint32_t)(n - 1); g[k] = 0.f; }
+    else { const float fl = floorf(vi); k0 = (uint32_t)fl; k1 = k0 + 1; g[k] = vi - fl; }
+    if (k1 > (uint32_t)(n - 1)) k1 = (uint32_t)(n - 1);
+    rank[1 + 2 * k] = k0; rank[2 + 2 * k] = k1;
+  }
+  rank[0] = 0; rank[5] = (uint32_t)(n - 1);
+  StageTimer t(c, "pclip_u8");
+  vd_launch_pclip_u8(c->stream, planes, B, n, rank, g[0], g[1], invert ? 1 : 0, c->pclip_ws, out_gray, lo_hi_dev_or_null);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -10,36 +10,10 @@
 // Arithmetic = oracle/vd3d_oracle.c:vo_depth_handoff (float32, fixed association, no contraction).
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
+#include "vd3d_cubic.h"   // cubic_coeffs / bicubic_at (shared with the tile blend)
 
 struct vd_handoff_args { int B, ph, pw, H, W, invert, same; float sh, sw; };
 
-VD_DEV float cubic1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-VD_DEV float cubic2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
-VD_DEV void cubic_coeffs(float t, float c[4]) {
-  const float A = -0.75f;
-  c[0] = cubic2(t + 1.f, A); c[1] = cubic1(t, A); c[2] = cubic1(1.f - t, A); c[3] = cubic2((1.f - t) + 1.f, A);
-}
-VD_DEV float bicubic_at(const float* __restrict__ p, const vd_handoff_args& a, const float cy[4], int iy, int x) {
-  const float rx = vd_fma(a.sw, (float)x + 0.5f, -0.5f);   // fused source index, like the bilinear taps (vd3d_dev.h)
-  const float fx = floorf(rx);
-  const int ix = (int)fx;
-  float cx[4];
-  cubic_coeffs(rx - fx, cx);
-  int xs[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { int xx = ix - 1 + j; xs[j] = xx < 0 ? 0 : (xx > a.pw - 1 ? a.pw - 1 : xx); }
-  float acc = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int yy = iy - 1 + i; yy = yy < 0 ? 0 : (yy > a.ph - 1 ? a.ph - 1 : yy);
-    const float* row = p + (size_t)yy * a.pw;
-    float r = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r += row[xs[j]] * cx[j];
-    acc += r * cy[i];
-  }
-  return acc;
-}
 VD_DEV uint32_t f2key(float v) { uint32_t b = __float_as_uint(v); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 VD_DEV float key2f(uint32_t k) { uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; return __uint_as_float(b); }
 
@@ -71,7 +45,7 @@ __global__ __launch_bounds__(256) void k_handoff(const float* __restrict__ pred,
       float cy[4];
       cubic_coeffs(ry - fy, cy);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) if (xq + q < a.W) v[q] = bicubic_at(p, a, cy, (int)fy, xq + q);
+      for (int q = 0; q < 4; ++q) if (xq + q < a.W) v[q] = bicubic_at(p, a.ph, a.pw, a.sw, cy, (int)fy, xq + q);
     }
   }
   if (!WRITE) {

@@ -270,6 +270,16 @@ bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const floa
 void vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,
                              uint8_t* out);
 
+// ---- vd3d_tiles.hip: tiled high-resolution depth (gather of apron crops, Hann blend of tile centres, percentile-clip normalisation)
+#define VD_PCLIP_NR 6                              // order statistics per frame: min, two around each percentile, max
+#define VD_PCLIP_WS_WORDS (4 * VD_PCLIP_NR * 256)  // uint32 words of histogram per frame: [digit pass][rank][256]
+bool vd_launch_tile_gather(hipStream_t s, const uint8_t* frames, long long pitch, long long fstride, int B, int H, int W, const int32_t* origins,
+                           int n, int ch, int cw, int chs, int cws, uint8_t* out);
+void vd_launch_tile_blend(hipStream_t s, const float* pool, const long long* pred_off, const int32_t* tab, const float* wpool, int B, int H, int W,
+                          int tile, int core, float* out);
+void vd_launch_pclip_u8(hipStream_t s, const float* planes, int B, long long n, const uint32_t rank[VD_PCLIP_NR], float g_lo, float g_hi, int invert,
+                        uint32_t* ws, uint8_t* out, float* lohi);
+
 // ---- vd3d_finish.hip
 bool vd_launch_finish_fused(hipStream_t s, const uint8_t* L, const uint8_t* R, const float* dn, int eh, int ew,
                             const vd3d_render_params& p, const vd_finish_consts& fc, const vd_dev_work* w, float focal,

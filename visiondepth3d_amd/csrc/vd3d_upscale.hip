@@ -12,64 +12,18 @@
 // All four are HBM-bound byte kernels: one thread per output pixel (resize: 16 taps out of L2) or per 4 bytes.
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
+#include "vd3d_cubic.h"
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
-// ---- OpenCV INTER_CUBIC, 8-bit ------------------------------------------------------------------------------------------
-struct rc_axis { int o[4]; int c[4]; };
-
-// coordinate map + coefficients of ONE output index along an axis of source length n (replicate border by index clamping)
-VD_DEV rc_axis rc_axis_make(int d, double scale, int n) {
-  rc_axis r;
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  const int s = (int)floorf(f);
-  f -= (float)s;
-  const float A = -0.75f;
-  float w[4];
-  w[0] = ((A * (f + 1.f) - 5.f * A) * (f + 1.f) + 8.f * A) * (f + 1.f) - 4.f * A;
-  w[1] = ((A + 2.f) * f - (A + 3.f)) * f * f + 1.f;
-  w[2] = ((A + 2.f) * (1.f - f) - (A + 3.f)) * (1.f - f) * (1.f - f) + 1.f;
-  w[3] = 1.f - w[0] - w[1] - w[2];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int i = s - 1 + k;
-    r.o[k] = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-    float v = rintf(w[k] * 2048.f);                       // saturate_cast<short>(cvRound(.))
-    r.c[k] = (int)fminf(fmaxf(v, -32768.f), 32767.f);
-  }
-  return r;
-}
-
+// ---- OpenCV INTER_CUBIC, 8-bit: rc_axis_make / rc_cubic_pixel live in vd3d_cubic.h (shared with the tile gather)
 template <int CN>
 __global__ __launch_bounds__(256) void k_resize_cubic_u8(const uint8_t* __restrict__ src, int sh, int sw, uint8_t* __restrict__ dst,
                                                          int dh, int dw, double scale_x, double scale_y) {
   const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (x >= dw || y >= dh) return;
   const rc_axis ax = rc_axis_make(x, scale_x, sw), ay = rc_axis_make(y, scale_y, sh);
-  int acc[CN];
-#pragma unroll
-  for (int c = 0; c < CN; ++c) acc[c] = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const uint8_t* row = src + (size_t)ay.o[k] * sw * CN;
-    int h[CN];
-#pragma unroll
-    for (int c = 0; c < CN; ++c) h[c] = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const uint8_t* p = row + (size_t)ax.o[j] * CN;
-#pragma unroll
-      for (int c = 0; c < CN; ++c) h[c] += (int)p[c] * ax.c[j];
-    }
-#pragma unroll
-    for (int c = 0; c < CN; ++c) acc[c] += h[c] * ay.c[k];
-  }
-  uint8_t* o = dst + ((size_t)y * dw + x) * CN;
-#pragma unroll
-  for (int c = 0; c < CN; ++c) {
-    const int v = (acc[c] + (1 << 21)) >> 22;
-    o[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-  }
+  rc_cubic_pixel<CN>(src, (size_t)sw * CN, ax, ay, dst + ((size_t)y * dw + x) * CN);
 }
 
 bool vd_launch_resize_cubic_u8(hipStream_t s, const uint8_t* src, int sh, int sw, int cn, uint8_t* dst, int dh, int dw) {

@@ -178,7 +178,9 @@ CONV_X3_MIN_TILES = 200
 
 class DepthPipe:
     """``pipe(images, inference_size=None) -> [{"predicted_depth": Tensor[h, w]}]`` (reference protocol) plus a
-    device-resident batch path."""
+    device-resident batch path.  OPT-IN tiled high-resolution depth (the reference's USE_TILED_DEPTH tiler, with a renderer):
+    ``infer_tiled_bgr_u8`` (batched equal-shape tiles, Hann blend on the device), ``depth_frames_u8(tiled=True)`` (percentile
+    hand-off) and ``call_tiled`` (reference protocol); the defaults are unchanged."""
 
     def __init__(self, name: str = "depth-anything-v2-small", device="cuda", dtype=torch.float32, seed: int = 0,
                  channels_last: bool = True, renderer=None, fuse_backbone: bool = True, model=None, processor: dict | None = None,
@@ -823,12 +825,20 @@ class DepthPipe:
         return pred
 
     @torch.no_grad()
-    def depth_frames_u8(self, frames_bgr: torch.Tensor, inference_size=None, invert: bool = False) -> torch.Tensor:
+    def depth_frames_u8(self, frames_bgr: torch.Tensor, inference_size=None, invert: bool = False, tiled: bool = False, tile: int = 512,
+                        pad: int = 32, tile_batch: int = 16) -> torch.Tensor:
         """The depth tab's per-frame product (core/render_depth.py:1907-1917) for uint8 [B,H,W,3] BGR frames: the prediction at the size
         the pipeline saw (the frame, or ``inference_size`` = (W', H')) -> ``convert_depth_to_grayscale`` -> optional ``255 -`` ->
-        ``cv2.resize(..., (W, H), INTER_CUBIC)``.  Returns uint8 [B,H,W] on the device (what the reference writes to its depth video)."""
+        ``cv2.resize(..., (W, H), INTER_CUBIC)``.  Returns uint8 [B,H,W] on the device (what the reference writes to its depth video).
+        ``tiled=True`` (OPT-IN, needs a renderer): the reference's USE_TILED_DEPTH product instead -- ``infer_tiled_bgr_u8`` (``tile`` /
+        ``pad`` / ``tile_batch``) -> ``_normalize_to_u8``'s 1 % - 99 % percentile normalisation (:173-194, ``Renderer.depth_normalize_pclip``) -> the same
+        INTER_CUBIC resize to the frame size."""
         B, H, W, _ = frames_bgr.shape
-        u8 = depth_to_u8(self.infer_bgr_u8(frames_bgr, inference_size, at_inference_size=True), invert)
+        if tiled:
+            d = self.infer_tiled_bgr_u8(frames_bgr, inference_size, tile=tile, pad=pad, tile_batch=tile_batch)
+            u8 = self.renderer.depth_normalize_pclip(d, invert)
+        else:
+            u8 = depth_to_u8(self.infer_bgr_u8(frames_bgr, inference_size, at_inference_size=True), invert)
         if tuple(u8.shape[-2:]) == (H, W):
             return u8
         if self.renderer is None:
@@ -837,6 +847,83 @@ class DepthPipe:
         for b in range(B):
             self.renderer.resize_cubic_u8(u8[b], H, W, out=out[b])
         return out
+
+    def _frames_to_inference_size(self, frames: torch.Tensor, tgt_h: int, tgt_w: int) -> torch.Tensor:
+        """infer_depth_tile's first step (core/render_depth.py:111-113): INTER_AREA when a side shrinks, INTER_CUBIC otherwise (a copy at
+        equal size).  One side shrinking while the other grows is not built."""
+        B, H, W, _ = frames.shape
+        if (tgt_h, tgt_w) == (H, W):
+            return frames
+        shrink, grow = tgt_w < W or tgt_h < H, tgt_w > W or tgt_h > H
+        if shrink and grow:
+            raise NotImplementedError(f"tiled depth: inference size {tgt_w}x{tgt_h} shrinks one side of the {W}x{H} frame and grows the other "
+                                      "(INTER_AREA with an up-scaled side) -- this mixed case is not built")
+        R = self.renderer
+        return torch.stack([R.resize_area_u8(frames[b], tgt_h, tgt_w) if shrink else R.resize_cubic_u8(frames[b], tgt_h, tgt_w) for b in range(B)])
+
+    @torch.no_grad()
+    def infer_tiled_bgr_u8(self, frames_bgr: torch.Tensor, inference_size=None, tile: int = 512, pad: int = 32, tile_batch: int = 16,
+                           model_call=None) -> torch.Tensor:
+        """The reference's tiler (infer_depth_tile, core/render_depth.py:102-170) for uint8 [B,H,W,3] BGR frames, on the device: frames to
+        ``inference_size`` = (W', H') (default: the frame size) -> apron crops of every tile, resized to multiples of 14
+        (``Renderer.tile_gather_cubic_u8``, one launch per crop shape across the B frames) -> the network on batches of at most
+        ``tile_batch`` equal-shape tiles (``infer_bgr_u8(tiles, raw=True)``; the reference runs one tile per forward) -> Hann blend of the
+        tile centres (``Renderer.tile_blend``, which also evaluates the pipeline's bicubic post-process of every tile).  Returns float32
+        [B,H',W'].  The blend keeps the reference's quirks: pixels only one tile covers (first row / column) carry a degenerate weight and a huge
+        value, which the percentile hand-off (``depth_frames_u8(tiled=True)``) clips.
+        ``model_call``: a callable uint8 [n,chs,cws,3] BGR tiles -> float32 [n,ph,pw] predictions (one (ph, pw) per tile shape) that
+        replaces the network."""
+        if self.renderer is None:
+            raise RuntimeError("infer_tiled_bgr_u8 needs DepthPipe(renderer=...): the tile gather and blend are HIP kernels")
+        from .depth_tiles import tile_plan
+        R = self.renderer
+        f = frames_bgr.to(self.device)
+        if f.dim() == 3:
+            f = f[None]
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+            raise TypeError("infer_tiled_bgr_u8 takes uint8 [B,H,W,3] BGR frames")
+        B, H, W, _ = f.shape
+        tgt_w, tgt_h = (W, H) if inference_size is None else (int(inference_size[0]), int(inference_size[1]))
+        img = self._frames_to_inference_size(f, tgt_h, tgt_w)
+        plan = tile_plan(tgt_h, tgt_w, int(tile), int(pad), 14)
+        cache = self.__dict__.setdefault("_tile_tables", {})
+        key = (plan, B)
+        if key not in cache:   # static per geometry: uploaded once
+            cache[key] = dict(origins=[torch.from_numpy(plan.gather_origins(g, B)).to(self.device) for g in plan.groups],
+                              w_pool=torch.from_numpy(plan.weight_pool()).to(self.device), blend={})
+        tabs = cache[key]
+        call = model_call if model_call is not None else (lambda t: self.infer_bgr_u8(t, raw=True))
+        step = max(1, int(tile_batch))
+        preds, shapes = [], []
+        for g, org in zip(plan.groups, tabs["origins"]):
+            tiles = R.tile_gather_cubic_u8(img, org, g.ch, g.cw, g.chs, g.cws)
+            shape = None
+            for i in range(0, tiles.shape[0], step):
+                p = call(tiles[i:i + step])
+                if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.shape[0] != min(step, tiles.shape[0] - i) or (shape or tuple(p.shape[1:])) != tuple(p.shape[1:]):
+                    raise ValueError("tiled depth: the model call returns a float32 [n,ph,pw] tensor, one (ph, pw) per tile shape")
+                shape = tuple(p.shape[1:])
+                preds.append(p.to(self.device, torch.float32).reshape(-1))
+            shapes.append(shape)
+        bkey = tuple(shapes)
+        if bkey not in tabs["blend"]:
+            tab, off, total = plan.blend_tables(B, shapes)
+            tabs["blend"][bkey] = (torch.from_numpy(tab).to(self.device), torch.from_numpy(off).to(self.device), total)
+        tab, off, total = tabs["blend"][bkey]
+        pool = torch.cat(preds)
+        assert pool.numel() == total
+        return R.tile_blend(pool, off, tab, tabs["w_pool"], B, tgt_h, tgt_w, int(tile), int(pad))
+
+    def call_tiled(self, images, inference_size=None, tile: int = 512, pad: int = 32):
+        """The USE_TILED_DEPTH branch of _run_pipe_or_tile (core/render_depth.py:242-250) behind the reference protocol: list of PIL images (or
+        HxWx3 uint8 RGB arrays) -> list of ``{"predicted_depth": float32 [H', W']}`` at the inference size (the frame size by default)."""
+        single = not isinstance(images, (list, tuple))
+        outs = []
+        for im in ([images] if single else list(images)):
+            a = np.asarray(im.convert("RGB") if hasattr(im, "convert") else im)
+            bgr = torch.from_numpy(np.ascontiguousarray(a[..., ::-1]))[None]
+            outs.append({"predicted_depth": self.infer_tiled_bgr_u8(bgr, inference_size, tile=tile, pad=pad)[0]})
+        return outs
 
     def __call__(self, images, inference_size=None):
         """Reference protocol: list of PIL images (or HxWx3 uint8 RGB arrays) -> list of dicts; ``predicted_depth`` has the size

@@ -344,6 +344,62 @@ class Renderer:
         _lib.check(self._L.vd3d_depth_handoff(self._ctx, _ptr(p), B, ph, pw, int(H), int(W), int(bool(invert)), _ptr(out)))
         return out
 
+    # ---- tiled high-resolution depth (core/render_depth.py:102-194; tables from visiondepth3d_amd.depth_tiles) ----
+    def tile_gather_cubic_u8(self, frames_bgr: torch.Tensor, origins: torch.Tensor, ch: int, cw: int, chs: int, cws: int,
+                             out: torch.Tensor | None = None) -> torch.Tensor:
+        """Apron crops of one shape group -> uint8 [n,chs,cws,3], each ``cv2.resize(crop, (cws, chs), INTER_CUBIC)`` (a copy at equal size).
+        ``frames_bgr``: uint8 [B,H,W,3] (or [H,W,3]) on the device, pixels contiguous, any row / frame pitch; ``origins``: int32 device
+        tensor [n,3] = (frame, y, x) of every ``ch x cw`` crop."""
+        f = frames_bgr if frames_bgr.dim() == 4 else frames_bgr[None]
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3 or f.device != self.device:
+            raise AssertionError("tile_gather_cubic_u8 takes uint8 [B,H,W,3] frames on the renderer's device")
+        if f.stride(3) != 1 or f.stride(2) != 3:
+            f = f.contiguous()
+        o = origins.to(self.device, torch.int32).contiguous()
+        if o.dim() != 2 or o.shape[1] != 3:
+            raise AssertionError("tile_gather_cubic_u8: origins is int32 [n,3] = (frame, y, x)")
+        B, H, W, _ = f.shape
+        n = int(o.shape[0])
+        if out is None:
+            out = torch.empty((n, int(chs), int(cws), 3), dtype=torch.uint8, device=self.device)
+        self._enter(f, o, out)
+        _lib.check(self._L.vd3d_tile_gather_cubic_u8(self._ctx, _ptr(f), int(f.stride(1)), int(f.stride(0)), B, H, W, _ptr(o), n,
+                                                     int(ch), int(cw), int(chs), int(cws), _ptr(out)))
+        return out
+
+    def tile_blend(self, pred_pool: torch.Tensor, pred_off: torch.Tensor, tile_tab: torch.Tensor, w_pool: torch.Tensor, n_frames: int,
+                   tgt_h: int, tgt_w: int, tile: int, pad: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Hann blend of the tile centres of ``n_frames`` frames in one launch -> float32 [n_frames,tgt_h,tgt_w] (vd3d_tile_blend_f32:
+        the reference's accumulation order, no atomics).  ``pred_pool`` float32 1-D, ``pred_off`` int64 [n_frames * n_tiles],
+        ``tile_tab`` int32 [n_tiles,8], ``w_pool`` float32 1-D: TilePlan.blend_tables / weight_pool on the device."""
+        for t, dt in ((pred_pool, torch.float32), (pred_off, torch.int64), (tile_tab, torch.int32), (w_pool, torch.float32)):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise AssertionError("tile_blend: float32 pools, int64 offsets, int32 tile table, contiguous, on the renderer's device")
+        if out is None:
+            out = torch.empty((int(n_frames), int(tgt_h), int(tgt_w)), dtype=torch.float32, device=self.device)
+        self._enter(pred_pool, pred_off, tile_tab, w_pool, out)
+        _lib.check(self._L.vd3d_tile_blend_f32(self._ctx, _ptr(pred_pool), _ptr(pred_off), _ptr(tile_tab), _ptr(w_pool), int(n_frames),
+                                               int(tgt_h), int(tgt_w), int(tile), int(pad), _ptr(out)))
+        return out
+
+    def depth_normalize_pclip(self, planes: torch.Tensor, invert: bool = False, pclip=(1.0, 99.0), out: torch.Tensor | None = None,
+                              lo_hi: torch.Tensor | None = None) -> torch.Tensor:
+        """_normalize_to_u8 (core/render_depth.py:173-193) per frame, without its final resize: float32 [B,H,W] -> uint8 [B,H,W] (numpy's
+        percentiles by exact radix select, clip, truncation, optional ``255 -``).  ``lo_hi``: optional float32 [B,2] device tensor that
+        receives the two percentiles."""
+        p = planes.to(self.device, torch.float32).contiguous()
+        if p.dim() == 2:
+            p = p[None]
+        B, H, W = p.shape
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        if lo_hi is not None and (lo_hi.dtype != torch.float32 or lo_hi.numel() < 2 * B or not lo_hi.is_contiguous() or lo_hi.device != self.device):
+            raise AssertionError("depth_normalize_pclip: lo_hi is a contiguous float32 [B,2] tensor on the renderer's device")
+        self._enter(p, out)
+        _lib.check(self._L.vd3d_depth_normalize_pclip_u8(self._ctx, _ptr(p), B, H, W, float(pclip[0]), float(pclip[1]), int(bool(invert)),
+                                                         _ptr(out), None if lo_hi is None else _ptr(lo_hi)))
+        return out
+
     # ---- optional NV12 wire format at the frame I/O boundary (SURVEY 8(f)1) ----
     def nv12_to_bgr(self, nv12: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """uint8 [h*3/2, w] NV12 frame (h rows of Y, then h/2 rows of interleaved UV: what ``-pix_fmt nv12`` rawvideo carries) ->
