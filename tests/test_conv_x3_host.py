@@ -1,4 +1,4 @@
-"""Host-side tests (no GPU) of the bf16x3 3 x 3 convolution (vd3d_conv3x3_x3, csrc/vd3d_conv3.hip) and of DepthPipe(conv="bf16x3"): the shape rule of the
+"""Host-side tests (no GPU) of the bf16x3 3 x 3 convolution (vd3d_conv3x3_x3, csrc/vd3d_conv_x3.hip) and of DepthPipe(conv="bf16x3"): the shape rule of the
 host-only weight-bytes call, the constructor's argument checks, and the kernel's register / LDS census from hipcc's own metadata."""
 import glob
 import os
@@ -58,25 +58,27 @@ def _census(src):
     finally:
         shutil.rmtree(d, ignore_errors=True)
     out = {}
-    for m in re.finditer(r"\.group_segment_fixed_size: (\d+).*?\.name:\s+(\S+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count: (\d+)", asm, re.S):
-        out[m.group(2)] = dict(lds=int(m.group(1)), vgpr=int(m.group(3)), spill=int(m.group(4)))
+    for m in re.finditer(r"\.group_segment_fixed_size: (\d+).*?\.name:\s+(\S+).*?\.sgpr_spill_count: (\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count: (\d+)", asm, re.S):
+        out[m.group(2)] = dict(lds=int(m.group(1)), sgpr_spill=int(m.group(3)), vgpr=int(m.group(4)), spill=int(m.group(5)))
     return out, asm
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_conv3x3_x3_census():
-    """512-thread workgroups, two waves per SIMD: at most 256 registers, none spilled; no static LDS in front of the dynamic array (or a multiple of 16: the
-    fragments are ds_read_b128); bf16 MFMAs only; the launcher's dynamic LDS request within what a workgroup can have."""
-    k, asm = _census("vd3d_conv3.hip")
-    convs = {n: v for n, v in k.items() if n.startswith("_Z12k_conv3x3_x3ILi")}
-    assert len(convs) == 3, sorted(k)   # 32, 64 and 128 output channels per workgroup (256 runs as two 128-channel halves)
+    """512-thread workgroups, two waves per SIMD: at most 256 registers, none spilled (vector or scalar); no static LDS in front of the dynamic array (or a
+    multiple of 16: the fragments are ds_read_b128); bf16 MFMAs only; the launcher's dynamic LDS request within what a workgroup can have."""
+    k, asm = _census("vd3d_conv_x3.hip")
+    convs = {n: v for n, v in k.items() if n.startswith("_Z9k_conv_x3ILi")}
+    plain = {n: v for n, v in convs.items() if re.match(r"_Z9k_conv_x3ILi0ELi\dELi\dELb0E", n)}   # K3S1 without epilogue options: this entry point's
+    assert len(plain) == 3, sorted(k)   # 32, 64 and 128 output channels per workgroup (256 runs as two 128-channel halves)
+    assert sum(n.startswith("_Z9k_conv_x3ILi0ELi4ELi2ELb0E") for n in plain) == 1 and len(convs) == 12, sorted(k)
     for n, c in convs.items():
-        assert c["spill"] == 0 and c["vgpr"] <= 256 and c["lds"] % 16 == 0, (n, c)
+        assert c["spill"] == 0 and c["sgpr_spill"] == 0 and c["vgpr"] <= 256 and c["lds"] % 16 == 0, (n, c)
     assert "v_mfma_f32_32x32x16_bf16" in asm and "v_mfma_f32_32x32x2_f32" not in asm
     assert "scratch_" not in asm
-    src = open(os.path.join(CSRC, "vd3d_conv3.hip")).read()
-    lds_max = int(re.search(r"#define C3_LDS_MAX (\d+)", src).group(1))
-    assert "static_assert(c3_lds(128, 4) == C3_LDS_MAX" in src   # the constant is tied to the launcher's own formula at compile time
+    src = open(os.path.join(CSRC, "vd3d_conv_x3.hip")).read()
+    lds_max = int(re.search(r"#define CX_LDS_MAX (\d+)", src).group(1))
+    assert "static_assert(cx_lds(128) == CX_LDS_MAX" in src   # the constant is tied to the launcher's own formula at compile time
     assert 0 < lds_max <= 163840
     # the same plan, from the layout constants: two A images, the float32 staging buffer, the four-stage ring of the 128-channel kernel
     a_img, stg, ring = 3 * 2 * (10 * 34) * 16, 3 * 512 * 16, 4 * 16384

@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the bf16x3 3 x 3 convolution (vd3d_conv3x3_x3, csrc/vd3d_conv3.hip) and of the depth leg that runs on it
+"""GPU tests (-m gpu) of the bf16x3 3 x 3 convolution (vd3d_conv3x3_x3, csrc/vd3d_conv_x3.hip) and of the depth leg that runs on it
 (DepthPipe(gemm="bf16x3", conv="bf16x3")).
 
 A floating-point kernel: the bar is stated against FLOAT64, beside PyTorch's float32 CPU convolution on the same operands (the yardstick of

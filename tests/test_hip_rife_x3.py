@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the interpolation network on this library's kernels: the bf16x3 convolution family vd3d_conv_ifn (csrc/vd3d_conv_ifn.hip: 3 x 3 stride 1,
+"""GPU tests (-m gpu) of the interpolation network on this library's kernels: the bf16x3 convolution family vd3d_conv_ifn (csrc/vd3d_conv_x3.hip: 3 x 3 stride 1,
 3 x 3 stride 2, transposed 4 x 4 stride 2; bias / PReLU / residual epilogue), the three glue kernels, and RifeSession(conv="bf16x3") end to end.
 
 Floating-point kernels: every bar is stated against FLOAT64, beside PyTorch's float32 CPU op on the same operands -- the yardstick and the bars of

@@ -1,5 +1,5 @@
 """CPU-only checks of RifeSession(conv="bf16x3"): the weight rewrites (channel padding, merged heads, the transposed convolution as four phases) and the whole
-operation list against torch in float64, the new entry points in the header and the export list, the register / LDS budget of csrc/vd3d_conv_ifn.hip from
+operation list against torch in float64, the new entry points in the header and the export list, the register / LDS budget of csrc/vd3d_conv_x3.hip from
 hipcc's own metadata, and the construction rules (no GPU, no renderer: ValueError, never a fall-back)."""
 import importlib.util
 import os
@@ -121,7 +121,7 @@ def test_header_declares_and_exports_list_the_new_entry_points():
     assert (_abi.IFN_K3S1, _abi.IFN_K3S2, _abi.IFN_T4S2) == (0, 1, 2)
     assert re.search(r"VD3D_IFN_K3S1 = 0, VD3D_IFN_K3S2 = 1, VD3D_IFN_T4S2 = 2", hdr)
     mk = open(os.path.join(ROOT, "visiondepth3d_amd", "csrc", "Makefile")).read()
-    assert "vd3d_conv_ifn.hip" in mk
+    assert "vd3d_conv_ifn.hip" in mk and "vd3d_conv_x3.hip" in mk
 
 
 def test_weight_bytes_query_names_the_built_shapes():
@@ -139,21 +139,24 @@ def test_weight_bytes_query_names_the_built_shapes():
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_conv_ifn_kernels_fit_their_register_and_lds_budget():
     """Nine instantiations (three geometries x C_out 32 / 64 / 96) of 512-thread workgroups: two waves per SIMD, so at most 256 registers, nothing spilled; no
-    static LDS in front of the dynamic array (a multiple of 16 keeps ds_read_b128 aligned); the launcher's largest dynamic-LDS request is CF_LDS_MAX <= 163 840,
-    tied to the plan by the file's static_assert.  No kernel of the file spills."""
-    k = _census("vd3d_conv_ifn.hip")
-    convs = {n: v for n, v in k.items() if n.startswith("_Z13k_conv_ifn_x3ILi")}
+    static LDS in front of the dynamic array (a multiple of 16 keeps ds_read_b128 aligned); the launcher's largest dynamic-LDS request is CX_LDS_MAX <= 163 840,
+    tied to the plan by the file's static_assert.  No kernel of the file spills.  (The other three instantiations are the DPT convolution's, without epilogue
+    options: tests/test_conv_x3_host.py.)"""
+    k = _census("vd3d_conv_x3.hip")
+    convs = {n: v for n, v in k.items() if re.match(r"_Z9k_conv_x3ILi[012]ELi(8ELi1|4ELi1|8ELi3)ELb1E", n)}
     assert len(convs) == 9, sorted(k)
+    assert len([n for n in k if n.startswith("_Z9k_conv_x3ILi")]) == 12, sorted(k)
     for n, v in convs.items():
         assert v["spill"] == 0 and v["vgpr"] <= 256 and v["lds"] % 16 == 0 and v["lds"] + 155392 <= 163840, (n, v)
     for n, v in k.items():
         assert v["spill"] == 0, (n, v)
-    src = open(os.path.join(ROOT, "visiondepth3d_amd", "csrc", "vd3d_conv_ifn.hip")).read()
-    m = re.search(r"#define CF_LDS_MAX (\d+)", src)
+    src = open(os.path.join(ROOT, "visiondepth3d_amd", "csrc", "vd3d_conv_x3.hip")).read()
+    m = re.search(r"#define CX_LDS_MAX (\d+)", src)
     assert m and int(m.group(1)) == 155392 and int(m.group(1)) <= 163840
-    assert "static_assert(cf_lds(96) == CF_LDS_MAX && cf_lds(64) <= CF_LDS_MAX && cf_lds(32) <= CF_LDS_MAX && CF_LDS_MAX <= 163840" in src
+    assert "static_assert(cx_lds(128) == CX_LDS_MAX && cx_lds(96) == CX_LDS_MAX && cx_lds(64) <= CX_LDS_MAX && cx_lds(32) <= CX_LDS_MAX && CX_LDS_MAX <= 163840" in src
     assert 2 * (3 * 2 * 340 * 16) + 3 * 512 * 16 + 4 * 16384 == 155392            # the plan of the header comment: two chunk images, staging, four ring stages
-    assert set(re.findall(r"cf_lds\((\d+)\), s, a\)", src)) == {"32", "64", "96"}      # every launch requests its plan's size
+    # every launch requests its plan's size (128: the DPT convolution's widest workgroup, launched from the same file)
+    assert set(re.findall(r"cx_lds\((\d+)\), s, a\)", src)) == {"32", "64", "96", "128"}
 
 
 def test_construction_rules():

@@ -2,7 +2,8 @@
 4, 2, 1, 0.5; the head at 8 x and at the input size): device-event time beside the float32 library convolution (MIOpen find mode on -- what gemm="bf16x3" uses
 today) and vd3d_conv3x3_x2 where that builds; then the whole forward with conv=None and conv="bf16x3" alternating in one process.
 
-  python tools/probe_conv_x3.py [--shapes [--cout N]] [--forward] [--out FILE.md]     (both parts when neither is named)"""
+  python tools/probe_conv_x3.py [--shapes [--cout N] [--x3-only]] [--forward] [--out FILE.md]     (both parts when neither is named)
+--x3-only times vd3d_conv3x3_x3 alone (no MIOpen find per shape: seconds instead of minutes), for A/B runs of two builds of the library through VD3D_LIB_PATH."""
 import argparse
 import os
 import statistics
@@ -46,7 +47,7 @@ def shape_list():
     return out
 
 
-def probe_shapes(R, say, only_cout=0):
+def probe_shapes(R, say, only_cout=0, x3_only=False):
     torch.backends.cudnn.benchmark = True
     g = torch.Generator(device="cuda").manual_seed(1)
     say("| model, layer | B x H x W x C_in -> C_out | 8 x 32 tiles | conv3x3_x3 ms | library f32 ms | x3 / library | conv3x3_x2 ms | bf16 MFMA TFLOP/s (6 products), of peak |")
@@ -59,12 +60,12 @@ def probe_shapes(R, say, only_cout=0):
         img = R.conv3x3_x3_pack(w)
         n = 5 if B * H * W * Cin * Cout > 4e11 else 10
         t3 = bench(lambda: R.conv3x3_x3(x, img, Cout), n)
-        t32 = bench(lambda: F.conv2d(x, w, None, 1, 1), n)
-        img2 = R.conv3x3_x2_pack(w)
+        t32 = float("nan") if x3_only else bench(lambda: F.conv2d(x, w, None, 1, 1), n)
+        img2 = None if x3_only else R.conv3x3_x2_pack(w)
         t2 = bench(lambda: R.conv3x3_x2(x, img2, Cout), n) if img2 is not None else None
         fl = 6 * 2.0 * B * H * W * Cin * 9 * Cout / (t3 * 1e-3)
         tiles = B * ((H + 7) // 8) * ((W + 31) // 32)
-        say(f"| {model} {where} | {B} x {H} x {W} x {Cin} -> {Cout} | {tiles} | {t3:.3f} | {t32:.3f} | {t3 / t32:.2f} | {'--' if t2 is None else f'{t2:.3f}'} | "
+        say(f"| {model} {where} | {B} x {H} x {W} x {Cin} -> {Cout} | {tiles} | {t3:.3f} | {'--' if x3_only else f'{t32:.3f}'} | {'--' if x3_only else f'{t3 / t32:.2f}'} | {'--' if t2 is None else f'{t2:.3f}'} | "
             f"{fl / 1e12:.0f}, {100 * fl / PEAK_BF16:.1f} % |")
         del x, w, img, img2
 
@@ -96,6 +97,7 @@ def main():
     ap.add_argument("--shapes", action="store_true")
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--cout", type=int, default=0, help="only the shapes with this many output channels")
+    ap.add_argument("--x3-only", action="store_true", help="with --shapes: time vd3d_conv3x3_x3 only")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     lines = []
@@ -108,7 +110,7 @@ def main():
                 f.write("\n".join(lines) + "\n")
     R = Renderer(0)
     if a.shapes or not a.forward:
-        probe_shapes(R, say, a.cout)
+        probe_shapes(R, say, a.cout, a.x3_only)
     if a.forward or not a.shapes:
         probe_forward(R, say)
     R.close()

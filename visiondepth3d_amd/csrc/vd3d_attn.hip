@@ -26,12 +26,9 @@
 // per workgroup it would be 16: the reason for the 8-wave workgroup).
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
+#include "vd3d_x3.h"
 
 #include <mutex>
-
-typedef short at_bf8 __attribute__((ext_vector_type(8)));
-typedef float at_f16 __attribute__((ext_vector_type(16)));
-typedef uint32_t at_u4 __attribute__((ext_vector_type(4)));
 
 #define AT_D 64
 #define AT_BQ 256
@@ -54,43 +51,6 @@ struct vd_at_args {
   int nq32, nkv, nqb;        // 32-query blocks, 64-row KV tiles, 256-query workgroups per (b, h)
   float c;                   // scale * log2(e)
 };
-
-VD_DEV void at_split(float a, uint32_t& t1, uint32_t& t2, uint32_t& t3) {
-  t1 = __float_as_uint(a) & 0xffff0000u;
-  const float r1 = a - __uint_as_float(t1);
-  t2 = __float_as_uint(r1) & 0xffff0000u;
-  const float r2 = r1 - __uint_as_float(t2);
-  t3 = __float_as_uint(r2);
-}
-VD_DEV uint32_t at_pack(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-VD_DEV void at_split8(const float v[8], at_bf8 out[3]) {
-  uint32_t t1[8], t2[8], t3[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) at_split(v[e], t1[e], t2[e], t3[e]);
-  const at_u4 p1 = {at_pack(t1[0], t1[1]), at_pack(t1[2], t1[3]), at_pack(t1[4], t1[5]), at_pack(t1[6], t1[7])};
-  const at_u4 p2 = {at_pack(t2[0], t2[1]), at_pack(t2[2], t2[3]), at_pack(t2[4], t2[5]), at_pack(t2[6], t2[7])};
-  const at_u4 p3 = {at_pack(t3[0], t3[1]), at_pack(t3[2], t3[3]), at_pack(t3[4], t3[5]), at_pack(t3[6], t3[7])};
-  out[0] = __builtin_bit_cast(at_bf8, p1); out[1] = __builtin_bit_cast(at_bf8, p2); out[2] = __builtin_bit_cast(at_bf8, p3);
-}
-typedef _Float16 at_h8 __attribute__((ext_vector_type(8)));
-VD_DEV void at_split8_h(const float v[8], float pre, at_bf8 out[2]) {   // h1 = fp16(x pre), h2 = fp16(x pre - h1), round to nearest
-  at_h8 h1, h2;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float x = v[e] * pre;
-    const _Float16 a1 = (_Float16)x;
-    h1[e] = a1;
-    h2[e] = (_Float16)(x - (float)a1);
-  }
-  out[0] = __builtin_bit_cast(at_bf8, h1); out[1] = __builtin_bit_cast(at_bf8, h2);
-}
-template <int MODE> VD_DEV void at_split8_m(const float v[8], float pre, at_bf8* out) {
-  if (MODE == 0) at_split8(v, out); else at_split8_h(v, pre, out);
-}
-template <int MODE> VD_DEV at_f16 at_mfma(const at_bf8& a, const at_bf8& b, const at_f16& c) {
-  if (MODE == 0) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(at_h8, a), __builtin_bit_cast(at_h8, b), c, 0, 0, 0);
-}
 
 // ---- prep: one thread = 8 consecutive elements of one fragment chunk.  which 0 / 1 (Q, K): 8 consecutive d of one token; which 2 (V^T): the 8 kv slots
 // of one (k-step, k-half) at one d.
@@ -118,8 +78,8 @@ __global__ __launch_bounds__(256) void k_attn_x3_prep(const float* __restrict__ 
     const int ks = c >> 1, kh = c & 1;
     if (which == 0) dst = Qimg + ((size_t)bh * a.nq32 + (t >> 5)) * AT_QBLK(MODE) + (size_t)((ks * NTERM) * 2 + kh) * 32 + (t & 31);
     else dst = Kimg + ((size_t)bh * a.nkv + (t >> 6)) * (AT_TILE(MODE) / 16) + (size_t)((ks * NTERM) * 2 + kh) * 64 + (t & 63);
-    at_bf8 o[NTERM];
-    at_split8_m<MODE>(v, AT_QKV_SCALE, o);
+    x3_s8 o[NTERM];
+    x3_split8_m<MODE>(v, AT_QKV_SCALE, o);
     const int ts = which == 0 ? 2 * 32 : 2 * 64;   // term stride in uint4
 #pragma unroll
     for (int t3 = 0; t3 < NTERM; ++t3) dst[(size_t)t3 * ts] = __builtin_bit_cast(uint4, o[t3]);
@@ -133,21 +93,18 @@ __global__ __launch_bounds__(256) void k_attn_x3_prep(const float* __restrict__ 
       const int kv = tile * 64 + 32 * m + (e & 3) + 8 * (2 * j + (e >> 2)) + 4 * kh;
       v[e] = kv < a.T ? qkv[((size_t)b * a.T + kv) * tok_stride + (size_t)2 * a.H * AT_D + h * AT_D + d] : 0.f;
     }
-    at_bf8 o[NTERM];
-    at_split8_m<MODE>(v, AT_QKV_SCALE, o);
+    x3_s8 o[NTERM];
+    x3_split8_m<MODE>(v, AT_QKV_SCALE, o);
     dst = Vimg + ((size_t)bh * a.nkv + tile) * (AT_TILE(MODE) / 16) + (size_t)((ks * NTERM) * 2 + kh) * 64 + d;
 #pragma unroll
     for (int t3 = 0; t3 < NTERM; ++t3) dst[(size_t)t3 * 128] = __builtin_bit_cast(uint4, o[t3]);
   }
 }
 
-typedef __attribute__((address_space(3))) void* at_lds_vp;
-typedef const __attribute__((address_space(1))) void* at_glb_vp;
-
 // six products (small first: x3 w1, x2 w2, x1 w3, x2 w1, x1 w2, x1 w1) into TWO accumulators that share the B operand, alternating: dependent MFMAs 64 cycles apart
 #define AT_MM1(ACC0, AF0, ACC1, AF1, BF, ta, tb)                                               \
-  ACC0 = at_mfma<MODE>(AF0[ta], BF[tb], ACC0);                                                 \
-  ACC1 = at_mfma<MODE>(AF1[ta], BF[tb], ACC1);
+  ACC0 = x3_mfma<MODE>(AF0[ta], BF[tb], ACC0);                                                 \
+  ACC1 = x3_mfma<MODE>(AF1[ta], BF[tb], ACC1);
 #define AT_MM6(ACC0, AF0, ACC1, AF1, BF)                                                       \
   if (MODE == 0) { AT_MM1(ACC0, AF0, ACC1, AF1, BF, NTERM - 1, 0) AT_MM1(ACC0, AF0, ACC1, AF1, BF, 1, 1) AT_MM1(ACC0, AF0, ACC1, AF1, BF, 0, NTERM - 1) }                               \
   AT_MM1(ACC0, AF0, ACC1, AF1, BF, 1, 0) AT_MM1(ACC0, AF0, ACC1, AF1, BF, 0, 1) AT_MM1(ACC0, AF0, ACC1, AF1, BF, 0, 0)
@@ -173,14 +130,14 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
 
   // Q fragments of the wave's 32 queries (zero rows past T: the image is padded to whole 32-query blocks; a wave past the last block reads block nq32 - 1 and
   // stores nothing)
-  at_bf8 qf[4][NTERM];
+  x3_s8 qf[4][NTERM];
   {
     const int blk = min(q0 >> 5, a.nq32 - 1);
     const uint4* qp = Qimg + ((size_t)bh * a.nq32 + blk) * AT_QBLK(MODE) + kh * 32 + li;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-      for (int t = 0; t < NTERM; ++t) qf[ks][t] = __builtin_bit_cast(at_bf8, qp[(ks * NTERM + t) * 64]);
+      for (int t = 0; t < NTERM; ++t) qf[ks][t] = __builtin_bit_cast(x3_s8, qp[(ks * NTERM + t) * 64]);
   }
   const uint4* kimg = Kimg + (size_t)bh * a.nkv * (TILE / 16) + tid;
   const uint4* vimg = Vimg + (size_t)bh * a.nkv * (TILE / 16) + tid;
@@ -190,10 +147,10 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
     if (pp >= NP) return;
     const uint4* src = (op == 0 ? kimg : vimg) + (size_t)tile * (TILE / 16) + pp * AT_NT;
     uint8_t* dst = at_lds + buf * STAGE + op * TILE + pp * (AT_NT * 16) + wave_base;
-    __builtin_amdgcn_global_load_lds((at_glb_vp)src, (at_lds_vp)dst, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((x3_glb_vp)src, (x3_lds_vp)dst, 16, 0, 0);
   };
 
-  at_f16 oacc[2];
+  x3_f16 oacc[2];
 #pragma unroll
   for (int dm = 0; dm < 2; ++dm)
 #pragma unroll
@@ -222,12 +179,12 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
 
   const int frag_off = (kh * 64 + li) * 16;     // + ((ks * 3 + t) * 2) * 1024 + m * 512
   // one k-step (16 of the 64 head dimensions) of S^T for both 32-row M tiles: 6 fragment reads, 12 MFMAs
-  auto st_step = [&](const uint8_t* sk, int ks, at_f16 (&sa)[2]) {
-    at_bf8 kf[2][NTERM];
+  auto st_step = [&](const uint8_t* sk, int ks, x3_f16 (&sa)[2]) {
+    x3_s8 kf[2][NTERM];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int t = 0; t < NTERM; ++t) kf[m][t] = *reinterpret_cast<const at_bf8*>(sk + frag_off + ((ks * NTERM + t) * 2) * 1024 + m * 512);
+      for (int t = 0; t < NTERM; ++t) kf[m][t] = *reinterpret_cast<const x3_s8*>(sk + frag_off + ((ks * NTERM + t) * 2) * 1024 + m * 512);
     AT_MM6(sa[0], kf[0], sa[1], kf[1], qf[ks])
   };
   // hint for one pinned chunk: 12 x (one MFMA = 32 cycles of the SIMD's matrix pipe, then up to n VALU), the fragment reads first
@@ -239,7 +196,7 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
   }                                                                \
   __builtin_amdgcn_sched_barrier(0);
 
-  at_f16 sacc[2];
+  x3_f16 sacc[2];
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -269,7 +226,7 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
           if (it * AT_BK + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh >= a.T) z[m][r] = -INFINITY;
     }
     // ---- region A: S^T (it + 1) on the matrix pipe || softmax (it) on the VALU, in four pinned chunks of 12 MFMAs
-    at_f16 sn[2];
+    x3_f16 sn[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -308,19 +265,19 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
     for (int dm = 0; dm < 2; ++dm)
 #pragma unroll
       for (int r = 0; r < 16; ++r) oacc[dm][r] *= alpha;
-    at_bf8 pf[2][NTERM];
-    at_split8_m<MODE>(&z[0][0], AT_P_SCALE, pf[0]);
+    x3_s8 pf[2][NTERM];
+    x3_split8_m<MODE>(&z[0][0], AT_P_SCALE, pf[0]);
     AT_CHUNK_HINT(7)
     // ---- region B: O^T += V^T P^T (tile it); the split of k-step ks + 1 rides on the MFMAs of k-step ks
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       if (ks < 2) { dma(tile_c(it + 2), s2, 4 + ks); __builtin_amdgcn_sched_barrier(0); }
-      if (ks < 3) at_split8_m<MODE>(&z[(ks + 1) >> 1][8 * ((ks + 1) & 1)], AT_P_SCALE, pf[(ks + 1) & 1]);
-      at_bf8 vf[2][NTERM];
+      if (ks < 3) x3_split8_m<MODE>(&z[(ks + 1) >> 1][8 * ((ks + 1) & 1)], AT_P_SCALE, pf[(ks + 1) & 1]);
+      x3_s8 vf[2][NTERM];
 #pragma unroll
       for (int dm = 0; dm < 2; ++dm)
 #pragma unroll
-        for (int t = 0; t < NTERM; ++t) vf[dm][t] = *reinterpret_cast<const at_bf8*>(sv + frag_off + ((ks * NTERM + t) * 2) * 1024 + dm * 512);
+        for (int t = 0; t < NTERM; ++t) vf[dm][t] = *reinterpret_cast<const x3_s8*>(sv + frag_off + ((ks * NTERM + t) * 2) * 1024 + dm * 512);
       AT_MM6(oacc[0], vf[0], oacc[1], vf[1], pf[ks & 1])
       AT_CHUNK_HINT(4)
     }
@@ -381,7 +338,7 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
 // (one scope per product, kept when the compiler pairs reads), and the compiler's wait-count pass then does not put a conservative vmcnt(0) behind every
 // LDS-DMA in front of them -- the ring is ordered by the kernel's own counted waits and barriers.
 // S^T[m] = K Q^T for the 32-row M tiles m = 0, 1 (q pre-scaled); K row r at sk + 256 r, 16-byte chunk c at position c ^ (r & 15)
-VD_DEV void af_st(const uint8_t* __restrict__ sk, const float (&qf)[32], int li, int kh, at_f16 (&s)[2]) {
+VD_DEV void af_st(const uint8_t* __restrict__ sk, const float (&qf)[32], int li, int kh, x3_f16 (&s)[2]) {
   const int kswz = (li & 15) << 4;
 #pragma unroll
   for (int m = 0; m < 2; ++m)
@@ -403,7 +360,7 @@ VD_DEV void af_st(const uint8_t* __restrict__ sk, const float (&qf)[32], int li,
   }
 }
 // O^T[dm] += V^T P^T: register r of M tile m is the K = 2 step of kv 32 m + (r & 3) + 8 (r >> 2) + 4 kh; V row kv at sv + 256 kv (linear), d = 2 li + dm
-VD_DEV void af_pv(const uint8_t* __restrict__ sv, const at_f16 (&p)[2], int li, int kh, at_f16 (&oacc)[2]) {
+VD_DEV void af_pv(const uint8_t* __restrict__ sv, const x3_f16 (&p)[2], int li, int kh, x3_f16 (&oacc)[2]) {
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
@@ -439,8 +396,8 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
     for (int p = 0; p < 2; ++p) {
       const int tok = min(tile * AT_BK + drow + 32 * p, a.T - 1);
       const float* src = base + (size_t)tok * tok_stride + a.H * AT_D;
-      __builtin_amdgcn_global_load_lds((at_glb_vp)(src + kchunk * 4), (at_lds_vp)(dst + p * 8192), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((at_glb_vp)(src + a.H * AT_D + dpos * 4), (at_lds_vp)(dst + AF_TILE + p * 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + kchunk * 4), (x3_lds_vp)(dst + p * 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + a.H * AT_D + dpos * 4), (x3_lds_vp)(dst + AF_TILE + p * 8192), 16, 0, 0);
     }
   };
 
@@ -463,7 +420,7 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
   }
   __builtin_amdgcn_s_barrier();
 
-  at_f16 oacc[2];
+  x3_f16 oacc[2];
 #pragma unroll
   for (int dm = 0; dm < 2; ++dm)
 #pragma unroll
@@ -476,7 +433,7 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
     const uint8_t* sk = at_lds + cur * AF_STAGE;
     const uint8_t* sv = sk + AF_TILE;
     // ---- S^T = K Q^T (pre-scaled logits)
-    at_f16 s[2];
+    x3_f16 s[2];
     af_st(sk, qf, li, kh, s);
     if ((it + 1) * AT_BK > a.T) {   // last tile: rows past T (a uniform branch off the hot path)
 #pragma unroll

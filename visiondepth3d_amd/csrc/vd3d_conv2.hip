@@ -13,16 +13,12 @@
 //     fragments from it -- a fragment = 32 consecutive pixels of a tile row shifted by the tap = consecutive 16-byte slots: conflict-free ds_read_b128,
 //     no swizzle.  That is what a GEMM-shaped kernel cannot have: it would fetch every input pixel nine times (a CU ingests ~12 bytes per cycle).
 //   B (weights): packed once per model into the K-step image [chunk][tap][term 2][k-half 2][oc][8 fp16] (8 KB per step for 128 output channels, padded to
-//     whole 8 KB DMA rounds) and streamed by LDS-DMA into a ring of four stages, three steps ahead, counted vmcnt + raw s_barrier (vd3d_gemm.hip).
+//     whole 8 KB DMA rounds) and streamed by LDS-DMA into a ring of four stages, three steps ahead, counted vmcnt + raw s_barrier (vd3d_gemm.hip; the derivation of the counts: vd3d_conv_x3.hip).
 //   Epilogue: acc * colscale[oc] (the power of two the channel's weights were scaled by, exact) -> float32 NHWC stores, 128 bytes per pixel and N tile.
 // Per K step and wave: 12 ds_read_b128 feed 4 x NWN x 3 MFMAs.
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
-
-typedef short c2_h8s __attribute__((ext_vector_type(8)));
-typedef _Float16 c2_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 c2_h4 __attribute__((ext_vector_type(4)));
-typedef float c2_f16 __attribute__((ext_vector_type(16)));
+#include "vd3d_x3.h"
 
 #define C2_TH 16
 #define C2_TW 32
@@ -44,9 +40,6 @@ struct vd_c2_args {
   int ntx, nty;          // tiles per frame
   int nchunk;            // Cin / 16
 };
-
-typedef __attribute__((address_space(3))) void* c2_lds_vp;
-typedef const __attribute__((address_space(1))) void* c2_glb_vp;
 
 template <int WM, int NWN>   // WM waves along M (4: four tile rows each, two waves along N; 8: two rows each, one along N), NWN N tiles per wave: C_out = 32 (8 / WM) NWN
 __global__ __launch_bounds__(C2_NT) void k_conv3x3_x2(const float* __restrict__ X, const uint4* __restrict__ Wimg, const float* __restrict__ colscale,
@@ -76,24 +69,22 @@ __global__ __launch_bounds__(C2_NT) void k_conv3x3_x2(const float* __restrict__ 
   auto load_a = [&](int chunk) {
 #pragma unroll
     for (int it = 0; it < C2_A_ITERS; ++it)
-      __builtin_amdgcn_global_load_lds((c2_glb_vp)(azero[it] ? ap[it] : ap[it] + chunk * 16),
-                                       (c2_lds_vp)(c2_lds + 2 * C2_A_BUF + it * (C2_NT * 16) + wave_base), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(azero[it] ? ap[it] : ap[it] + chunk * 16),
+                                       (x3_lds_vp)(c2_lds + 2 * C2_A_BUF + it * (C2_NT * 16) + wave_base), 16, 0, 0);
   };
   auto write_a = [&](int buf) {   // staging (float32) -> split (round to nearest) -> two 8-byte LDS stores per item
     uint8_t* dst = c2_lds + buf * C2_A_BUF;
     const uint8_t* stg = c2_lds + 2 * C2_A_BUF + tid * 16;
 #pragma unroll
     for (int it = 0; it < C2_A_ITERS; ++it) {
-      // read as a short vector and bit-cast: hipcc orders a float4 LDS read behind every LDS-DMA in flight (vmcnt(0)), not this type (vd3d_gemm.hip)
-      const c2_h8s raw = *reinterpret_cast<const c2_h8s*>(stg + it * (C2_NT * 16));
+      const x3_s8 raw = *reinterpret_cast<const x3_s8*>(stg + it * (C2_NT * 16));   // a short vector, bit-cast: not ordered behind the DMAs in flight (vd3d_x3.h)
       const float4 f = __builtin_bit_cast(float4, raw);
       const float v[4] = {f.x, f.y, f.z, f.w};
-      c2_h4 h1, h2;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { const _Float16 t = (_Float16)v[e]; h1[e] = t; h2[e] = (_Float16)(v[e] - (float)t); }
+      x3_h4 h1, h2;
+      x3_split4_h(v, h1, h2);
       if (adst[it] >= 0) {
-        *reinterpret_cast<c2_h4*>(dst + adst[it]) = h1;
-        *reinterpret_cast<c2_h4*>(dst + 2 * C2_NPIX * 16 + adst[it]) = h2;
+        *reinterpret_cast<x3_h4*>(dst + adst[it]) = h1;
+        *reinterpret_cast<x3_h4*>(dst + 2 * C2_NPIX * 16 + adst[it]) = h2;
       }
     }
   };
@@ -102,11 +93,11 @@ __global__ __launch_bounds__(C2_NT) void k_conv3x3_x2(const float* __restrict__ 
   auto stage_b = [&](int ks, int slot) {
 #pragma unroll
     for (int p = 0; p < NBP; ++p)
-      __builtin_amdgcn_global_load_lds((c2_glb_vp)(wb + (size_t)ks * (BST / 16) + p * C2_NT),
-                                       (c2_lds_vp)(c2_lds + C2_B_OFF + slot * BST + p * (C2_NT * 16) + wave_base), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(wb + (size_t)ks * (BST / 16) + p * C2_NT),
+                                       (x3_lds_vp)(c2_lds + C2_B_OFF + slot * BST + p * (C2_NT * 16) + wave_base), 16, 0, 0);
   };
 
-  c2_f16 acc[MR][NWN];
+  x3_f16 acc[MR][NWN];
 #pragma unroll
   for (int m = 0; m < MR; ++m)
 #pragma unroll
@@ -138,21 +129,21 @@ __global__ __launch_bounds__(C2_NT) void k_conv3x3_x2(const float* __restrict__ 
       stage_b(ks + 3 < KS ? ks + 3 : KS - 1, (ks + 3) & 3);   // behind the last step: a harmless re-fetch (straight-line code, one counted wait)
       const uint8_t* sb = c2_lds + slot * BST;
       const uint8_t* sat = sa + fa_base + (dy * C2_PW + dx) * 16;
-      c2_h8s bf[NWN][2];
+      x3_s8 bf[NWN][2];
 #pragma unroll
       for (int n = 0; n < NWN; ++n)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) bf[n][t] = *reinterpret_cast<const c2_h8s*>(sb + fb_base + t * (2 * COUT * 16) + n * 512);
+        for (int t = 0; t < 2; ++t) bf[n][t] = *reinterpret_cast<const x3_s8*>(sb + fb_base + t * (2 * COUT * 16) + n * 512);
 #pragma unroll
       for (int m = 0; m < MR; ++m) {
-        c2_h8s af[2];
+        x3_s8 af[2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) af[t] = *reinterpret_cast<const c2_h8s*>(sat + t * (2 * C2_NPIX * 16) + m * (C2_PW * 16));
+        for (int t = 0; t < 2; ++t) af[t] = *reinterpret_cast<const x3_s8*>(sat + t * (2 * C2_NPIX * 16) + m * (C2_PW * 16));
 #pragma unroll
         for (int n = 0; n < NWN; ++n) {   // small products first: x2 w1, x1 w2, x1 w1
-          acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(c2_h8, af[1]), __builtin_bit_cast(c2_h8, bf[n][0]), acc[m][n], 0, 0, 0);
-          acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(c2_h8, af[0]), __builtin_bit_cast(c2_h8, bf[n][1]), acc[m][n], 0, 0, 0);
-          acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(c2_h8, af[0]), __builtin_bit_cast(c2_h8, bf[n][0]), acc[m][n], 0, 0, 0);
+          acc[m][n] = x3_mfma<1>(af[1], bf[n][0], acc[m][n]);
+          acc[m][n] = x3_mfma<1>(af[0], bf[n][1], acc[m][n]);
+          acc[m][n] = x3_mfma<1>(af[0], bf[n][0], acc[m][n]);
         }
       }
       // Counted wait.  In flight, oldest first: [B (ks + 1)] [B (ks + 2)] [the next chunk's C2_A_ITERS DMAs, issued at tap 0] [B (ks + 3)].  The next step needs
@@ -210,7 +201,7 @@ __global__ __launch_bounds__(256) void k_conv3x3_x2_pack(const float* __restrict
   if (t >= total) return;
   const int oc = t % Cout, khf = (t / Cout) & 1, tap = (t / (2 * Cout)) % 9, chunk = t / (18 * Cout);
   const float sc = 1.0f / colscale[oc];
-  c2_h8 h1, h2;
+  x3_h8 h1, h2;   // x3_split8_h (vd3d_x3.h) by hand: through the helper hipcc orders this kernel's loads and converts differently
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int ic = chunk * 16 + khf * 8 + e;
@@ -220,8 +211,8 @@ __global__ __launch_bounds__(256) void k_conv3x3_x2_pack(const float* __restrict
   }
   const int bst = (2 * 2 * Cout * 16 + 8191) / 8192 * 8192;
   uint8_t* base = img + (size_t)(chunk * 9 + tap) * bst + (khf * Cout + oc) * 16;
-  *reinterpret_cast<c2_h8*>(base) = h1;
-  *reinterpret_cast<c2_h8*>(base + 2 * Cout * 16) = h2;
+  *reinterpret_cast<x3_h8*>(base) = h1;
+  *reinterpret_cast<x3_h8*>(base + 2 * Cout * 16) = h2;
 }
 
 static bool c2_shape_ok(int Cin, int Cout) { return Cin >= 16 && (Cin & 15) == 0 && (Cout == 32 || Cout == 64 || Cout == 128); }

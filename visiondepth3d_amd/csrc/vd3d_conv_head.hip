@@ -8,7 +8,7 @@
 // [oh][ow][C_OUT] -- existed only to be read once.  Arithmetic: float32 operands on v_mfma_f32_32x32x2_f32, float32 accumulation: k_attn_f32's class, not a
 // split-operand mode.  No split-K, no atomics: every output is summed by one lane in one fixed K order, identical from run to run.
 //
-// Implicit GEMM per workgroup: an 8 x 32 output tile (k_conv3x3_x3's geometry), 512 threads = 8 waves, wave w = tile row w.  Output channels are the MFMA's M
+// Implicit GEMM per workgroup: an 8 x 32 output tile (k_conv_x3's geometry, vd3d_conv_x3.hip), 512 threads = 8 waves, wave w = tile row w.  Output channels are the MFMA's M
 // side (A[i = lane & 31 = channel][k = lane >> 5]), the row's 32 pixels its N side (B[k = lane >> 5][j = lane & 31 = pixel]): a lane's 16 accumulator
 // registers are channels (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of ONE pixel, so the tail's dot product is an in-lane sum plus one exchange with lane ^ 32.
 // K order (fixed): 16-channel chunk (outer), tap 0 .. 8 (dy major), channel group g = 0, 1 of the chunk, j = 0 .. 3; one MFMA sums channels 8 g + j (k = 0)
@@ -26,8 +26,8 @@
 //   LDS (dynamic only): 2 x 24 832 + 2 x 24 576 = 98 816 (C_OUT 32), 2 x 24 832 + 2 x 40 960 = 131 584 (C_OUT 64; the weight buffers padded to whole 512-thread rounds): one workgroup, two waves per SIMD.
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
+#include "vd3d_x3.h"
 
-typedef float ch_f16 __attribute__((ext_vector_type(16)));
 typedef float ch_f4 __attribute__((ext_vector_type(4)));   // native vectors: the register images of the loads below stay SSA values (HIP's float4 arrays went to scratch)
 
 #define CH_TH 8
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(CH_NT) void k_conv3x3_up_f32(const float* __restric
     for (int p = 0; p < W_ITERS; ++p) *reinterpret_cast<ch_f4*>(ch_smem + 2 * CH_X_BUF + buf * WLDS + (p * CH_NT + tid) * 16) = wv[p];
   };
 
-  ch_f16 tot[NM];
+  x3_f16 tot[NM];
 #pragma unroll
   for (int m = 0; m < NM; ++m)
 #pragma unroll
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(CH_NT) void k_conv3x3_up_f32(const float* __restric
     // Blocked summation: a chunk's 72 K = 2 steps go into two fresh accumulators (j even / j odd), added to the running total behind the chunk.  One chain
     // over all of K measured 1.6 x the library path's RMS error against float64 (the rounding of a float32 fmaf chain grows with its length and with the
     // magnitude of its partial sums); chains of 36 steps whose sums meet in C_IN / 8 additions stay below it (tests/test_hip_dpt_head_f32.py).
-    ch_f16 acc[2][NM];
+    x3_f16 acc[2][NM];
 #pragma unroll
     for (int m = 0; m < NM; ++m)
 #pragma unroll

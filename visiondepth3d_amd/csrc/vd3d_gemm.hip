@@ -47,10 +47,8 @@
 // accumulator register = two 128-byte row segments per wave).
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
+#include "vd3d_x3.h"
 #include <cstdlib>
-
-typedef short gx_bf8 __attribute__((ext_vector_type(8)));     // 8 bf16 = one MFMA A / B fragment (4 VGPRs)
-typedef float gx_f16 __attribute__((ext_vector_type(16)));    // one 32 x 32 accumulator tile per wave
 
 #define GX_BM 256
 #define GX_BN 256
@@ -73,54 +71,14 @@ struct vd_gx_args {
   int has_bias;
 };
 
-// exact split of a float32 into bf16 terms by truncation: a == t1 + t2 + t3 (as floats whose low 16 bits are zero)
-VD_DEV void gx_split(float a, uint32_t& t1, uint32_t& t2, uint32_t& t3) {
-  t1 = __float_as_uint(a) & 0xffff0000u;
-  const float r1 = a - __uint_as_float(t1);
-  t2 = __float_as_uint(r1) & 0xffff0000u;
-  const float r2 = r1 - __uint_as_float(t2);
-  t3 = __float_as_uint(r2);   // <= 8 significant bits: its low half is zero
-}
-// pack the high halves of two words: lo | hi << 16
-VD_DEV uint32_t gx_pack(uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x07060302u); }
-// eight float32 (k = 8 kh .. 8 kh + 7 of one row) -> the three bf16 fragments of that lane
-VD_DEV void gx_split8(const float4& lo, const float4& hi, gx_bf8 out[3]) {
-  uint32_t t1[8], t2[8], t3[8];
-  gx_split(lo.x, t1[0], t2[0], t3[0]); gx_split(lo.y, t1[1], t2[1], t3[1]); gx_split(lo.z, t1[2], t2[2], t3[2]); gx_split(lo.w, t1[3], t2[3], t3[3]);
-  gx_split(hi.x, t1[4], t2[4], t3[4]); gx_split(hi.y, t1[5], t2[5], t3[5]); gx_split(hi.z, t1[6], t2[6], t3[6]); gx_split(hi.w, t1[7], t2[7], t3[7]);
-  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-  const u4 p1 = {gx_pack(t1[0], t1[1]), gx_pack(t1[2], t1[3]), gx_pack(t1[4], t1[5]), gx_pack(t1[6], t1[7])};
-  const u4 p2 = {gx_pack(t2[0], t2[1]), gx_pack(t2[2], t2[3]), gx_pack(t2[4], t2[5]), gx_pack(t2[6], t2[7])};
-  const u4 p3 = {gx_pack(t3[0], t3[1]), gx_pack(t3[2], t3[3]), gx_pack(t3[4], t3[5]), gx_pack(t3[6], t3[7])};
-  out[0] = __builtin_bit_cast(gx_bf8, p1); out[1] = __builtin_bit_cast(gx_bf8, p2); out[2] = __builtin_bit_cast(gx_bf8, p3);
-}
-
-// fp16x2: a ~ h1 + h2 with h1 = fp16(a), h2 = fp16(a - h1), both round-to-nearest: |a - h1 - h2| <= 2^-22 |a| while h2 stays a normal fp16 number (|a| >= 2^-2
-// for unscaled data; below that the absolute error is <= 2^-25).  |a| must stay below 65 504.
-typedef _Float16 gx_h8 __attribute__((ext_vector_type(8)));
-VD_DEV void gx_split8_h(const float4& lo, const float4& hi, gx_bf8 out[2]) {
+// the two 16-byte halves of a lane's eight k values, as they were read from LDS (short vectors: vd3d_x3.h) -> its NTERM fragments
+template <int MODE> VD_DEV void gx_split8_m(const x3_s8& lo8, const x3_s8& hi8, x3_s8* out) {
+  const float4 lo = __builtin_bit_cast(float4, lo8), hi = __builtin_bit_cast(float4, hi8);
   const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  gx_h8 h1, h2;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const _Float16 a1 = (_Float16)v[e];
-    h1[e] = a1;
-    h2[e] = (_Float16)(v[e] - (float)a1);
-  }
-  out[0] = __builtin_bit_cast(gx_bf8, h1); out[1] = __builtin_bit_cast(gx_bf8, h2);
-}
-template <int MODE> VD_DEV void gx_split8_m(const float4& lo, const float4& hi, gx_bf8* out) {
-  if (MODE == 0) gx_split8(lo, hi, out); else gx_split8_h(lo, hi, out);
-}
-template <int MODE> VD_DEV gx_f16 gx_mfma(const gx_bf8& a, const gx_bf8& b, const gx_f16& c) {
-  if (MODE == 0) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(gx_h8, a), __builtin_bit_cast(gx_h8, b), c, 0, 0, 0);
+  x3_split8_m<MODE>(v, out);
 }
 
 VD_DEV float gx_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-typedef __attribute__((address_space(3))) void* gx_lds_vp;
-typedef const __attribute__((address_space(1))) void* gx_glb_vp;
 
 // DBG (development ablations, VD3D_GEMM_DBG; results are wrong): 1 no DMA, 2 no barrier, 4 no MFMA, 8 no A split, 16 no stores, 32 no A DMA, 64 no B DMA, 128 no vmcnt wait, 256 three of the six products
 template <int DBG, int MODE>
@@ -163,14 +121,14 @@ __global__ __launch_bounds__(GX_NT) void k_gemm_bf16x3(const float* __restrict__
     uint8_t* dst = gx_lds + buf * STAGE;
 #pragma unroll
     for (int p = 0; p < 2; ++p)
-      __builtin_amdgcn_global_load_lds((gx_glb_vp)(xa[p] + ks * 16), (gx_lds_vp)(dst + p * (GX_NT * 16) + wave_base), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(xa[p] + ks * 16), (x3_lds_vp)(dst + p * (GX_NT * 16) + wave_base), 16, 0, 0);
     const uint4* src = wb + (size_t)ks * (STAGE_HALF / 16);
 #pragma unroll
     for (int p = 0; p < NB; ++p)
-      __builtin_amdgcn_global_load_lds((gx_glb_vp)(src + p * GX_NT), (gx_lds_vp)(dst + GX_A_STAGE + p * (GX_NT * 16) + wave_base), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + p * GX_NT), (x3_lds_vp)(dst + GX_A_STAGE + p * (GX_NT * 16) + wave_base), 16, 0, 0);
   };
 
-  gx_f16 acc[2][4];
+  x3_f16 acc[2][4];
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -184,16 +142,16 @@ __global__ __launch_bounds__(GX_NT) void k_gemm_bf16x3(const float* __restrict__
   const int fa_off0 = (a_row * 4 + ((2 * kh) ^ a_sw)) * 16, fa_off1 = (a_row * 4 + ((2 * kh + 1) ^ a_sw)) * 16;
   const int fb_off = GX_A_STAGE + (kh * GX_BN + wn * 128 + li) * 16;
 
-  auto load_split_a = [&](int buf, gx_bf8 (*af)[NTERM]) {
+  auto load_split_a = [&](int buf, x3_s8 (*af)[NTERM]) {
     const uint8_t* sa = gx_lds + buf * STAGE;
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
       // read as the fragment type (the LDS reads of this kernel all have ONE type: hipcc orders a float4 LDS read behind every LDS-DMA in flight
       // -- s_waitcnt vmcnt(0) at the top of each stage -- and leaves the short-vector reads alone)
-      const gx_bf8 lo8 = *reinterpret_cast<const gx_bf8*>(sa + fa_off0 + mi * 2048);
-      const gx_bf8 hi8 = *reinterpret_cast<const gx_bf8*>(sa + fa_off1 + mi * 2048);
+      const x3_s8 lo8 = *reinterpret_cast<const x3_s8*>(sa + fa_off0 + mi * 2048);
+      const x3_s8 hi8 = *reinterpret_cast<const x3_s8*>(sa + fa_off1 + mi * 2048);
       if (DBG & 8) { af[mi][0] = lo8; af[mi][1] = hi8; af[mi][NTERM - 1] = lo8; }
-      else gx_split8_m<MODE>(__builtin_bit_cast(float4, lo8), __builtin_bit_cast(float4, hi8), af[mi]);
+      else gx_split8_m<MODE>(lo8, hi8, af[mi]);
     }
   };
 
@@ -203,16 +161,16 @@ __global__ __launch_bounds__(GX_NT) void k_gemm_bf16x3(const float* __restrict__
   stage(a.KS > 2 ? 2 : a.KS - 1, 2);
   if (NDMA == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  gx_bf8 af[2][NTERM];
+  x3_s8 af[2][NTERM];
   load_split_a(0, af);
 
   // one DMA instruction of a stage: pieces 0, 1 = A, 2 .. (4 | 3) = B
   auto stage_piece = [&](int ks, int buf, int piece) {
     if (DBG & 1) return;
     uint8_t* dst = gx_lds + buf * STAGE;
-    if (piece < 2) { if (!(DBG & 32)) __builtin_amdgcn_global_load_lds((gx_glb_vp)(xa[piece] + ks * 16), (gx_lds_vp)(dst + piece * (GX_NT * 16) + wave_base), 16, 0, 0); }
-    else if (!(DBG & 64)) __builtin_amdgcn_global_load_lds((gx_glb_vp)(wb + (size_t)ks * (STAGE_HALF / 16) + (piece - 2) * GX_NT),
-                                          (gx_lds_vp)(dst + GX_A_STAGE + (piece - 2) * (GX_NT * 16) + wave_base), 16, 0, 0);
+    if (piece < 2) { if (!(DBG & 32)) __builtin_amdgcn_global_load_lds((x3_glb_vp)(xa[piece] + ks * 16), (x3_lds_vp)(dst + piece * (GX_NT * 16) + wave_base), 16, 0, 0); }
+    else if (!(DBG & 64)) __builtin_amdgcn_global_load_lds((x3_glb_vp)(wb + (size_t)ks * (STAGE_HALF / 16) + (piece - 2) * GX_NT),
+                                          (x3_lds_vp)(dst + GX_A_STAGE + (piece - 2) * (GX_NT * 16) + wave_base), 16, 0, 0);
   };
 
   int cur = 0;
@@ -228,31 +186,31 @@ __global__ __launch_bounds__(GX_NT) void k_gemm_bf16x3(const float* __restrict__
     const int nxt = (cur + 1) & 3, sk = ks + 3 < a.KS ? ks + 3 : a.KS - 1, sbuf = (cur + 3) & 3;
     const uint8_t* sb = gx_lds + cur * STAGE;
     const uint8_t* sa = gx_lds + nxt * STAGE;
-    gx_bf8 an[2][NTERM];
-    gx_bf8 raw[2][2];
+    x3_s8 an[2][NTERM];
+    x3_s8 raw[2][2];
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {   // read as the fragment type (see load_split_a)
-      raw[mi][0] = *reinterpret_cast<const gx_bf8*>(sa + fa_off0 + mi * 2048);
-      raw[mi][1] = *reinterpret_cast<const gx_bf8*>(sa + fa_off1 + mi * 2048);
+      raw[mi][0] = *reinterpret_cast<const x3_s8*>(sa + fa_off0 + mi * 2048);
+      raw[mi][1] = *reinterpret_cast<const x3_s8*>(sa + fa_off1 + mi * 2048);
     }
 #pragma unroll
     for (int nj = 0; nj < 4; ++nj) {
       stage_piece(sk, sbuf, nj);
       if (nj == 3 && NDMA == 5) stage_piece(sk, sbuf, 4);
       __builtin_amdgcn_sched_barrier(0);
-      gx_bf8 bf[NTERM];
+      x3_s8 bf[NTERM];
 #pragma unroll
-      for (int t = 0; t < NTERM; ++t) bf[t] = *reinterpret_cast<const gx_bf8*>(sb + fb_off + t * 8192 + nj * 512);
+      for (int t = 0; t < NTERM; ++t) bf[t] = *reinterpret_cast<const x3_s8*>(sb + fb_off + t * 8192 + nj * 512);
       if (nj == 0 || nj == 2) {   // the split of one M tile of the next stage rides on this group's MFMAs
         const int mi = nj >> 1;
         if (DBG & 8) { an[mi][0] = raw[mi][0]; an[mi][1] = raw[mi][1]; an[mi][NTERM - 1] = raw[mi][0]; }
-        else gx_split8_m<MODE>(__builtin_bit_cast(float4, raw[mi][0]), __builtin_bit_cast(float4, raw[mi][1]), an[mi]);
+        else gx_split8_m<MODE>(raw[mi][0], raw[mi][1], an[mi]);
       }
       // small products first; (ta, tb): x3 w1, x2 w2, x1 w3, x2 w1, x1 w2, x1 w1; the two M tiles alternate (dependent MFMAs 64 cycles apart)
 #define GX_MM(ta, tb)                                                                                    \
   if (DBG & 4) { acc[0][nj][0] += (float)af[0][ta][0] * (float)bf[tb][0]; acc[1][nj][0] += (float)af[1][ta][1] * (float)bf[tb][1]; } else {            \
-  acc[0][nj] = gx_mfma<MODE>(af[0][ta], bf[tb], acc[0][nj]);         \
-  acc[1][nj] = gx_mfma<MODE>(af[1][ta], bf[tb], acc[1][nj]); }
+  acc[0][nj] = x3_mfma<MODE>(af[0][ta], bf[tb], acc[0][nj]);         \
+  acc[1][nj] = x3_mfma<MODE>(af[1][ta], bf[tb], acc[1][nj]); }
       if (MODE == 0 && !(DBG & 256)) { GX_MM(NTERM - 1, 0) GX_MM(1, 1) GX_MM(0, NTERM - 1) }   // (NTERM - 1 = 2 here; written so that the fp16x2 instantiation compiles)
       GX_MM(1, 0) GX_MM(0, 1) GX_MM(0, 0)
 #undef GX_MM
@@ -330,8 +288,8 @@ __global__ __launch_bounds__(256) void k_gemm_x3_pack_w(const float* __restrict_
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = n < N ? W[(size_t)n * K + c * 8 + j] * sc : 0.f;
-  gx_bf8 o[NTERM];
-  gx_split8_m<MODE>(float4{v[0], v[1], v[2], v[3]}, float4{v[4], v[5], v[6], v[7]}, o);
+  x3_s8 o[NTERM];
+  x3_split8_m<MODE>(v, o);
   const int ntile = n / GX_BN, nl = n - ntile * GX_BN, ks = c >> 1, khf = c & 1;
   uint4* base = img + ((size_t)ntile * (K / 16) + ks) * (STAGE_HALF / 16) + khf * GX_BN + nl;
 #pragma unroll

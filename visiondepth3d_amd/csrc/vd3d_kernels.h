@@ -234,7 +234,7 @@ bool vd_launch_gemm_x3(hipStream_t s, const float* X, long long M, int K, const 
 long long vd_conv3x3_x2_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_x2_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
-// vd3d_conv3.hip: the same convolution in the bf16x3 arithmetic (three bf16 terms, six products), C_out 32 / 64 / 128 / 256
+// vd3d_conv_x3.hip: the same convolution in the bf16x3 arithmetic (three bf16 terms, six products), C_out 32 / 64 / 128 / 256
 long long vd_conv3x3_x3_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
@@ -244,8 +244,8 @@ bool vd_launch_dpt_head_conv_pack(hipStream_t s, const float* W, int Cin, int Co
 bool vd_dpt_head_conv_shape_ok(int B, int ih, int iw, int oh, int ow, int Cin, int Cout, bool tail);
 bool vd_launch_dpt_head_conv_f32(hipStream_t s, const float* x, const float* b_in, int B, int ih, int iw, int oh, int ow, int Cin, const void* wimg, int Cout,
                                  const float* b2, const float* w3, float b3, float scale, float* out);
-// vd3d_conv_ifn.hip: the convolutions of the RIFE interpolation network in the bf16x3 arithmetic (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
-// bias / PReLU / residual epilogue, channel slices of strided NHWC buffers) and the float32 glue between its blocks
+// vd3d_conv_x3.hip: the convolutions of the RIFE interpolation network on the same kernel (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
+// bias / PReLU / residual epilogue, channel slices of strided NHWC buffers); vd3d_conv_ifn.hip: the float32 glue between its blocks
 long long vd_conv_ifn_weight_bytes(int kind, int Cin, int Cout);
 bool vd_launch_conv_ifn_pack(hipStream_t s, int kind, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv_ifn(hipStream_t s, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* wimg, const float* bias,
