@@ -34,7 +34,8 @@ extern "C" {
  *    -DVD3D_DEV_KNOBS; aten_threads / aten_sum_threads accept 1 .. 1024.
  * 5 (round 5): vd3d_shift_params gained aten_threads / reserved0 at its end (vd3d_render_params embeds it: its later fields moved by 8 bytes); vd3d_torch_math_aten.
  * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
- * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32. */
+ * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32,
+ *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs. */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -420,6 +421,55 @@ int vd3d_tile_blend_f32(vd3d_ctx* ctx, const float* pred_pool, const int64_t* pr
  * truncation, optional 255 - u8.  lo_hi_dev_or_null: [B][2] float32 device array that receives lo, hi (they never visit the host). */
 int vd3d_depth_normalize_pclip_u8(vd3d_ctx* ctx, const float* planes, int B, int H, int W, float p_lo, float p_hi, int invert, uint8_t* out_gray,
                                   float* lo_hi_dev_or_null);
+
+/* ---- letterbox handling of the depth pass (core/render_depth.py:280-573: LetterboxTracker and the detectors it calls; :1919-1933: the bar fill
+ * behind the hand-off).  visiondepth3d_amd/letterbox.py holds the numpy statement these reproduce bit for bit (numpy's own arithmetic in numpy's
+ * pairwise summation order; the cv2 parts -- BGR2GRAY, BGR2HSV's S, Canny, calcHist / normalize / compareHist, INTER_CUBIC -- from OpenCV's
+ * documented 8-bit behaviour, unpinned).  Frames are dense uint8 BGR [B][H][W][3] in device memory, W <= 8192.  Everything enqueues on the
+ * context's stream.  Host synchronisation: vd3d_letterbox_state_export / _import always; any other call only the FIRST time a context meets a
+ * frame size or a larger batch (the summation plans of that size are built and uploaded with blocking copies and kept for the context's life -- none is evicted; lengths are at most 8192, a plan a few KB --,
+ * workspaces grow behind a stream synchronise) -- steady state, alternating sizes included, enqueues and returns.  One tracker state per context. */
+typedef struct vd3d_letterbox_state {   /* the reference tracker's attributes + what is_scene_cut compares the next frame with */
+  int32_t top, bottom;                  /* the bars in force */
+  int32_t locked_zero, locked_bars;
+  int32_t cand_top, cand_bottom, streak;
+  int32_t cooldown;                     /* frames left before a cut may re-measure */
+  int32_t have_prev, prev_h, prev_w;    /* a previous frame's gray plane and 64-bin histogram are kept in the context */
+  int32_t reserved;
+} vd3d_letterbox_state;
+typedef struct vd3d_letterbox_params {  /* LetterboxTracker.__init__ after its int() conversions */
+  int32_t min_change, confirm_needed;
+  int32_t max_total;                    /* int(h * max_total_frac) */
+  int32_t cooldown_frames;              /* int(fps * cooldown_sec) */
+} vd3d_letterbox_params;
+/* vd3d_letterbox_stats: one pass over the frames.  Per row: float32 luma mean and variance (numpy's pairwise order) and the integer sum of the HSV
+ * saturation (row_sat_sum [B][H] uint32; its mean is (float)sum / (float)W); the gray plane [B][H][W]; the 64-bin gray histogram [B][64] uint32;
+ * mad_sum [B] uint64 = sum |gray_t - gray_(t-1)|; frame_mean [B] = y.mean() of the float32 luma plane.  Frame 0 has no predecessor (mad_sum 0) unless
+ * chain != 0: then it is compared with the frame the tracker state keeps (when it has one of the same size), and the last frame of this batch
+ * takes that place afterwards. */
+int vd3d_letterbox_stats(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, int chain, float* row_mean, float* row_var,
+                         uint32_t* row_sat_sum, uint8_t* gray, uint32_t* hist64, uint64_t* mad_sum, float* frame_mean);
+/* vd3d_canny_u8: cv2.Canny(gray, low, high, apertureSize=3, L2gradient=True) per plane of gray [B][H][W] -> edges [B][H][W] (0 / 255);
+ * row_counts_or_null [B][H] int32 receives the number of edge pixels per row.  vd3d_canny_hysteresis_u8 is its second half on a given class map
+ * (0 none, 1 weak, 2 strong): 255 on every non-zero pixel that is 8-connected, through non-zero pixels, to a strong one. */
+int vd3d_canny_u8(vd3d_ctx* ctx, const uint8_t* gray, int B, int H, int W, int low, int high, uint8_t* edges, int32_t* row_counts_or_null);
+int vd3d_canny_hysteresis_u8(vd3d_ctx* ctx, const uint8_t* classes, int B, int H, int W, uint8_t* edges, int32_t* row_counts_or_null);
+/* vd3d_letterbox_track: LetterboxTracker.update for the B frames of a step, in order, on the state in the context: statistics, Canny and one tracker
+ * launch; out_bars [B][2] int32 = (top, bottom) in force after each frame (device memory). */
+int vd3d_letterbox_track(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, const vd3d_letterbox_params* params, int32_t* out_bars);
+/* Tracker state: reset = a new tracker (locked_zero, nothing kept); export / import move the scalars, and -- when the pointers are given and a
+ * previous frame is kept -- its histogram (host, 64 uint32) and gray plane (DEVICE, prev_h * prev_w bytes; gray_capacity = room at prev_gray_dev).
+ * An import without both pointers keeps no previous frame. */
+int vd3d_letterbox_state_reset(vd3d_ctx* ctx);
+int vd3d_letterbox_state_export(vd3d_ctx* ctx, vd3d_letterbox_state* out, uint32_t* prev_hist64_host_or_null, uint8_t* prev_gray_dev_or_null,
+                                long long gray_capacity);
+int vd3d_letterbox_state_import(vd3d_ctx* ctx, const vd3d_letterbox_state* in, const uint32_t* prev_hist64_host_or_null,
+                                const uint8_t* prev_gray_dev_or_null);
+/* vd3d_depth_letterbox_fill_u8: :1919-1933 per plane of depth [B][H][W] uint8 -> out (another buffer): (top, bottom) of frame b =
+ * bars_dev[b * bars_stride + 0 / 1] (device int32; bars_stride 0 = one pair for all frames; negative values count as 0).  The plane is squeezed
+ * into core_h = H - top - bottom rows with vd3d_resize_cubic_u8's arithmetic and the bar rows are filled with int(np.median(squeezed)); no bars, or
+ * core_h <= 0, copy the plane. */
+int vd3d_depth_letterbox_fill_u8(vd3d_ctx* ctx, const uint8_t* depth, int B, int H, int W, const int32_t* bars_dev, int bars_stride, uint8_t* out);
 
 /* element type of the depth network's activations (a25).  The reference loads its Hugging Face depth models with
  * AutoModelForDepthEstimation.from_pretrained(checkpoint) and no dtype, i.e. float32 (core/render_depth.py:758-759,823-824):

@@ -111,3 +111,17 @@ class FrameScalars(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class LetterboxState(C.Structure):
+    """vd3d_letterbox_state: the reference LetterboxTracker's attributes + the size of the previous frame the context keeps."""
+    _fields_ = [(k, C.c_int32) for k in ("top", "bottom", "locked_zero", "locked_bars", "cand_top", "cand_bottom", "streak", "cooldown",
+                                         "have_prev", "prev_h", "prev_w", "reserved")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class LetterboxParams(C.Structure):
+    """vd3d_letterbox_params: LetterboxTracker.__init__ after its int() conversions."""
+    _fields_ = [(k, C.c_int32) for k in ("min_change", "confirm_needed", "max_total", "cooldown_frames")]

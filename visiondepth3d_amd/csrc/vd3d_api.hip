@@ -54,6 +54,7 @@ struct vd3d_ctx {
   uint8_t* gLR = nullptr; size_t gLR_cap = 0;   // [H][2W][3] sharpened eyes side by side (E1 in front of a fit it does not take)
   uint32_t* mm = nullptr; int mm_cap = 0;
   uint32_t* pclip_ws = nullptr; int pclip_cap = 0;    // vd3d_depth_normalize_pclip_u8: [frames][VD_PCLIP_WS_WORDS] radix-select histograms
+  vd_lb_ws* lb = nullptr;                             // letterbox tracker state and workspace (vd3d_letterbox.hip), created on first use
   uint32_t* rowflag = nullptr; int rowflag_cap = 0;   // k_autocrop: one flag per source row
   uint8_t* blank_eye = nullptr; size_t blank_cap = 0; // skip_blank_frames: the side-masked source frame (source size)
   // vd3d_render_params::aten_sum_threads > 0: piece plan of the two torch.mean sums (vd3d_atensum.hip) for the current eye size / thread count, and the
@@ -261,6 +262,7 @@ VD3D_EXPORT int vd3d_ctx_destroy(vd3d_ctx* c) {
   for (auto& t : c->w2_tabs) (void)hipFree(t.dev);
   for (auto& t : c->wk_tabs) (void)hipFree(t.dev);
   for (void* p : ptrs) if (p) (void)hipFree(p);
+  vd_lb_free(c->lb);
   for (auto* v : {&c->slot_rgb, &c->slot_dn, &c->slot_D, &c->slot_tdf, &c->slot_tdfp})
     for (float* q : *v) (void)hipFree(q);
   if (c->slot_work) (void)hipFree(c->slot_work);
@@ -1494,6 +1496,86 @@ VD3D_EXPORT int vd3d_depth_normalize_pclip_u8(vd3d_ctx* c, const float* planes, 
   StageTimer t(c, "pclip_u8");
   vd_launch_pclip_u8(c->stream, planes, B, n, rank, g[0], g[1], invert ? 1 : 0, c->pclip_ws, out_gray, lo_hi_dev_or_null);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// letterbox handling of the depth pass (vd3d_letterbox.hip): LetterboxTracker and the bar fill (core/render_depth.py:280-573,1919-1933)
+static int lb_check(vd3d_ctx* c, const void* p0, const void* p1, int B, int H, int W) {
+  if (!c || !p0 || !p1 || B < 1 || H < 1 || W < 1) return set_err(VD3D_E_INVALID, "bad argument");
+  if (!vd_lb_size_ok(B, H, W)) return set_err(VD3D_E_UNSUPPORTED, "letterbox: %d frames of %dx%d (built for W <= 8192, H <= 8192, B <= 4096)", B, W, H);
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_letterbox_stats(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int chain, float* row_mean, float* row_var,
+                                     uint32_t* row_sat_sum, uint8_t* gray, uint32_t* hist64, uint64_t* mad_sum, float* frame_mean) {
+  if (!row_mean || !row_var || !row_sat_sum || !hist64 || !mad_sum || !frame_mean) return set_err(VD3D_E_INVALID, "bad argument");
+  if (int rc = lb_check(c, frames_bgr, gray, B, H, W)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "letterbox_stats");
+  HIPCHK(vd_lb_stats(&c->lb, c->stream, frames_bgr, B, H, W, chain ? 1 : 0, row_mean, row_var, row_sat_sum, gray, hist64,
+                     reinterpret_cast<unsigned long long*>(mad_sum), frame_mean));
+  if (chain) HIPCHK(vd_lb_stats_commit(&c->lb, c->stream, gray, hist64, B, H, W));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_canny_u8(vd3d_ctx* c, const uint8_t* gray, int B, int H, int W, int low, int high, uint8_t* edges, int32_t* row_counts_or_null) {
+  if (int rc = lb_check(c, gray, edges, B, H, W)) return rc;
+  if (low < 0 || high < low || high > 1442) return set_err(VD3D_E_INVALID, "canny: thresholds %d, %d (0 <= low <= high <= 1442)", low, high);
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "canny");
+  HIPCHK(vd_lb_canny(&c->lb, c->stream, gray, B, H, W, low, high, edges, row_counts_or_null));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_canny_hysteresis_u8(vd3d_ctx* c, const uint8_t* classes, int B, int H, int W, uint8_t* edges, int32_t* row_counts_or_null) {
+  if (int rc = lb_check(c, classes, edges, B, H, W)) return rc;
+  if (classes == edges) return set_err(VD3D_E_INVALID, "canny_hysteresis: the edge map needs its own buffer");
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "canny_hysteresis");
+  HIPCHK(vd_lb_hysteresis(&c->lb, c->stream, classes, B, H, W, edges, row_counts_or_null));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_letterbox_track(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, const vd3d_letterbox_params* params, int32_t* out_bars) {
+  if (!params) return set_err(VD3D_E_INVALID, "bad argument");
+  if (int rc = lb_check(c, frames_bgr, out_bars, B, H, W)) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "letterbox_track");
+  HIPCHK(vd_lb_track(&c->lb, c->stream, frames_bgr, B, H, W, params, out_bars));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_letterbox_state_reset(vd3d_ctx* c) {
+  if (!c) return set_err(VD3D_E_INVALID, "NULL context");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(vd_lb_state_reset(&c->lb, c->stream));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_letterbox_state_export(vd3d_ctx* c, vd3d_letterbox_state* out, uint32_t* prev_hist64_host_or_null, uint8_t* prev_gray_dev_or_null,
+                                            long long gray_capacity) {
+  if (!c || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(vd_lb_state_export(&c->lb, c->stream, out, prev_hist64_host_or_null, prev_gray_dev_or_null, gray_capacity));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_letterbox_state_import(vd3d_ctx* c, const vd3d_letterbox_state* in, const uint32_t* prev_hist64_host_or_null,
+                                            const uint8_t* prev_gray_dev_or_null) {
+  if (!c || !in) return set_err(VD3D_E_INVALID, "bad argument");
+  if (in->have_prev && prev_gray_dev_or_null && !vd_lb_size_ok(1, in->prev_h, in->prev_w)) return set_err(VD3D_E_INVALID, "letterbox state: previous frame %dx%d", in->prev_w, in->prev_h);
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(vd_lb_state_import(&c->lb, c->stream, in, prev_hist64_host_or_null, prev_gray_dev_or_null));
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_depth_letterbox_fill_u8(vd3d_ctx* c, const uint8_t* depth, int B, int H, int W, const int32_t* bars_dev, int bars_stride, uint8_t* out) {
+  if (!bars_dev || bars_stride < 0 || bars_stride == 1) return set_err(VD3D_E_INVALID, "bad argument");
+  if (int rc = lb_check(c, depth, out, B, H, W)) return rc;
+  if (depth == out) return set_err(VD3D_E_INVALID, "depth_letterbox_fill: the output needs its own buffer");
+  HIPCHK(hipSetDevice(c->device));
+  StageTimer t(c, "letterbox_fill");
+  HIPCHK(vd_lb_fill(&c->lb, c->stream, depth, B, H, W, bars_dev, bars_stride, out));
   return 0;
 }
 

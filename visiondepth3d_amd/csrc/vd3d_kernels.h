@@ -280,6 +280,22 @@ void vd_launch_tile_blend(hipStream_t s, const float* pool, const long long* pre
 void vd_launch_pclip_u8(hipStream_t s, const float* planes, int B, long long n, const uint32_t rank[VD_PCLIP_NR], float g_lo, float g_hi, int invert,
                         uint32_t* ws, uint8_t* out, float* lohi);
 
+// ---- vd3d_letterbox.hip: the depth pass's letterbox tracker and bar fill (frame statistics, Canny, tracker step, INTER_CUBIC squeeze + median fill).
+// The workspace (tracker state, plans of numpy's pairwise sums, labelling planes) is created on first use; every call enqueues on `s`.
+struct vd_lb_ws;
+void vd_lb_free(vd_lb_ws* w);
+bool vd_lb_size_ok(int B, int H, int W);
+hipError_t vd_lb_state_reset(vd_lb_ws** ws, hipStream_t s);
+hipError_t vd_lb_state_export(vd_lb_ws** ws, hipStream_t s, vd3d_letterbox_state* out, uint32_t* prev_hist64, uint8_t* prev_gray_dev, long long gray_cap);
+hipError_t vd_lb_state_import(vd_lb_ws** ws, hipStream_t s, const vd3d_letterbox_state* in, const uint32_t* prev_hist64, const uint8_t* prev_gray_dev);
+hipError_t vd_lb_stats(vd_lb_ws** ws, hipStream_t s, const uint8_t* frames, int B, int H, int W, int chain, float* row_mean, float* row_var,
+                       uint32_t* row_sat, uint8_t* gray, uint32_t* hist, unsigned long long* mad, float* fmean);
+hipError_t vd_lb_stats_commit(vd_lb_ws** ws, hipStream_t s, const uint8_t* gray, const uint32_t* hist, int B, int H, int W);
+hipError_t vd_lb_canny(vd_lb_ws** ws, hipStream_t s, const uint8_t* gray, int B, int H, int W, int low, int high, uint8_t* edges, int32_t* rowcnt);
+hipError_t vd_lb_hysteresis(vd_lb_ws** ws, hipStream_t s, const uint8_t* cls, int B, int H, int W, uint8_t* edges, int32_t* rowcnt);
+hipError_t vd_lb_track(vd_lb_ws** ws, hipStream_t s, const uint8_t* frames, int B, int H, int W, const vd3d_letterbox_params* p, int32_t* out_bars);
+hipError_t vd_lb_fill(vd_lb_ws** ws, hipStream_t s, const uint8_t* depth, int B, int H, int W, const int32_t* bars_dev, int bars_stride, uint8_t* out);
+
 // ---- vd3d_finish.hip
 bool vd_launch_finish_fused(hipStream_t s, const uint8_t* L, const uint8_t* R, const float* dn, int eh, int ew,
                             const vd3d_render_params& p, const vd_finish_consts& fc, const vd_dev_work* w, float focal,

@@ -826,13 +826,24 @@ class DepthPipe:
 
     @torch.no_grad()
     def depth_frames_u8(self, frames_bgr: torch.Tensor, inference_size=None, invert: bool = False, tiled: bool = False, tile: int = 512,
-                        pad: int = 32, tile_batch: int = 16) -> torch.Tensor:
+                        pad: int = 32, tile_batch: int = 16, bars=None) -> torch.Tensor:
         """The depth tab's per-frame product (core/render_depth.py:1907-1917) for uint8 [B,H,W,3] BGR frames: the prediction at the size
         the pipeline saw (the frame, or ``inference_size`` = (W', H')) -> ``convert_depth_to_grayscale`` -> optional ``255 -`` ->
         ``cv2.resize(..., (W, H), INTER_CUBIC)``.  Returns uint8 [B,H,W] on the device (what the reference writes to its depth video).
         ``tiled=True`` (OPT-IN, needs a renderer): the reference's USE_TILED_DEPTH product instead -- ``infer_tiled_bgr_u8`` (``tile`` /
         ``pad`` / ``tile_batch``) -> ``_normalize_to_u8``'s 1 % - 99 % percentile normalisation (:173-194, ``Renderer.depth_normalize_pclip``) -> the same
-        INTER_CUBIC resize to the frame size."""
+        INTER_CUBIC resize to the frame size.
+        ``bars`` (``ignore_letterbox_bars``, :1919-1933; needs a renderer): a (top, bottom) pair or the int32 [B,2] device tensor
+        ``letterbox.LetterboxTracker.update`` returns -- every plane is then squeezed into the picture rows and the bars are filled with the
+        squeezed plane's median (``Renderer.depth_letterbox_fill``).  ``None``: the planes as they are."""
+        u8 = self._depth_frames_u8(frames_bgr, inference_size, invert, tiled, tile, pad, tile_batch)
+        if bars is None:
+            return u8
+        if self.renderer is None:
+            raise RuntimeError("depth_frames_u8(bars=...) needs DepthPipe(renderer=...) for the letterbox fill")
+        return self.renderer.depth_letterbox_fill(u8, bars)
+
+    def _depth_frames_u8(self, frames_bgr, inference_size, invert, tiled, tile, pad, tile_batch):
         B, H, W, _ = frames_bgr.shape
         if tiled:
             d = self.infer_tiled_bgr_u8(frames_bgr, inference_size, tile=tile, pad=pad, tile_batch=tile_batch)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _abi, _lib
-from ._abi import DEPTH_BGR_U8, DEPTH_F32, DEPTH_GRAY_U8, DT_BF16, DT_F16, DT_F32, FORMAT_IDS, FrameScalars, RenderParams, ShiftParams, State
+from ._abi import DEPTH_BGR_U8, DEPTH_F32, DEPTH_GRAY_U8, DT_BF16, DT_F16, DT_F32, FORMAT_IDS, FrameScalars, LetterboxParams, LetterboxState, RenderParams, ShiftParams, State
 from .geometry import aspect_ratios  # noqa: F401  (re-exported like the reference module does)
 from .params import reference_aten_threads, render_kwargs_to_params, shift_params_from_kwargs
 
@@ -398,6 +398,131 @@ class Renderer:
         self._enter(p, out)
         _lib.check(self._L.vd3d_depth_normalize_pclip_u8(self._ctx, _ptr(p), B, H, W, float(pclip[0]), float(pclip[1]), int(bool(invert)),
                                                          _ptr(out), None if lo_hi is None else _ptr(lo_hi)))
+        return out
+
+    # ---- letterbox handling of the depth pass (core/render_depth.py:280-573,1919-1933; statement: visiondepth3d_amd.letterbox) ----
+    def _lb_frames(self, frames: torch.Tensor, what: str) -> torch.Tensor:
+        f = torch.as_tensor(frames)
+        f = f if f.dim() == 4 else f[None]
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+            raise AssertionError(f"{what} takes uint8 [B,H,W,3] BGR frames")
+        return f.to(self.device).contiguous()
+
+    def _lb_planes(self, planes: torch.Tensor, what: str) -> torch.Tensor:
+        p = torch.as_tensor(planes)
+        p = p if p.dim() == 3 else p[None]
+        if p.dtype != torch.uint8 or p.dim() != 3:
+            raise AssertionError(f"{what} takes uint8 [B,H,W] planes")
+        return p.to(self.device).contiguous()
+
+    def letterbox_stats(self, frames_bgr: torch.Tensor, chain: bool = False) -> dict:
+        """One statistics pass over uint8 [B,H,W,3] frames (vd3d_letterbox_stats): dict of device tensors ``row_mean`` / ``row_var`` float32
+        [B,H], ``row_sat`` int32 [B,H] (integer sums of the HSV saturation), ``gray`` uint8 [B,H,W], ``hist`` int32 [B,64], ``mad_sum`` int64
+        [B] (sum |gray_t - gray_(t-1)|; frame 0: against the tracker state's frame when ``chain``, else 0) and ``frame_mean`` float32 [B]."""
+        f = self._lb_frames(frames_bgr, "letterbox_stats")
+        B, H, W, _ = f.shape
+        dev = self.device
+        o = dict(row_mean=torch.empty((B, H), dtype=torch.float32, device=dev), row_var=torch.empty((B, H), dtype=torch.float32, device=dev),
+                 row_sat=torch.empty((B, H), dtype=torch.int32, device=dev), gray=torch.empty((B, H, W), dtype=torch.uint8, device=dev),
+                 hist=torch.empty((B, 64), dtype=torch.int32, device=dev), mad_sum=torch.empty((B,), dtype=torch.int64, device=dev),
+                 frame_mean=torch.empty((B,), dtype=torch.float32, device=dev))
+        self._enter(f, *o.values())
+        _lib.check(self._L.vd3d_letterbox_stats(self._ctx, _ptr(f), B, H, W, int(bool(chain)), _ptr(o["row_mean"]), _ptr(o["row_var"]), _ptr(o["row_sat"]),
+                                                _ptr(o["gray"]), _ptr(o["hist"]), _ptr(o["mad_sum"]), _ptr(o["frame_mean"])))
+        return o
+
+    def canny_u8(self, gray: torch.Tensor, low: int = 30, high: int = 90, want_counts: bool = False):
+        """cv2.Canny(gray, low, high, apertureSize=3, L2gradient=True) per uint8 [B,H,W] plane -> uint8 edge maps [B,H,W]; with ``want_counts``
+        also the int32 [B,H] edge pixels per row."""
+        g = self._lb_planes(gray, "canny_u8")
+        B, H, W = g.shape
+        out = torch.empty_like(g)
+        cnt = torch.empty((B, H), dtype=torch.int32, device=self.device) if want_counts else None
+        self._enter(g, out, *(() if cnt is None else (cnt,)))
+        _lib.check(self._L.vd3d_canny_u8(self._ctx, _ptr(g), B, H, W, int(low), int(high), _ptr(out), None if cnt is None else _ptr(cnt)))
+        return (out, cnt) if want_counts else out
+
+    def canny_hysteresis_u8(self, classes: torch.Tensor, want_counts: bool = False):
+        """Canny's second half on a given class map uint8 [B,H,W] (0 none, 1 weak, 2 strong): 255 on every non-zero pixel 8-connected, through
+        non-zero pixels, to a strong one."""
+        c = self._lb_planes(classes, "canny_hysteresis_u8")
+        B, H, W = c.shape
+        out = torch.empty_like(c)
+        cnt = torch.empty((B, H), dtype=torch.int32, device=self.device) if want_counts else None
+        self._enter(c, out, *(() if cnt is None else (cnt,)))
+        _lib.check(self._L.vd3d_canny_hysteresis_u8(self._ctx, _ptr(c), B, H, W, _ptr(out), None if cnt is None else _ptr(cnt)))
+        return (out, cnt) if want_counts else out
+
+    def letterbox_track(self, frames_bgr: torch.Tensor, h: int, min_change: int = 8, confirm_needed: int = 3, max_total: int | None = None,
+                        cooldown_frames: int = 90, out: torch.Tensor | None = None) -> torch.Tensor:
+        """LetterboxTracker.update for the frames of a step, in order, on the tracker state in the context -> int32 [B,2] (top, bottom) on
+        the device; no host synchronisation.  ``max_total`` defaults to int(h * 0.35)."""
+        f = self._lb_frames(frames_bgr, "letterbox_track")
+        B, H, W, _ = f.shape
+        p = LetterboxParams(int(min_change), int(confirm_needed), int(int(h) * 0.35) if max_total is None else int(max_total), int(cooldown_frames))
+        if out is None:
+            out = torch.empty((B, 2), dtype=torch.int32, device=self.device)
+        self._enter(f, out)
+        _lib.check(self._L.vd3d_letterbox_track(self._ctx, _ptr(f), B, H, W, C.byref(p), _ptr(out)))
+        return out
+
+    def letterbox_state_reset(self):
+        """A new tracker: no bars (locked_zero), no previous frame."""
+        self._enter()
+        _lib.check(self._L.vd3d_letterbox_state_reset(self._ctx))
+
+    def letterbox_state_export(self, with_frame: bool = False) -> dict:
+        """The tracker state as a dict (synchronises).  ``with_frame``: also ``prev_hist`` (numpy int64 [64]) and ``prev_gray`` (device uint8
+        [prev_h, prev_w]) of the frame the next update is compared with, when one is kept."""
+        self._enter()
+        s = LetterboxState()
+        _lib.check(self._L.vd3d_letterbox_state_export(self._ctx, C.byref(s), None, None, 0))
+        d = s.as_dict()
+        if with_frame and s.have_prev:
+            hist = (C.c_uint32 * 64)()
+            g = torch.empty((s.prev_h, s.prev_w), dtype=torch.uint8, device=self.device)
+            _lib.check(self._L.vd3d_letterbox_state_export(self._ctx, C.byref(s), hist, _ptr(g), g.numel()))
+            self.sync()
+            d["prev_hist"], d["prev_gray"] = np.asarray(list(hist), np.int64), g
+        return d
+
+    def letterbox_state_import(self, state: dict):
+        """Restore a tracker state (``letterbox_state_export``'s dict; without ``prev_hist`` / ``prev_gray`` no previous frame is kept)."""
+        s = LetterboxState()
+        for k, _ in LetterboxState._fields_:
+            setattr(s, k, int(state.get(k, 0)))
+        g, hist = state.get("prev_gray"), state.get("prev_hist")
+        if g is None or hist is None or not s.have_prev:
+            s.have_prev = 0
+            self._enter()
+            _lib.check(self._L.vd3d_letterbox_state_import(self._ctx, C.byref(s), None, None))
+            return
+        g = g.to(self.device).contiguous()
+        s.prev_h, s.prev_w = int(g.shape[0]), int(g.shape[1])
+        h64 = (C.c_uint32 * 64)(*[int(v) for v in hist])
+        self._enter(g)
+        _lib.check(self._L.vd3d_letterbox_state_import(self._ctx, C.byref(s), h64, _ptr(g)))
+
+    def depth_letterbox_fill(self, depth_u8: torch.Tensor, bars, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The letterbox handling behind the hand-off (core/render_depth.py:1919-1933) per uint8 [B,H,W] depth plane: squeezed into the picture
+        rows with INTER_CUBIC, bars filled with the squeezed plane's median.  ``bars``: a (top, bottom) pair for every frame or an int32 [B,2]
+        device tensor (LetterboxTracker.update's result: it never visits the host)."""
+        d = self._lb_planes(depth_u8, "depth_letterbox_fill")
+        B, H, W = d.shape
+        if isinstance(bars, torch.Tensor):
+            t = bars.to(self.device, torch.int32).contiguous()
+            if t.numel() == 2:
+                t, stride = t.reshape(2), 0
+            elif tuple(t.shape) == (B, 2):
+                stride = 2
+            else:
+                raise AssertionError("depth_letterbox_fill: bars is a (top, bottom) pair or an int32 [B,2] tensor")
+        else:
+            t, stride = torch.tensor([int(bars[0]), int(bars[1])], dtype=torch.int32, device=self.device), 0
+        if out is None:
+            out = torch.empty_like(d)
+        self._enter(d, t, out)
+        _lib.check(self._L.vd3d_depth_letterbox_fill_u8(self._ctx, _ptr(d), B, H, W, _ptr(t), stride, _ptr(out)))
         return out
 
     # ---- optional NV12 wire format at the frame I/O boundary (SURVEY 8(f)1) ----
