@@ -36,7 +36,15 @@ def _frames(h, w):
 # ---- statistics ------------------------------------------------------------------------------------------------------------------------
 # 81 x 100 = 8100 elements: the last (here the only) chunk of the whole-plane mean splits into 65 leaves, one more than a full 8192-element chunk;
 # 103 x 155 = 8192 + 7773: a full chunk followed by such a tail, in every frame of the batch
-@pytest.mark.parametrize("hw", SIZES + [(81, 100), (103, 155)])
+# Wide rows, few of them (k_lb_rows gives a leaf to each 8-lane group, 32 leaves per sweep): 1920 is 16 leaves (wave 1 sums too), 3840 and 4096
+# are 32 (every group of every wave), 4104 is 33 (a second sweep with one leaf), 7688 is 64 (two full sweeps), 7689 and 8190 are 65 leaves + 64
+# steps (the largest plan there is, a third sweep), 8192 is 64 again.
+WIDE = [(4, 1920), (4, 3840), (3, 4096), (3, 4104), (3, 7688), (3, 7689), (3, 8190), (2, 8192)]
+# Rows shorter than 8 (the plain loop of a leaf), one leaf and no combine step, a single row, a single column, 130 = two leaves of 64 and 66
+DEGENERATE = [(1, 1), (1, 7), (7, 1), (2, 9), (5, 8), (3, 130)]
+
+
+@pytest.mark.parametrize("hw", SIZES + [(81, 100), (103, 155)] + WIDE + DEGENERATE)
 def test_stats_bit_exact_vs_statement(R, hw):
     h, w = hw
     f = _frames(h, w)
@@ -70,6 +78,39 @@ def test_stats_chain_compares_with_the_previous_batch(R):
     assert np.array_equal(s["prev_gray"].cpu().numpy(), lb.bgr2gray_numpy(f[2])) and np.array_equal(s["prev_hist"], lb.hist64_numpy(lb.bgr2gray_numpy(f[2])))
 
 
+def test_frame_mean_over_more_chunks_than_its_window(R):
+    """1025 x 8190 is 1025 chunks of 8192 elements, the last one short: k_lb_frame_mean sums 1024 chunk sums per pass through its LDS window, so
+    its second pass gets exactly the tail chunk.  Against numpy itself and the statement of its order; the statement's Canny is not needed."""
+    h, w = 1025, 8190
+    assert -(-h * w // lb.NUMPY_BUFSIZE) == 1025 and h * w % lb.NUMPY_BUFSIZE
+    f = np.random.default_rng(h + w).integers(0, 256, (1, h, w, 3), dtype=np.uint8)
+    R.letterbox_state_reset()
+    got = {k: v.cpu().numpy() for k, v in R.letterbox_stats(torch.from_numpy(f).cuda()).items() if k != "gray"}
+    y, s = lb.luma_saturation_numpy(f[0])
+    assert got["frame_mean"][0] == lb.luma_mean_numpy(y), (got["frame_mean"][0], lb.luma_mean_numpy(y))
+    assert got["frame_mean"][0] == y.mean(), "numpy itself"
+    assert np.array_equal(got["row_mean"][0], y.mean(axis=1)) and np.array_equal(got["row_var"][0], y.var(axis=1))
+    assert np.array_equal(got["row_sat"][0], s.astype(np.int64).sum(axis=1)) and int(got["mad_sum"][0]) == 0
+
+
+def test_stats_chain_across_a_change_of_size(R):
+    """The state's gray plane grows (72 x 100 -> 96 x 136) and is reused at a smaller size (-> 72 x 100): no comparison across the change, the
+    usual one inside a size, and the state keeps the last frame each time."""
+    R.letterbox_state_reset()
+    for h, w in ((72, 100), (96, 136), (72, 100)):
+        f = _frames(h, w)
+        gray = [lb.bgr2gray_numpy(fr).astype(np.int64) for fr in f]
+        dev = torch.from_numpy(f).cuda()
+        a = R.letterbox_stats(dev[:2], chain=True)
+        assert int(a["mad_sum"][0]) == 0, (h, w)
+        assert int(a["mad_sum"][1]) == int(np.abs(gray[1] - gray[0]).sum()) > 0
+        b = R.letterbox_stats(dev[2:], chain=True)
+        assert int(b["mad_sum"][0]) == int(np.abs(gray[2] - gray[1]).sum()) > 0, (h, w)
+        s = R.letterbox_state_export(with_frame=True)
+        assert (s["have_prev"], s["prev_h"], s["prev_w"]) == (1, h, w)
+        assert np.array_equal(s["prev_gray"].cpu().numpy(), gray[2]) and np.array_equal(s["prev_hist"], lb.hist64_numpy(gray[2].astype(np.uint8)))
+
+
 # ---- Canny -----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("hw", SIZES)
 def test_canny_equals_statement(R, hw):
@@ -83,6 +124,24 @@ def test_canny_equals_statement(R, hw):
         assert exp.any()
         assert np.array_equal(edges[b], exp), (hw, b, int(np.count_nonzero(edges[b] != exp)))
         assert np.array_equal(counts[b], np.count_nonzero(exp, axis=1))
+
+
+@pytest.mark.parametrize("hw", LC.CANNY_SIZES)
+def test_canny_small_sizes_and_tie_planes(R, hw):
+    """Images smaller than the 64 x 16 tile plus halo, exactly one tile, one pixel past it; the third plane decides ties of the non-maximum test
+    in both directions (tests/test_letterbox_host.py asserts that on the statement), so it goes through with both of its flips."""
+    h, w = hw
+    tie = LC.tie_plane(h, w)
+    gray = np.stack([lb.bgr2gray_numpy(fr) for fr in _frames(h, w)[1:]] + [tie])     # a synth frame, noise, the tie plane
+    flips = np.stack([np.ascontiguousarray(tie[:, ::-1]), np.ascontiguousarray(tie[::-1])])
+    for planes in (gray, flips):
+        edges, counts = R.canny_u8(torch.from_numpy(planes).cuda(), 30, 90, want_counts=True)
+        edges, counts = edges.cpu().numpy(), counts.cpu().numpy()
+        for b in range(len(planes)):
+            exp = lb.canny_numpy(planes[b], 30, 90)
+            assert np.array_equal(edges[b], exp), (hw, b, int(np.count_nonzero(edges[b] != exp)))
+            assert np.array_equal(counts[b], np.count_nonzero(exp, axis=1)), (hw, b)
+    assert lb.canny_numpy(tie).any() == (hw != (1, 1))
 
 
 def _serpentine(h, w, step=4):
@@ -134,11 +193,10 @@ def test_hysteresis_on_hand_made_class_maps(R):
 # ---- tracker ---------------------------------------------------------------------------------------------------------------------------
 def _device_run(R, name, batch):
     boot, upd = LC.clip(name)
-    t = lb.LetterboxTracker(R, LC.H, LC.FPS)
+    h, _, fps = LC.geometry(name)
+    t = lb.LetterboxTracker(R, h, fps)
     b = t.bootstrap(torch.from_numpy(np.stack(boot)))
-    frames = torch.from_numpy(np.stack(upd)).cuda()
-    n = len(upd) if batch is None else batch
-    bars = torch.cat([t.update(frames[i:i + n]) for i in range(0, len(upd), n)]).cpu().numpy()
+    bars = torch.cat([t.update(torch.from_numpy(np.stack(fr)).cuda()) for fr in LC.batches(upd, batch)]).cpu().numpy()   # a batch has one frame size
     return b, [tuple(int(v) for v in r) for r in bars], t
 
 
@@ -159,7 +217,8 @@ def test_tracker_state_round_trips_through_export_and_import(R):
     exp = LC.statement_run(name)
     boot, upd = LC.clip(name)
     frames = torch.from_numpy(np.stack(upd)).cuda()
-    t = lb.LetterboxTracker(R, LC.H, LC.FPS)
+    h, _, fps = LC.geometry(name)
+    t = lb.LetterboxTracker(R, h, fps)
     t.bootstrap(torch.from_numpy(np.stack(boot)))
     first = t.update(frames[:9]).cpu().numpy()                  # stops between two cuts with a streak of 2 pending
     saved = R.letterbox_state_export(with_frame=True)
@@ -196,6 +255,67 @@ def test_fill_equals_statement(R, hw):
     one = R.depth_letterbox_fill(torch.from_numpy(d).cuda(), (7, 12)).cpu().numpy()
     for b in range(4):
         assert np.array_equal(one[b], lb.letterbox_fill_numpy(d[b], 7, 12)), (hw, b)
+
+
+# core_h = 1 (one picture row, either side), core_h = 2, a single bar row (either side), no picture row left (the plane is copied); H = 1
+SQUEEZES = [((40, 70), [(39, 0), (0, 39), (19, 19), (1, 0), (0, 1), (40, 0)]), ((1, 70), [(1, 0), (0, 0)])]
+
+
+@pytest.mark.parametrize("hw,pairs", SQUEEZES)
+def test_fill_at_the_extreme_squeezes(R, hw, pairs):
+    h, w = hw
+    d = _depth_planes(h, w)
+    exp = {p: [lb.letterbox_fill_numpy(d[k], *p) for k in range(4)] for p in pairs}
+    for p in pairs:   # one pair for every plane
+        one = R.depth_letterbox_fill(torch.from_numpy(d).cuda(), p).cpu().numpy()
+        for k in range(4):
+            assert np.array_equal(one[k], exp[p][k]), (hw, p, k)
+    # a pair per plane: every plane kind with every pair, in one batch
+    planes = np.concatenate([d] * len(pairs))
+    bars = np.array([p for p in pairs for _ in range(4)], np.int32)
+    got = R.depth_letterbox_fill(torch.from_numpy(planes).cuda(), torch.from_numpy(bars).cuda()).cpu().numpy()
+    for i, p in enumerate(pairs):
+        for k in range(4):
+            assert np.array_equal(got[4 * i + k], exp[p][k]), (hw, p, k)
+    if (h, 0) in pairs:
+        assert all(np.array_equal(exp[(h, 0)][k], d[k]) for k in range(4)), "no picture row left: the plane as it is"
+    if h > 1:
+        assert (exp[(h - 1, 0)][0][:h - 1] == exp[(h - 1, 0)][0][0, 0]).all() and exp[(h - 1, 0)][1][h - 1].std() > 0, "one picture row under a filled bar"
+
+
+# ---- seeded sweep ------------------------------------------------------------------------------------------------------------------------
+def test_seeded_sweep_of_small_geometries(R):
+    """24 geometries from a fixed seed, H in 1..47, W in 1..399, a noise frame and a block frame each: statistics, Canny with its row counts and
+    one fill with random valid bars, all against the statement."""
+    rng = np.random.default_rng(0)
+    for _ in range(24):
+        h, w = int(rng.integers(1, 48)), int(rng.integers(1, 400))
+        tie = LC.tie_plane(h, w)
+        f = np.stack([rng.integers(0, 256, (h, w, 3), dtype=np.uint8), np.stack([tie, tie[:, ::-1], tie[::-1]], axis=-1)])
+        top = int(rng.integers(0, h))
+        bars = np.array([[top, int(rng.integers(0, h - top))], [int(rng.integers(0, h)), 0]], np.int32)
+        geo = dict(h=h, w=w, bars=bars.tolist())
+        R.letterbox_state_reset()
+        got = {k: v.cpu().numpy() for k, v in R.letterbox_stats(torch.from_numpy(f).cuda()).items()}
+        gray = np.stack([lb.bgr2gray_numpy(f[0]), tie])
+        edges, counts = R.canny_u8(torch.from_numpy(gray).cuda(), 30, 90, want_counts=True)
+        edges, counts = edges.cpu().numpy(), counts.cpu().numpy()
+        fill = R.depth_letterbox_fill(torch.from_numpy(gray).cuda(), torch.from_numpy(bars).cuda()).cpu().numpy()
+        prev = None
+        for b in range(2):
+            st = lb.frame_stats_numpy(f[b], prev)
+            prev = st["gray"]
+            _, s = lb.luma_saturation_numpy(f[b])
+            for k in ("row_mean", "row_var"):
+                assert np.array_equal(got[k][b].view(np.uint32), st[k].view(np.uint32)), (geo, b, k)
+            assert np.array_equal(got["row_sat"][b], s.astype(np.int64).sum(axis=1)), (geo, b)
+            assert np.array_equal(got["gray"][b], st["gray"]) and np.array_equal(got["hist"][b], st["hist"]), (geo, b)
+            assert int(got["mad_sum"][b]) == (st["mad_sum"] if b else 0), (geo, b)
+            assert got["frame_mean"][b] == st["frame_mean"], (geo, b)
+            exp = lb.canny_numpy(gray[b], 30, 90)
+            assert np.array_equal(edges[b], exp), (geo, b, int(np.count_nonzero(edges[b] != exp)))
+            assert np.array_equal(counts[b], np.count_nonzero(exp, axis=1)), (geo, b)
+            assert np.array_equal(fill[b], lb.letterbox_fill_numpy(gray[b], *bars[b])), (geo, b)
 
 
 @pytest.fixture(scope="module")

@@ -20,7 +20,8 @@ GOLDEN_JSON = os.path.join(GOLDEN, "letterbox_tracker.json")
 
 
 # ---- pairwise statement ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("w", [7, 64, 100, 129, 136, 333])
+# 1, 5: a leaf shorter than 8 elements; 1920, 3840: 16 and 32 leaves; 4104: 33; 7689, 8190: 65, the most a row can have; 8192: 64
+@pytest.mark.parametrize("w", [1, 5, 7, 64, 100, 129, 136, 333, 1920, 3840, 4104, 7689, 8190, 8192])
 def test_pairwise_restatement_equals_numpy_mean_and_var(w):
     rng = np.random.default_rng(w)
     f = rng.integers(0, 256, (9, w, 3), dtype=np.uint8)
@@ -31,15 +32,22 @@ def test_pairwise_restatement_equals_numpy_mean_and_var(w):
     mean, var, sat = lb.row_uniformity_numpy(f)
     assert np.array_equal(mean, y.mean(axis=1)) and np.array_equal(var, y.var(axis=1)) and np.array_equal(sat, s.mean(axis=1))
     assert lb.luma_mean_numpy(y) == y.mean()          # the whole plane: one run of 9 * w elements
-    assert lb.pairwise_sum(y) == np.add.reduce(y.reshape(-1))
+    flat = y.reshape(-1)
+    if flat.size <= lb.NUMPY_BUFSIZE:
+        assert lb.pairwise_sum(y) == np.add.reduce(flat)
+    else:   # numpy hands a longer run to its inner loop in buffers of 8192: a pairwise sum per buffer, added up in order
+        acc = np.float32(0)
+        for o in range(0, flat.size, lb.NUMPY_BUFSIZE):
+            acc = np.float32(acc + lb.pairwise_sum(flat[o:o + lb.NUMPY_BUFSIZE]))
+        assert acc == np.add.reduce(flat)
     e = rng.random(w)
     assert lb.pairwise_sum(e, np.float64) == np.add.reduce(e)
 
 
-@pytest.mark.parametrize("shape", [(64, 128), (1, 8193), (96, 136), (270, 480), (33, 1000), (81, 100), (103, 155)])
+@pytest.mark.parametrize("shape", [(64, 128), (1, 8193), (96, 136), (270, 480), (33, 1000), (81, 100), (103, 155), (1025, 8190)])
 def test_whole_plane_mean_follows_numpys_reduction_buffers(shape):
     """Above 8192 elements numpy's y.mean() is not one pairwise sum: the plane goes through the 8192-element iteration buffer, a pairwise sum
-    per buffer and a running sum over the buffers."""
+    per buffer and a running sum over the buffers.  1025 x 8190 is 1025 buffers, the last one short: one more than the device's window of 1024."""
     assert np.getbufsize() == lb.NUMPY_BUFSIZE
     y = (np.random.default_rng(shape[1]).random(shape) * 255).astype(np.float32)
     assert lb.luma_mean_numpy(y) == y.mean()
@@ -107,6 +115,20 @@ def test_hsv_saturation_and_gray_known_values():
     assert abs(lb.hist_correlation(a, a) - 1.0) < 1e-12 and lb.hist_correlation(a, a[::-1]) < 0
 
 
+@pytest.mark.parametrize("hw", LC.CANNY_SIZES)
+def test_canny_tie_planes_decide_a_tie_in_each_direction(hw):
+    """The non-maximum test is > towards one neighbour and >= towards the other.  A plane whose edge map changes under a flip holds a tie that
+    this asymmetry decides: a kernel with the comparison on the wrong side cannot pass on it.  (Uniform noise, the dense-edge input of the
+    device test, gives an exactly mirror-symmetric map.)"""
+    g = LC.tie_plane(*hw)
+    e = lb.canny_numpy(g)
+    assert e.any() == (hw != (1, 1))
+    if hw[1] > 1:
+        assert (lb.canny_numpy(g[:, ::-1])[:, ::-1] != e).any(), "no left-right tie"
+    if hw[0] > 1:
+        assert (lb.canny_numpy(g[::-1])[::-1] != e).any(), "no up-down tie"
+
+
 # ---- tracker ---------------------------------------------------------------------------------------------------------------------------
 def test_bootstrap_enables_bars_at_confidence():
     boot, _ = LC.clip("three_cuts")
@@ -154,6 +176,94 @@ def test_cuts_do_not_invent_bars():
     assert set(r["bars"]) == {(0, 0)} and r["state"]["locked_zero"] == 1
     corr = [g["corr"] for g in r["gates"][-2:]]
     assert all(c is not None and c < lb.CORR_THRESH for c in corr), "the dimmed frame is a cut by the histogram test alone"
+
+
+def _run_of(ok):
+    """the rows from the top that pass the detector's row test"""
+    return int(np.argmin(ok)) if not ok.all() else len(ok)
+
+
+def test_every_new_clip_reaches_its_branch():
+    """A clip that misses the branch it was built for would pass every comparison vacuously: the evidence, on the statement's own run."""
+    run, cuts = LC.statement_run, LC.cuts
+    zero, bars = dict(locked_zero=1, locked_bars=0), dict(locked_zero=0, locked_bars=1)
+    has = lambda st, want: all(st[k] == v for k, v in want.items())
+
+    r = run("bars_appear")                       # locked_zero -> bars, exactly at the third cut
+    third = cuts("bars_appear")[2][0]
+    assert r["boot"] == (0, 0, (False, True)) and r["state"]["locked_bars"] == 1 and len(cuts("bars_appear")) == 3
+    assert r["bars"][:third] == [(0, 0)] * third and set(r["bars"][third:]) == {r["detect"][third]} != {(0, 0)}
+    assert has(r["states"][third - 1], zero) and has(r["states"][third], bars)
+
+    r = run("bars_vanish")                       # bars -> locked_zero, exactly at the third cut
+    third = cuts("bars_vanish")[2][0]
+    p = r["boot"][:2]
+    assert r["boot"][2] == (True, False) and p != (0, 0) and r["state"]["locked_zero"] == 1 and len(cuts("bars_vanish")) == 3
+    assert r["bars"][:third] == [p] * third and set(r["bars"][third:]) == {(0, 0)}
+    assert has(r["states"][third - 1], bars) and has(r["states"][third], zero)
+
+    r = run("over_cap")                          # bars inside the scan whose sum is above max_total count as (0, 0)
+    live = [i for i, cd in cuts("over_cap") if cd == 0]
+    max_total, scan = int(LC.H * 0.35), int(LC.H * lb.MAX_SCAN_FRAC)
+    assert len(live) >= 3
+    for i in live:
+        t, b = r["detect"][i]
+        assert t + b > max_total and 0 < t < scan and 0 < b < scan, (i, t, b)
+    assert (r["state"]["cand_top"], r["state"]["cand_bottom"]) == (0, 0) and r["state"]["streak"] == 3
+    assert r["boot"][2] == (True, False) and has(r["state"], zero), "the capped (0, 0) is what the three cuts agree on: the bars go"
+
+    r = run("thin_bars")                         # rows pass the row test, but fewer than min_band of them
+    min_band = int(LC.H * lb.MIN_BAND_FRAC)
+    assert len(cuts("thin_bars")) >= 3 and max(LC.BARS_THIN) < min_band
+    for i, _ in cuts("thin_bars"):
+        # every painted row but the last passes (the last one carries the Canny edge of the bar's border): a run of 1 .. min_band - 1 rows
+        top, bot = _run_of(r["row_ok"][i]), _run_of(r["row_ok"][i][::-1])
+        assert top == LC.BARS_THIN[0] - 1 and bot == LC.BARS_THIN[1] - 1 and 0 < top < min_band and 0 < bot < min_band, (i, top, bot)
+        assert r["detect"][i] == (0, 0)
+    assert set(r["bars"]) == {(0, 0)} and r["state"]["streak"] == 0 and r["boot"] == (0, 0, (False, True))
+
+    r = run("cooldown")                          # cuts with other bars while the cooldown of a switch runs: swallowed
+    swallowed = [i for i, cd in cuts("cooldown") if cd > 0]
+    assert len(swallowed) >= 1
+    for i in swallowed:
+        t, b = r["detect"][i]
+        assert abs(t - r["bars"][i][0]) + abs(b - r["bars"][i][1]) >= 8 and r["bars"][i] != r["boot"][:2], (i, t, b)
+        assert r["states"][i]["streak"] == r["states"][i - 1]["streak"] and r["states"][i]["cand_top"] == r["states"][i - 1]["cand_top"]
+    after = [i for i, cd in cuts("cooldown") if cd == 0 and i > swallowed[-1]]
+    assert after and r["states"][after[0]]["streak"] == 1 and (r["state"]["cand_top"], r["state"]["cand_bottom"]) == r["detect"][after[0]]
+
+    for name in ("size_switch", "size_switch_back"):   # the first frame of the other size is a cut without a MAD
+        r, (_, upd) = run(name), LC.clip(name)
+        sw = [i for i in range(1, len(upd)) if upd[i].shape != upd[i - 1].shape]
+        assert len(sw) == 1 and upd[0].shape[0] == LC.geometry(name)[0]
+        g = r["gates"][sw[0]]
+        assert g["mad"] is None and g["corr"] is None and not g["near_black"] and (sw[0], 0) in cuts(name)
+        assert r["states"][sw[0]]["streak"] == 1 and r["state"]["streak"] == 3 and r["bars"][-1] != r["boot"][:2]
+        assert [len(b) for b in LC.batches(upd)] == [sw[0], len(upd) - sw[0]] and max(len(b) for b in LC.batches(upd, 4)) == 4
+
+    r = run("small_frame")                       # H < 64: bars that the row test passes are refused all the same
+    assert LC.geometry("small_frame")[0] < 64 and len(cuts("small_frame")) >= 3 and all(cd == 0 for _, cd in cuts("small_frame"))
+    assert set(r["bars"]) == {(0, 0)} and set(r["detect"]) == {(0, 0)} and r["state"]["streak"] == 0
+    for i, _ in cuts("small_frame"):
+        top, bot = _run_of(r["row_ok"][i]), _run_of(r["row_ok"][i][::-1])
+        assert (top - top % 2) + (bot - bot % 2) >= 8 and min(top, bot) >= int(48 * lb.MIN_BAND_FRAC), "bars a taller frame would have counted"
+
+    r = run("tall_frame")                        # the near-black gate reads the edge mean: at H = 150 a tree of two leaves with a tail
+    leaves, comb = lb.pairwise_plan(LC.geometry("tall_frame")[0])
+    assert len(leaves) == 2 and len(comb) == 1 and leaves[-1][1] % 8 != 0
+    assert [g["near_black"] for g in r["gates"]].count(True) >= 1 and len(set(r["bars"])) == 2 and r["state"]["locked_bars"] == 1
+    # ... and one dark frame on which that sum decides: not near-black, so a cut that takes a streak of 2 back to 1 -- with any one of the
+    # tail's rows left out of the sum it would be skipped as near-black, and the next cut would be the third agreeing one
+    upd = LC.clip("tall_frame")[1]
+    d = [i for i, f in enumerate(upd) if np.array_equal(f, LC.dark_title())]
+    assert len(d) == 1 and (d[0], 0) in LC.cuts("tall_frame") and not r["gates"][d[0]]["near_black"]
+    st = lb.frame_stats_numpy(upd[d[0]])
+    e = lb.edge_density_from_counts(st["edge_counts"], st["w"])
+    tail = range(leaves[-1][0] + leaves[-1][1] - leaves[-1][1] % 8, len(e))
+    assert float(st["frame_mean"]) < lb.BLACK_MEAN and len(tail) == 6
+    assert lb._edge_mean(st) >= lb.BLACK_EDGE + 0.001 and all((e.sum() - e[i]) / len(e) < lb.BLACK_EDGE - 0.0002 for i in tail)
+    assert r["states"][d[0] - 1]["streak"] == 2 and r["states"][d[0]]["streak"] == 1 and r["detect"][d[0]] != r["detect"][d[0] + 1]
+    assert r["bars"].index(r["bars"][-1]) == LC.cuts("tall_frame")[-1][0] > d[0] + 1
 
 
 def _margins(name):
@@ -250,7 +360,8 @@ class _Cap:
 def _reference_run(name):
     ns, cv2 = _reference_namespace()
     head, upd = LC.source(name)
-    tr = ns["LetterboxTracker"](LC.H, LC.FPS)
+    h, _, fps = LC.geometry(name)
+    tr = ns["LetterboxTracker"](h, fps)
     t, b, locks = tr.bootstrap(_Cap(list(head), cv2))
     bars = [[int(v) for v in tr.update(f, i)] for i, f in enumerate(upd)]
     return dict(boot=[int(t), int(b), bool(locks[0]), bool(locks[1])], bars=bars)
