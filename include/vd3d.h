@@ -34,7 +34,7 @@ extern "C" {
  *    -DVD3D_DEV_KNOBS; aten_threads / aten_sum_threads accept 1 .. 1024.
  * 5 (round 5): vd3d_shift_params gained aten_threads / reserved0 at its end (vd3d_render_params embeds it: its later fields moved by 8 bytes); vd3d_torch_math_aten.
  * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
- * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32,
+ * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32, vd3d_attention_f32_form,
  *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs. */
 #define VD3D_ABI_VERSION 6
 
@@ -523,6 +523,10 @@ int vd3d_attention_x3(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int 
  * order and the exp implementation differ.  Same qkv / out layout as vd3d_attention_x3; no workspace.  VD3D_E_UNSUPPORTED for D != 64, an empty shape,
  * B * H > 65 535 or qkv / out not 16-byte aligned. */
 int vd3d_attention_f32(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int D, float scale, float* out);
+/* The same call with the kernel's form named: the workgroup's wave count, 8 (256 queries, one workgroup per CU) or 4 (128 queries, two per CU), or 0 = the
+ * library's choice, which is what vd3d_attention_f32 passes.  Per query both forms run the same operations in the same order: their results are bit-identical,
+ * the forms differ in speed only (tests, probes).  Any other form is VD3D_E_INVALID. */
+int vd3d_attention_f32_form(vd3d_ctx* ctx, const float* qkv, int B, int T, int H, int D, float scale, float* out, int form);
 
 /* The 3 x 3 convolutions of the DPT neck / head in the fp16x2 arithmetic (the third piece of DepthPipe(gemm="fp16x2")): stride 1, zero padding 1, no bias
  * (DepthPipe runs them bias-free with a glue launch behind each), float32 channels_last: X [B][H][W][Cin] -> Y [B][H][W][Cout], W the module's float32

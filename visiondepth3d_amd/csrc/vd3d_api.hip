@@ -1755,13 +1755,18 @@ VD3D_EXPORT int vd3d_attention_x3(vd3d_ctx* c, const float* qkv, int B, int T, i
   return 0;
 }
 
-VD3D_EXPORT int vd3d_attention_f32(vd3d_ctx* c, const float* qkv, int B, int T, int H, int D, float scale, float* out) {
+VD3D_EXPORT int vd3d_attention_f32_form(vd3d_ctx* c, const float* qkv, int B, int T, int H, int D, float scale, float* out, int form) {
   if (!c || !qkv || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (form != 0 && form != 4 && form != 8) return set_err(VD3D_E_INVALID, "attention_f32: form %d is not 0 (choose), 4 or 8 waves per workgroup", form);
   HIPCHK(hipSetDevice(c->device));
-  if (!vd_launch_attn_f32(c->stream, qkv, B, T, H, D, scale, out))
+  if (!vd_launch_attn_f32(c->stream, qkv, B, T, H, D, scale, out, form))
     return set_err(VD3D_E_UNSUPPORTED, "attention_f32: head size %d not built (64), an empty shape (B %d T %d H %d), B * H > 65535 or qkv / out not 16-byte aligned", D, B, T, H);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+VD3D_EXPORT int vd3d_attention_f32(vd3d_ctx* c, const float* qkv, int B, int T, int H, int D, float scale, float* out) {
+  return vd3d_attention_f32_form(c, qkv, B, T, H, D, scale, out, 0);
 }
 
 VD3D_EXPORT int64_t vd3d_gemm_x3_weight_bytes(int N, int K, int mode) { return (int64_t)vd_gemm_x3_weight_bytes(N, K, mode); }

@@ -333,7 +333,17 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
 // only when some lane's running maximum grew (alpha = exp2(0) = 1 exactly for the others).
 #define AF_TILE (AT_BK * AT_D * 4)   // 16 384 bytes: 64 rows x 256
 #define AF_STAGE (2 * AF_TILE)       // K + V
-#define AF_LDS (AT_NSTAGE * AF_STAGE)   // 98 304
+#define AF_LDS(NS) ((NS) * AF_STAGE)   // 98 304 (8 waves, three stages) / 65 536 (4 waves, two stages)
+// Two forms of one kernel, k_attn_f32<NW, NS>: NW waves (32 NW queries) per workgroup, a ring of NS stages.
+//   <8, 3>  256 queries, 96 KB: one workgroup per CU, two waves per SIMD held in step by one barrier per tile.
+//   <4, 2>  128 queries, 64 KB, __launch_bounds__(256, 2): TWO workgroups per CU, again two waves per SIMD but with independent barriers (the two are not forced
+//           into the softmax at the same moment), twice as many equal workgroups (the last, partly filled round of the grid leaves each SIMD's matrix pipe to one
+//           wave instead of idling half the CUs) and padding waves that skip their matrix work (below).  Tile it + 1 is issued at the top of iteration it into
+//           the stage tile it - 1 left and waited for (vmcnt(0)) in front of the barrier that ends the iteration: a tile has > 8 000 matrix-pipe cycles to
+//           land, one tile ahead is enough.  K/V are staged per 128 queries: ~4 bytes per matrix-pipe cycle and CU, a third of the ~12 B / cycle limit.
+// Per query both forms run the same operations in the same order (tiles ascending, the two S^T chains, masking, maximum, rescale, sum order, P V chain, division):
+// their results are bit-identical (tests/test_hip_attention_f32_forms.py).
+static_assert(2 * AF_LDS(2) <= 160 * 1024, "two 4-wave workgroups per CU");
 // The two matrix products of one tile, each reading its stage of the ring through a restrict pointer: inlined, the LDS reads carry alias-scope information
 // (one scope per product, kept when the compiler pairs reads), and the compiler's wait-count pass then does not put a conservative vmcnt(0) behind every
 // LDS-DMA in front of them -- the ring is ordered by the kernel's own counted waits and barriers.
@@ -371,9 +381,12 @@ VD_DEV void af_pv(const uint8_t* __restrict__ sv, const x3_f16 (&p)[2], int li, 
     }
 }
 
-__global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qkv, float* __restrict__ out, vd_at_args a) {
+template <int NW, int NS>
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_attn_f32(const float* __restrict__ qkv, float* __restrict__ out, vd_at_args a) {
+  static_assert((NW == 8 && NS == 3) || (NW == 4 && NS == 2), "built forms");
+  constexpr int NP = 16 / NW;   // DMA passes per thread and operand tile: 1 024 sixteen-byte chunks over NW * 64 threads
   extern __shared__ __attribute__((aligned(16))) uint8_t at_lds[];
-  int bh, qb;   // (b, h) grouped by XCD as in k_attn_bf16x3: the workgroups of one (b, h) read the same K / V rows
+  int bh, qb;   // (b, h) grouped by XCD as in k_attn_bf16x3: the workgroups of one (b, h) read the same K / V rows (and are consecutive in dispatch order on their XCD)
   {
     const int wg = blockIdx.x, x = wg & 7, idx = wg >> 3;
     const int g = idx / a.nqb;
@@ -383,40 +396,47 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, kh = lane >> 5;
-  const int q0 = qb * AT_BQ + wave * 32;
+  const int q0 = qb * (NW * 32) + wave * 32;
+  // 4-wave form: a wave whose 32 queries are all past T (padding of the last workgroup) does its share of the DMA and reaches every barrier, and nothing else:
+  // its SIMD's matrix pipe is left to the co-resident workgroup's wave.  Wave-uniform (q0 is).  The 8-wave form computes them as it always did.
+  const bool live = NW == 8 || q0 < a.T;
   const int b = bh / a.H, h = bh - b * a.H;
   const size_t tok_stride = (size_t)3 * a.H * AT_D;
   const float* base = qkv + (size_t)b * a.T * tok_stride + h * AT_D;   // q of token t at base + t tok_stride, k at + H 64, v at + 2 H 64
 
-  // one tile's DMA: thread tid fills LDS chunks tid and tid + 512 of the K and of the V image = rows tid / 16 and + 32, chunk position tid & 15
+  // one tile's DMA: thread tid fills LDS chunks tid + 64 NW p (p < NP) of the K and of the V image = rows tid / 16 + 4 NW p, chunk position tid & 15 (4 NW is a
+  // multiple of 16: the K swizzle of a thread is the same in every pass)
   const int drow = tid >> 4, dpos = tid & 15, kchunk = dpos ^ (drow & 15);
   auto dma = [&](int tile, int stage) {
     uint8_t* dst = at_lds + stage * AF_STAGE + wave * 1024;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int tok = min(tile * AT_BK + drow + 32 * p, a.T - 1);
+    for (int p = 0; p < NP; ++p) {
+      const int tok = min(tile * AT_BK + drow + 4 * NW * p, a.T - 1);
       const float* src = base + (size_t)tok * tok_stride + a.H * AT_D;
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + kchunk * 4), (x3_lds_vp)(dst + p * 8192), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + a.H * AT_D + dpos * 4), (x3_lds_vp)(dst + AF_TILE + p * 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + kchunk * 4), (x3_lds_vp)(dst + p * (NW * 1024)), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + a.H * AT_D + dpos * 4), (x3_lds_vp)(dst + AF_TILE + p * (NW * 1024)), 16, 0, 0);
     }
   };
 
   // Q of the wave's 32 queries (rows past T read row T - 1 and are never stored), pre-scaled by scale * log2 e
   float qf[32];
-  {
+  if (live) {
     const float4* qp = reinterpret_cast<const float4*>(base + (size_t)min(q0 + li, a.T - 1) * tok_stride + 32 * kh);
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       const float4 v = qp[g];
       qf[4 * g] = v.x * a.c; qf[4 * g + 1] = v.y * a.c; qf[4 * g + 2] = v.z * a.c; qf[4 * g + 3] = v.w * a.c;
     }
+  } else {
+#pragma unroll
+    for (int g = 0; g < 32; ++g) qf[g] = 0.f;
   }
   dma(0, 0);
-  if (a.nkv > 1) {
+  if (NS == 3 && a.nkv > 1) {
     dma(1, 1);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // tile 0 (and Q) landed, tile 1 in flight
   } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // two stages: tile 1 is iteration 0's to issue, whatever nkv is
   }
   __builtin_amdgcn_s_barrier();
 
@@ -428,50 +448,53 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
   float m_run = -INFINITY, l_half = 0.f;
   int cur = 0;
   for (int it = 0; it < a.nkv; ++it) {
-    const bool ahead = it + 2 < a.nkv;
-    if (ahead) dma(it + 2, cur == 0 ? 2 : cur - 1);
+    const bool ahead = it + (NS - 1) < a.nkv;
+    if (NS == 3) { if (ahead) dma(it + 2, cur == 0 ? 2 : cur - 1); }
+    else { if (ahead) dma(it + 1, cur ^ 1); }   // the stage tile it - 1 left: every wave's reads of it returned before the barrier that ended iteration it - 1
     const uint8_t* sk = at_lds + cur * AF_STAGE;
     const uint8_t* sv = sk + AF_TILE;
-    // ---- S^T = K Q^T (pre-scaled logits)
-    x3_f16 s[2];
-    af_st(sk, qf, li, kh, s);
-    if ((it + 1) * AT_BK > a.T) {   // last tile: rows past T (a uniform branch off the hot path)
+    if (live) {
+      // ---- S^T = K Q^T (pre-scaled logits)
+      x3_f16 s[2];
+      af_st(sk, qf, li, kh, s);
+      if ((it + 1) * AT_BK > a.T) {   // last tile: rows past T (a uniform branch off the hot path)
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (it * AT_BK + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh >= a.T) s[m][r] = -INFINITY;
+      }
+      // ---- online softmax: running maximum over both lane halves, rescale only when it grew somewhere in the wave
+      float mx = s[0][0];
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (it * AT_BK + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh >= a.T) s[m][r] = -INFINITY;
+        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[m][r]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float m_new = fmaxf(m_run, mx);
+      if (__any(m_new > m_run)) {
+        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // 0 on the first tile (m_run = -inf), exactly 1 where the maximum did not grow
+#pragma unroll
+        for (int dm = 0; dm < 2; ++dm)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) oacc[dm][r] *= alpha;
+        l_half *= alpha;
+        m_run = m_new;
+      }
+      float ps = 0.f;
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { s[m][r] = __builtin_amdgcn_exp2f(s[m][r] - m_run); ps += s[m][r]; }
+      l_half += ps;
+      // ---- O^T += V^T P^T
+      af_pv(sv, s, li, kh, oacc);
     }
-    // ---- online softmax: running maximum over both lane halves, rescale only when it grew somewhere in the wave
-    float mx = s[0][0];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[m][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    if (__any(m_new > m_run)) {
-      const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // 0 on the first tile (m_run = -inf), exactly 1 where the maximum did not grow
-#pragma unroll
-      for (int dm = 0; dm < 2; ++dm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[dm][r] *= alpha;
-      l_half *= alpha;
-      m_run = m_new;
-    }
-    float ps = 0.f;
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s[m][r] = __builtin_amdgcn_exp2f(s[m][r] - m_run); ps += s[m][r]; }
-    l_half += ps;
-    // ---- O^T += V^T P^T
-    af_pv(sv, s, li, kh, oacc);
-    // before the barrier: this wave's reads of stage cur have returned (behind it, iteration it + 1's DMA of tile it + 3 overwrites that stage) and tile it + 1
-    // has landed (the four DMA instructions of tile it + 2 may stay in flight)
-    if (ahead) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    // before the barrier: this wave's reads of stage cur have returned (behind it, the next iteration's DMA overwrites that stage: tile it + 3 / it + 2) and
+    // tile it + 1 has landed (three stages: the four DMA instructions of tile it + 2 may stay in flight; two stages: tile it + 1 is the only one in flight)
+    if (NS == 3 && ahead) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    cur = cur == 2 ? 0 : cur + 1;
+    cur = NS == 3 ? (cur == 2 ? 0 : cur + 1) : cur ^ 1;
   }
 
   // ---- epilogue: out[b][q][h][16 g + 8 kh + 2 j + dm] = O^T_dm[register 4 g + j] / l
@@ -489,18 +512,34 @@ __global__ __launch_bounds__(AT_NT) void k_attn_f32(const float* __restrict__ qk
   }
 }
 
-bool vd_launch_attn_f32(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, float* out) {
-  if (B < 1 || T < 1 || H < 1 || D != AT_D || (long long)B * H > 65535) return false;
-  if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return false;
+template <int NW, int NS>
+static bool af_launch(hipStream_t s, const float* qkv, float* out, vd_at_args a) {
   static bool attr_set[64] = {};
-  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_attn_f32), AF_LDS}}, attr_set)) return false;   // per device (vd3d_kernels.h)
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_attn_f32<NW, NS>), AF_LDS(NS)}}, attr_set)) return false;   // per device (vd3d_kernels.h)
+  a.nqb = (a.T + NW * 32 - 1) / (NW * 32);
+  const int groups = (a.B * a.H + 7) / 8;
+  hipLaunchKernelGGL((k_attn_f32<NW, NS>), dim3((unsigned)(8 * groups * a.nqb)), dim3(NW * 64), AF_LDS(NS), s, qkv, out, a);
+  return true;
+}
+
+// form: 8 / 4 = the workgroup's wave count, 0 = the library's choice.
+// Form 0, from profiles/r15_attn_f32_forms.md (MI355X, 256 CUs): the 4-wave form where the 8-wave grid is at least four rounds of the chip (1 024 workgroups),
+// the 8-wave form below that.  Grounds: alone, the 4-wave form is faster wherever the 8-wave grid ends in a short round (16 x 2 443 x 12: 7.5 rounds, 2.55 ->
+// 2.44 ms; 16 x 1 370 x 6: 2.25 rounds, 0.552 -> 0.470 ms) and level where it does not (16 x 2 443 x 16: 10 rounds); no shape was found where it is slower alone.
+// Inside the depth + DIBR step the long grid keeps most of that (4K DA-V2-Base: 113.31 -> 112.30 ms per step, 4.4 x the spread), the short one does not: at
+// 1080p DA-V2-Small the attention shares the chip with the pixel kernels of the other streams for its whole length (1.33 ms per call in the step against 0.55
+// alone) and the step came out 0.4 % SLOWER with the 4-wave form (381.0 -> 379.5 pairs/s, three alternating runs each, 1.9 x the spread).  Nothing was measured
+// between 576 and 1 920 workgroups: the threshold is the round number in between, not a measured crossover.
+bool vd_launch_attn_f32(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, float* out, int form) {
+  if (B < 1 || T < 1 || H < 1 || D != AT_D || (long long)B * H > 65535) return false;
+  if (form != 0 && form != 4 && form != 8) return false;
+  if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return false;
   vd_at_args a;
   a.B = B; a.H = H; a.T = T;
-  a.nq32 = (T + 31) / 32; a.nkv = (T + AT_BK - 1) / AT_BK; a.nqb = (T + AT_BQ - 1) / AT_BQ;
+  a.nq32 = (T + 31) / 32; a.nkv = (T + AT_BK - 1) / AT_BK; a.nqb = 0;
   a.c = scale * 1.44269504088896340736f;
-  const int groups = (B * H + 7) / 8;
-  hipLaunchKernelGGL(k_attn_f32, dim3((unsigned)(8 * groups * a.nqb)), dim3(AT_NT), AF_LDS, s, qkv, out, a);
-  return true;
+  if (form == 0) form = 8LL * ((B * H + 7) / 8) * ((T + AT_BQ - 1) / AT_BQ) >= 1024 ? 4 : 8;
+  return form == 4 ? af_launch<4, 2>(s, qkv, out, a) : af_launch<8, 3>(s, qkv, out, a);
 }
 
 static bool at_mode_ok(int mode) { return mode == 0 || mode == 1; }

@@ -257,7 +257,7 @@ void vd_launch_rife_blend(hipStream_t s, const float* X, const float* S, int N, 
 long long vd_attn_x3_workspace_bytes(int B, int T, int H, int D, int mode);
 bool vd_launch_attn_x3(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, void* ws, float* out, int mode);
 // ... and in exact float32 (v_mfma_f32_32x32x2_f32, no workspace)
-bool vd_launch_attn_f32(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, float* out);
+bool vd_launch_attn_f32(hipStream_t s, const float* qkv, int B, int T, int H, int D, float scale, float* out, int form);   // form 0 = choose, 4, 8 waves per workgroup
 bool vd_launch_add_layernorm(hipStream_t s, int dtype, const void* x, const void* y, const void* gamma, const void* beta, float eps,
                              long long rows, int cols, void* out_sum, void* out_norm);
 bool vd_launch_upsample_bilinear_nhwc(hipStream_t s, int dtype, const void* in, void* out, int B, int ih, int iw, int oh, int ow, int C);

@@ -867,9 +867,10 @@ class Renderer:
         _lib.check(self._L.vd3d_attention_x3(self._ctx, _ptr(qkv), B, T, n_heads, D, float(scale), m, _ptr(ws), ws.numel(), _ptr(out)))
         return out
 
-    def attention_f32(self, qkv: torch.Tensor, n_heads: int, scale: float) -> torch.Tensor:
+    def attention_f32(self, qkv: torch.Tensor, n_heads: int, scale: float, form: int = 0) -> torch.Tensor:
         """softmax(q k^T * scale) v for the contiguous float32 output ``qkv`` [B, T, 3 * H * 64] of a fused QKV linear -> [B, T, H * 64] float32, in exact
-        float32: both products on the float32-input matrix cores, float32 online softmax (include/vd3d.h vd3d_attention_f32).  No workspace."""
+        float32: both products on the float32-input matrix cores, float32 online softmax (include/vd3d.h vd3d_attention_f32).  No workspace.
+        ``form``: waves per workgroup, 4 or 8, or 0 = the library's choice (vd3d_attention_f32_form; the same bits either way)."""
         B, T, C3 = qkv.shape
         D = C3 // (3 * n_heads)
         if qkv.dtype != torch.float32 or not qkv.is_contiguous() or D * 3 * n_heads != C3:
@@ -878,7 +879,7 @@ class Renderer:
             raise NotImplementedError(f"attention_f32: head size {D} not built")
         out = torch.empty((B, T, n_heads * D), dtype=torch.float32, device=self.device)
         self._enter(qkv, out)
-        _lib.check(self._L.vd3d_attention_f32(self._ctx, _ptr(qkv), B, T, n_heads, D, float(scale), _ptr(out)))
+        _lib.check(self._L.vd3d_attention_f32_form(self._ctx, _ptr(qkv), B, T, n_heads, D, float(scale), _ptr(out), int(form)))
         return out
 
     def conv3x3_x2_pack(self, weight: torch.Tensor):
