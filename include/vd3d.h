@@ -35,7 +35,8 @@ extern "C" {
  * 5 (round 5): vd3d_shift_params gained aten_threads / reserved0 at its end (vd3d_render_params embeds it: its later fields moved by 8 bytes); vd3d_torch_math_aten.
  * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
  * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32, vd3d_attention_f32_form,
- *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs. */
+ *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs, vd3d_conv3x3_s2_x3_weight_bytes,
+ *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -548,6 +549,20 @@ int vd3d_conv3x3_x2(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin,
 int64_t vd3d_conv3x3_x3_weight_bytes(int Cin, int Cout);
 int vd3d_conv3x3_x3_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
 int vd3d_conv3x3_x3(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
+/* The stride-2 form for wide maps -- the reassemble stage's Conv2d(C, C, 3, stride 2, padding 1) of the DINOv2 depth models (C = 384 / 768 / 1024), the
+ * convolution DepthPipe(self_contained=True) adds: no bias, groups 1, the same bf16x3 arithmetic (exact three-term truncation split, the six products above,
+ * x1 w1 in one float32 accumulator and the five corrections in another, summed once), float32 NHWC in and out: X [B][H][W][Cin] -> Y [B][(H+1)/2][(W+1)/2][Cout],
+ * W the module's float32 weight [Cout][Cin][3][3].  The kernel runs the space-to-depth view of the input and no tap on a zero weight, so a NaN / Inf input
+ * pixel gives NaN in exactly the outputs whose 3 x 3 window holds it.  One fixed summation order per output (16-channel chunk, sub-pixel, tap; no split-K, no
+ * atomics): bit-for-bit repeatable and independent of B.  128 output channels per workgroup; Cout = 128 n runs as n channel slices of the grid.
+ * Cin a positive multiple of 16 (at most 65 536), Cout a positive multiple of 128 (at most 1024), H, W >= 1, 1 <= B <= 65 535, X and the image 16-byte aligned
+ * (Y 4-byte); anything else is VD3D_E_UNSUPPORTED with a message that names the rule, and nothing is launched.  The weights are split and packed once into
+ * vd3d_conv3x3_s2_x3_weight_bytes(Cin, Cout) bytes (host-only; < 0: shape not built): per slice, per 16 input channels, the K steps in the order a workgroup
+ * runs them -- sub-pixel (0,0): tap (1,1); (0,1): (1,0), (1,2); (1,0): (0,1), (2,1); (1,1): (0,0), (0,2), (2,0), (2,2) -- then a 64-byte zero page.  The image
+ * is opaque, differs from vd3d_conv3x3_x3's and is only valid for this library version. */
+int64_t vd3d_conv3x3_s2_x3_weight_bytes(int Cin, int Cout);
+int vd3d_conv3x3_s2_x3_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
+int vd3d_conv3x3_s2_x3(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
 
 /* The convolutions of the RIFE interpolation network (IFNet HDv3; RifeSession(conv="bf16x3")) in the same bf16x3 arithmetic: exact three-term truncation
  * split of every float32 operand, the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 into one float32 accumulator and x1 w1 into another, summed in the epilogue
@@ -621,6 +636,14 @@ int vd3d_dpt_head_conv_f32(vd3d_ctx* ctx, const float* x, const float* b_in, int
  *   out[b][y*s + i][x*s + j][c] = y[(b*H + y)*W + x][i][j][c] + bias[c]   (an exact copy and one float32 add; bias_or_null == NULL: the copy alone).
  * C a multiple of 4 and y / bias / out 16-byte aligned, else VD3D_E_UNSUPPORTED. */
 int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* ctx, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out);
+
+/* The gather half of a ViT patch embedding (Conv2d(3, C, kernel_size=p, stride=p): kernel == stride, every patch is one GEMM row) for
+ * DepthPipe(self_contained=True): x float32 NHWC [B][th][tw][3] (what vd3d_depth_preprocess writes) -> rows float32 [B * gh * gw][Kp], gh = th / p, gw = tw / p
+ * (a remainder is dropped, as the convolution drops it), Kp = 3 p^2 rounded up to a multiple of 16 (p = 14: 588 -> 592),
+ *   rows[(b * gh + gy) * gw + gx][(c * p + ky) * p + kx] = x[b][gy * p + ky][gx * p + kx][c]   (exact copies, F.unfold's column order);
+ * the columns from 3 p^2 on are written as zeros.  vd3d_gemm_x3 on the weight [C][3 p^2] zero-padded to Kp, with the bias, then gives the patch tokens
+ * [B][gh * gw][C].  1 <= p <= 64, th, tw >= p, B >= 1, rows 16-byte aligned (x 4-byte), else VD3D_E_UNSUPPORTED and nothing is launched. */
+int vd3d_patchify_f32(vd3d_ctx* ctx, const float* x, int B, int th, int tw, int p, float* rows);
 
 /* ---- preview visualisers: generate_preview_image, core/preview_utils.py:23-84, the exactly defined types.
  * left / right: uint8 BGR [h][w][3] eyes (outputs of vd3d_pixel_shift).  out: [h][w][3], except HSBS: [h][2*(w/2)][3].

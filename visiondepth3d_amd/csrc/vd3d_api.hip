@@ -1651,6 +1651,37 @@ VD3D_EXPORT int vd3d_conv3x3_x3(vd3d_ctx* c, const float* X, int B, int H, int W
   return 0;
 }
 
+// the stride-2 form for the reassemble stage's wide maps (vd3d_conv_s2.hip): the same rules, C_out in multiples of 128
+VD3D_EXPORT int64_t vd3d_conv3x3_s2_x3_weight_bytes(int Cin, int Cout) { return (int64_t)vd_conv3x3_s2_x3_weight_bytes(Cin, Cout); }
+
+static int conv3x3_s2_x3_shape_err(int Cin, int Cout) {
+  return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: shape not built: C_in %d must be a positive multiple of 16 (at most 65536) and C_out %d a positive multiple of 128 (at most 1024)",
+                 Cin, Cout);
+}
+
+VD3D_EXPORT int vd3d_conv3x3_s2_x3_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
+  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  if (vd_conv3x3_s2_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_s2_x3_shape_err(Cin, Cout);
+  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: the weight image must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_conv3x3_s2_x3_pack(c->stream, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "conv3x3_s2_x3: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_conv3x3_s2_x3(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
+  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
+  if (vd_conv3x3_s2_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_s2_x3_shape_err(Cin, Cout);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: batch %d must be 1 .. 65535 (one grid row per frame)", B);
+  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: map %d x %d must be at least 1 x 1", H, W);
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: the input and the weight image must be 16-byte aligned (the output 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_conv3x3_s2_x3(c->stream, X, B, H, W, Cin, w_image, Cout, Y)) return set_err(VD3D_E_HIP, "conv3x3_s2_x3: the dynamic LDS opt-in or the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // the convolutions of the interpolation network (vd3d_conv_ifn.hip): every rule of include/vd3d.h is checked here, before anything is launched
 VD3D_EXPORT int64_t vd3d_conv_ifn_weight_bytes(int kind, int Cin, int Cout) { return (int64_t)vd_conv_ifn_weight_bytes(kind, Cin, Cout); }
 
@@ -1856,6 +1887,17 @@ VD3D_EXPORT int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* c, const float* y, c
   HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_depth_to_space_bias_f32(c->stream, y, bias_or_null, B, H, W, s, C, out))
     return set_err(VD3D_E_UNSUPPORTED, "depth_to_space_bias: C %d not a multiple of 4, y / bias / out not 16-byte aligned, or a map too large for one grid", C);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_patchify_f32(vd3d_ctx* c, const float* x, int B, int th, int tw, int p, float* out) {
+  if (!c || !x || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || p < 1 || p > 64 || th < p || tw < p)
+    return set_err(VD3D_E_UNSUPPORTED, "patchify: batch %d must be at least 1, the patch size %d 1 .. 64 and the image %d x %d at least one patch", B, p, th, tw);
+  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(out) & 15))
+    return set_err(VD3D_E_UNSUPPORTED, "patchify: the rows must be 16-byte aligned (the image 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_patchify_f32(c->stream, x, B, th, tw, p, out)) return set_err(VD3D_E_UNSUPPORTED, "patchify: too many rows for one grid");
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -1,7 +1,9 @@
-// vd3d_conv_x3.hip -- the tile convolution in the bf16x3 arithmetic (vd3d_x3.h): ONE kernel behind two entry points,
+// vd3d_conv_x3.hip -- the tile convolution in the bf16x3 arithmetic (vd3d_x3.h): ONE kernel (k_conv_x3, vd3d_conv_x3.h) behind two entry points here,
 //   vd3d_conv3x3_x3  the 3 x 3 convolutions of the DPT neck / fusion stage / head (stride 1, zero padding 1, no bias; C_out 32 / 64 / 128 / 256), and
 //   vd3d_conv_ifn    the convolutions of the RIFE interpolation network (IFNet HDv3: three IFBlocks of 14; C_out 32 / 64 / 96; bias, per-channel PReLU and
 //                    residual in the epilogue, channel slices of strided NHWC buffers).
+// and a third one, vd3d_conv3x3_s2_x3 (the reassemble stage's 3 x 3 stride-2 convolution, C_out = 128 n), whose launch is vd3d_conv_s2.hip's and whose weight
+// image is packed here.
 // Arithmetic: every float32 operand is split EXACTLY into three bf16 terms by truncation (x3_split); the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 go into a `lo`
 // accumulator and x1 w1 into `acc` (v_mfma_f32_32x32x16_bf16, float32 accumulation, small products first), summed in the epilogue; x2 w3, x3 w2, x3 w3 <= 2^-24
 // relative are dropped, as in the GEMM.  Float32 NHWC in and out, no weight pre-scaling, no range limit, NaN / Inf in gives NaN out.
@@ -35,215 +37,14 @@
 // Epilogue (float32).  vd3d_conv_ifn (EPI): y = acc + lo + bias[oc]; y = y >= 0 ? y : slope[oc] * y (slope == nullptr: none); y += R[pixel][oc] (R == nullptr:
 // none).  vd3d_conv3x3_x3: y = acc + lo, nothing else (a bias-free convolution adds no zero either: -0 + 0 is +0).
 #include "vd3d_dev.h"
-#include "vd3d_kernels.h"
-#include "vd3d_x3.h"
+#include "vd3d_conv_x3.h"
 
-#define CX_TH 8
-#define CX_TW 32
-#define CX_PH (CX_TH + 2)
-#define CX_PW (CX_TW + 2)
-#define CX_NPIX (CX_PH * CX_PW)                       // 340
-#define CX_NT 512
-#define CX_NS 4                                       // weight ring stages
-#define CX_PLANE (CX_NPIX * 16)                       // one (term, k-half) plane: 5 440 bytes
-#define CX_A_BUF (3 * 2 * CX_PLANE)                   // one chunk image: 32 640 bytes
-#define CX_A_ITEMS (CX_NPIX * 4)                      // (pixel, 4-channel quad) items of a chunk: 1 360
-#define CX_A_ITERS ((CX_A_ITEMS + CX_NT - 1) / CX_NT) // 3 per thread
-#define CX_A_STG (CX_A_ITERS * CX_NT * 16)            // float32 staging buffer of one chunk, item-linear (what a DMA instruction can write): 24 576 bytes
-__host__ __device__ constexpr int cx_b_stage(int ck) { return (3 * 2 * ck * 16 + 8191) / 8192 * 8192; }   // 8 192 (32, 64), 16 384 (96, 128)
-#define CX_B_OFF (2 * CX_A_BUF + CX_A_STG)
-__host__ __device__ constexpr int cx_lds(int ck) { return CX_B_OFF + CX_NS * cx_b_stage(ck); }
 #define CX_LDS_MAX 155392                             // the largest dynamic LDS request of any instantiation (CK 96, 128); a workgroup can have 163 840
 static_assert(cx_lds(128) == CX_LDS_MAX && cx_lds(96) == CX_LDS_MAX && cx_lds(64) <= CX_LDS_MAX && cx_lds(32) <= CX_LDS_MAX && CX_LDS_MAX <= 163840, "LDS plan");
 
-enum { CX_K3S1 = 0, CX_K3S2 = 1, CX_T4S2 = 2 };   // include/vd3d.h VD3D_IFN_*
-
-struct vd_cx_args {
-  const float* X; const uint8_t* Wimg; const float* zero16; const float* bias; const float* slope; const float* R; float* Y;
-  int B, H, W;              // the input map
-  int Ho, Wo;               // the output map
-  int x_stride, y_stride, y_offset, r_stride;
-  int ntx;                  // tiles per row of the tile grid
-  int nchunk;               // C_in / 16
-};
-
-// EPI: the two entry points' thin variants of the one body.  true (vd3d_conv_ifn): + bias (never null there), optional slope and residual, at most 96 output
-// channels.  false (vd3d_conv3x3_x3, K3S1 only): the bare sum -- nothing is added, not even a zero -- and the channel slices of C_out 256.
-template <int KIND, int WM, int NWN, bool EPI>
-__global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
-  constexpr int NS = CX_NS, WN = 8 / WM, MR = CX_TH / WM, CK = 32 * WN * NWN, BST = cx_b_stage(CK), NBP = BST / (CX_NT * 16), B_ITEMS = 6 * CK;
-  constexpr int A_FLY = NS - 2;   // the taps of a chunk whose counted wait leaves the next chunk's pixel DMAs in flight
-  constexpr int SUBS = KIND == CX_K3S2 ? 4 : 1, ST = KIND == CX_K3S2 ? 2 : 1;
-  extern __shared__ __attribute__((aligned(16))) uint8_t cx_smem[];   // the only LDS object: [A buffer 0][A buffer 1][float32 staging][B ring]
-  const int tile = blockIdx.x, b = blockIdx.y;
-  // blockIdx.z is the weight slice of the workgroup: the output phase 2 p_y + p_x for T4S2, the CK-channel slice of C_out for K3S1 without EPI (0 or 1: C_out
-  // 256); otherwise the grid has one z plane and it is not read
-  constexpr bool SLICED = KIND == CX_T4S2 || !EPI;
-  const unsigned slice = SLICED ? blockIdx.z : 0u;
-  const int ph_y = KIND == CX_T4S2 ? (int)(slice >> 1) : 0, ph_x = KIND == CX_T4S2 ? (int)(slice & 1) : 0, oc0 = KIND == CX_T4S2 ? 0 : (int)slice * CK;
-  const int tyi = tile / a.ntx, txi = tile - tyi * a.ntx;
-  const int y0 = tyi * CX_TH, x0 = txi * CX_TW;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave - wm * WN, li = lane & 31, kh = lane >> 5;
-  const int wave_base = (tid & ~63) * 16;
-
-  // ---- A staging: item i = it * 512 + tid -> (pixel = i >> 2 of the 10 x 34 halo tile, quad = i & 3 = four of the chunk's 16 channels); the DMA of item i lands
-  // in staging slot i.  A pixel outside the image (zero padding) or an item past the tile fetches the 64 zero bytes behind the weight image.
-  int aty[CX_A_ITERS], atx[CX_A_ITERS], adst[CX_A_ITERS];
-  const int q4 = tid & 3;
-#pragma unroll
-  for (int it = 0; it < CX_A_ITERS; ++it) {
-    const int i = it * CX_NT + tid, pix = i >> 2;
-    const int py = pix / CX_PW, px = pix - py * CX_PW;
-    aty[it] = i < CX_A_ITEMS ? y0 - 1 + py : -(1 << 28);   // an item past the tile is "above the image"
-    atx[it] = x0 - 1 + px;
-    adst[it] = i < CX_A_ITEMS ? ((q4 >> 1) * CX_NPIX + pix) * 16 + (q4 & 1) * 8 : -1;   // + term * 2 * CX_PLANE
-  }
-  const float* xb = a.X + (size_t)b * a.H * a.W * a.x_stride + q4 * 4;
-  auto load_a = [&](int chunk) {   // chunk = c16 * SUBS + (sy * 2 + sx)
-    const int c16 = chunk / SUBS, sy = KIND == CX_K3S2 ? (chunk >> 1) & 1 : 0, sx = KIND == CX_K3S2 ? chunk & 1 : 0;
-#pragma unroll
-    for (int it = 0; it < CX_A_ITERS; ++it) {
-      const int gy = ST * aty[it] + sy, gx = ST * atx[it] + sx;
-      const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-      const float* p = in ? xb + ((size_t)gy * a.W + gx) * a.x_stride + c16 * 16 : a.zero16;
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)p, (x3_lds_vp)(cx_smem + 2 * CX_A_BUF + it * (CX_NT * 16) + wave_base), 16, 0, 0);
-    }
-  };
-  auto write_a = [&](int buf) {   // staging (float32) -> exact three-term split -> three 8-byte LDS stores per item
-    uint8_t* dst = cx_smem + buf * CX_A_BUF;
-    const uint8_t* stg = cx_smem + 2 * CX_A_BUF + tid * 16;
-#pragma unroll
-    for (int it = 0; it < CX_A_ITERS; ++it) {
-      const x3_s8 raw = *reinterpret_cast<const x3_s8*>(stg + it * (CX_NT * 16));   // a short vector, bit-cast: not ordered behind the DMAs in flight (vd3d_x3.h)
-      const float4 f = __builtin_bit_cast(float4, raw);
-      uint32_t t1[4], t2[4], t3[4];
-      x3_split(f.x, t1[0], t2[0], t3[0]); x3_split(f.y, t1[1], t2[1], t3[1]); x3_split(f.z, t1[2], t2[2], t3[2]); x3_split(f.w, t1[3], t2[3], t3[3]);
-      if (adst[it] >= 0) {
-        *reinterpret_cast<x3_u2*>(dst + adst[it]) = x3_u2{x3_pack(t1[0], t1[1]), x3_pack(t1[2], t1[3])};
-        *reinterpret_cast<x3_u2*>(dst + 2 * CX_PLANE + adst[it]) = x3_u2{x3_pack(t2[0], t2[1]), x3_pack(t2[2], t2[3])};
-        *reinterpret_cast<x3_u2*>(dst + 4 * CX_PLANE + adst[it]) = x3_u2{x3_pack(t3[0], t3[1]), x3_pack(t3[2], t3[3])};
-      }
-    }
-  };
-  // ---- B staging: the slice's K steps are contiguous in the packed image, [step][term 3][k-half 2][oc CK][8 bf16]; item i = p * 512 + tid is 16 bytes of a
-  // step; the items behind the step's 96 CK bytes read the zero page
-  const int NCH = a.nchunk * SUBS;
-  const int KS = KIND == CX_T4S2 ? a.nchunk * 4 : a.nchunk * 9;
-  const size_t bstep = (size_t)CK * 96;
-  const uint8_t* wbase = a.Wimg + (SLICED ? (size_t)slice * KS * bstep : (size_t)0);
-  auto stage_b = [&](int ks, int slot) {
-#pragma unroll
-    for (int p = 0; p < NBP; ++p) {
-      const int i = p * CX_NT + tid;
-      const uint8_t* src = i < B_ITEMS ? wbase + (size_t)ks * bstep + i * 16 : reinterpret_cast<const uint8_t*>(a.zero16);
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)src, (x3_lds_vp)(cx_smem + CX_B_OFF + slot * BST + p * (CX_NT * 16) + wave_base), 16, 0, 0);
-    }
-  };
-
-  // Two accumulators per tile: x1 w1 in `acc`, the five correction products (<= 2^-7 of it) in `lo`, summed in the epilogue.  One float32 rounding at the
-  // running sum's magnitude per K step instead of six: with a single accumulator the 1024-channel neck convolution (55 296 MFMA adds per output) measured a
-  // relative RMS error 1.8 x that of a float32 CPU convolution, outside the bar of tests/test_hip_conv_x3.py.
-  x3_f16 acc[MR][NWN], lo[MR][NWN];
-#pragma unroll
-  for (int m = 0; m < MR; ++m)
-#pragma unroll
-    for (int n = 0; n < NWN; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[m][n][r] = lo[m][n][r] = 0.f;
-
-  load_a(0);
-#pragma unroll
-  for (int st = 0; st < NS - 1; ++st) stage_b(st < KS ? st : KS - 1, st);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the prologue waits for everything; a thread converts only the staging slots its OWN DMA lanes filled
-  write_a(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-
-  // fragment base offsets: A: k-half plane, tile row MR wm + m (+ 1 halo + dy), column li (+ 1 + dx); B: k-half plane, output channel (wn * NWN + n) * 32 + li
-  const int fa_base = (kh * CX_NPIX + (MR * wm + 1) * CX_PW + li + 1) * 16;
-  const int fb_base = CX_B_OFF + (kh * CK + wn * NWN * 32 + li) * 16;
-  int ks = 0;
-  for (int chunk = 0; chunk < NCH; ++chunk) {
-    const bool more_a = chunk + 1 < NCH;   // uniform
-    if (more_a) load_a(chunk + 1);
-    const uint8_t* sa = cx_smem + (chunk & 1) * CX_A_BUF;
-    const int sy = KIND == CX_K3S2 ? (chunk >> 1) & 1 : 0, sx = KIND == CX_K3S2 ? chunk & 1 : 0;
-    const int T = KIND == CX_K3S1 ? 9 : KIND == CX_T4S2 ? 4 : (1 + sy) * (1 + sx);
-#pragma unroll 1
-    for (int tap = 0; tap < T; ++tap, ++ks) {
-      int dy, dx;
-      if (KIND == CX_K3S1) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
-      else if (KIND == CX_T4S2) { dy = ph_y + (tap >> 1) - 1; dx = ph_x + (tap & 1) - 1; }
-      else { const int ty = sx ? tap >> 1 : tap, tx = sx ? tap & 1 : 0; dy = ty - sy; dx = tx - sx; }
-      const int slot = ks % NS;
-      stage_b(ks + NS - 1 < KS ? ks + NS - 1 : KS - 1, (ks + NS - 1) % NS);   // behind the last step: a harmless re-fetch (straight-line code, one counted wait)
-      const uint8_t* sb = cx_smem + slot * BST;
-      const uint8_t* sat = sa + fa_base + (dy * CX_PW + dx) * 16;
-      x3_s8 af[MR][3];
-#pragma unroll
-      for (int m = 0; m < MR; ++m)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) af[m][t] = *reinterpret_cast<const x3_s8*>(sat + t * (2 * CX_PLANE) + m * (CX_PW * 16));
-#pragma unroll
-      for (int n = 0; n < NWN; ++n) {
-        x3_s8 bf[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) bf[t] = *reinterpret_cast<const x3_s8*>(sb + fb_base + t * (2 * CK * 16) + n * 512);
-        // small products first, into their own accumulator; the M tiles alternate so that dependent MFMAs are not back to back
-#define CX_MM(ACC, ta, tb) _Pragma("unroll") for (int m = 0; m < MR; ++m) ACC[m][n] = x3_mfma<0>(af[m][ta], bf[tb], ACC[m][n]);
-        CX_MM(lo, 0, 2) CX_MM(lo, 2, 0) CX_MM(lo, 1, 1) CX_MM(lo, 0, 1) CX_MM(lo, 1, 0) CX_MM(acc, 0, 0)
-#undef CX_MM
-      }
-      // Counted wait.  In flight, oldest first: B (ks + 1) .. B (ks + NS - 1), with the next chunk's CX_A_ITERS pixel DMAs issued in front of this chunk's tap 0
-      // B round.  The next step needs B (ks + 1): while fewer than NS - 1 B rounds have followed the pixel DMAs (tap < NS - 2) they are younger than B (ks + 1)
-      // and stay in flight with the NS - 2 younger B rounds; from tap NS - 2 on they are older than what must land, so they land too.
-      if (more_a && tap < A_FLY) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NS - 2) * NBP + CX_A_ITERS) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((NS - 2) * NBP) : "memory");
-      // Split the next chunk's pixels into the other buffer (last read in the previous chunk).  They have landed at tap NS - 2's wait, so tap NS - 1 is the first
-      // step that can do it, and the DPT convolution does it there; the interpolation network's geometries have chunks shorter than that (K3S2) and do it at
-      // the chunk's last step, all three alike.  Either position is safe; each entry point keeps the one it was measured with.
-      if (more_a && tap == (EPI ? T : NS) - 1) {
-        if (KIND == CX_K3S2 && T < NS - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a 1- or 2-step chunk: the pixel DMAs have not been waited for yet
-        write_a((chunk + 1) & 1);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
-  // ---- epilogue: accumulator register r of (m, n) = tile column (r & 3) + 8 (r >> 2) + 4 kh of tile row MR wm + m, output channel oc0 + (wn * NWN + n) * 32 + li
-#pragma unroll
-  for (int n = 0; n < NWN; ++n) {
-    const int oc = oc0 + (wn * NWN + n) * 32 + li;
-    float bv = 0.f, sv = 1.f;
-    if constexpr (EPI) { bv = a.bias[oc]; sv = a.slope ? a.slope[oc] : 1.f; }
-#pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const int ty = y0 + MR * wm + m;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int tx = x0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        const int oy = KIND == CX_T4S2 ? 2 * ty + ph_y : ty, ox = KIND == CX_T4S2 ? 2 * tx + ph_x : tx;
-        if (oy < a.Ho && ox < a.Wo) {
-          const size_t pix = ((size_t)b * a.Ho + oy) * a.Wo + ox;
-          float v = acc[m][n][r] + lo[m][n][r];
-          if constexpr (EPI) {
-            v += bv;
-            if (a.slope) v = v >= 0.f ? v : sv * v;
-            if (a.R) v += a.R[pix * a.r_stride + oc];
-          }
-          a.Y[pix * a.y_stride + a.y_offset + oc] = v;
-        }
-      }
-    }
-  }
-}
-
 // ---- weights -> the K-step images [slice][step][term 3][k-half 2][oc CK][8 bf16] in the order a workgroup runs the steps; one thread = (step, k-half, oc): 8
-// channels.  K3S1 / K3S2: W[Cout][Cin][3][3]; T4S2: W[Cin][Cout][4][4] (PyTorch's layouts).  CK = Cout, but 128 for K3S1's C_out 256 (two channel slices); the
-// four phases of T4S2 are its slices.
+// channels.  K3S1 / K3S2: W[Cout][Cin][3][3]; T4S2: W[Cin][Cout][4][4] (PyTorch's layouts).  CK = Cout, but 128 for a C_out above 128 (K3S1's 256, K3S2's 128 n:
+// channel slices, each slice's steps contiguous); the four phases of T4S2 are its slices.
 __global__ __launch_bounds__(256) void k_conv_x3_pack(int kind, const float* __restrict__ W, int Cout, int Cin, uint8_t* __restrict__ img) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int nchunk = Cin / 16, spc = kind == CX_T4S2 ? 16 : 9, total = nchunk * spc * 2 * Cout;
@@ -257,6 +58,7 @@ __global__ __launch_bounds__(256) void k_conv_x3_pack(int kind, const float* __r
     const int sub = j == 0 ? 0 : j < 3 ? 1 : j < 5 ? 2 : 3, tap = j == 0 ? 0 : j < 3 ? j - 1 : j < 5 ? j - 3 : j - 5;
     const int sy = sub >> 1, sx = sub & 1, ty = sx ? tap >> 1 : tap, tx = sx ? tap & 1 : 0;
     ky = sy ? 2 * ty : 1; kx = sx ? 2 * tx : 1;
+    step += (oc / CK) * nchunk * 9;
   } else {                      // [phase 4][chunk][tap 4]
     const int phase = step / (nchunk * 4), rem = step - phase * (nchunk * 4);
     c16 = rem >> 2;
@@ -338,6 +140,15 @@ bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, in
   if (vd_conv3x3_x3_weight_bytes(Cin, Cout) < 0 || B < 1 || H < 1 || W < 1 || B > 65535) return false;
   if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3)) return false;
   return cx_launch(s, false, CX_K3S1, X, B, H, W, Cin, Cin, wimg, nullptr, nullptr, Cout, nullptr, 0, Y, Cout, 0);
+}
+
+// ---- vd3d_conv3x3_s2_x3 (host half; the launch is vd3d_conv_s2.hip's): K3S2 on dense maps, C_out = 128 n as n channel slices
+long long vd_conv3x3_s2_x3_weight_bytes(int Cin, int Cout) {
+  if (Cin < 16 || (Cin & 15) || Cin > 65536 || Cout < 128 || (Cout & 127) || Cout > 1024) return -1;
+  return cx_weight_bytes(CX_K3S2, Cin, Cout);
+}
+bool vd_launch_conv3x3_s2_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img) {
+  return vd_conv3x3_s2_x3_weight_bytes(Cin, Cout) >= 0 && cx_pack(s, CX_K3S2, W, Cin, Cout, img);
 }
 
 // ---- vd3d_conv_ifn: the entry point has checked every argument

@@ -238,6 +238,10 @@ bool vd_launch_conv3x3_x2(hipStream_t s, const float* X, int B, int H, int W, in
 long long vd_conv3x3_x3_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+// vd3d_conv_x3.hip (weights) / vd3d_conv_s2.hip (launch): 3 x 3, stride 2, padding 1, no bias, C_out = 128 n <= 1024 as n channel slices; output (H+1)/2 x (W+1)/2
+long long vd_conv3x3_s2_x3_weight_bytes(int Cin, int Cout);
+bool vd_launch_conv3x3_s2_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
+bool vd_launch_conv3x3_s2_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
 // vd3d_conv_head.hip: conv3x3(up(x) + b_in) [+ the head's tail] in exact float32 (v_mfma_f32_32x32x2_f32); b2 == nullptr: plain NHWC output
 long long vd_dpt_head_conv_weight_bytes(int Cin, int Cout);
 bool vd_launch_dpt_head_conv_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
@@ -266,6 +270,7 @@ bool vd_launch_bias_act_f32(hipStream_t s, const float* y, const float* bias, co
 bool vd_launch_upsample_bilinear_bias_nhwc_f32(hipStream_t s, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C);
 bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, const float* w3, float b3, float scale, long long n_pix, int C, float* out);
 bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const float* bias, int B, int H, int W, int f, int C, float* out);
+bool vd_launch_patchify_f32(hipStream_t s, const float* x, int B, int th, int tw, int p, float* out);   // NHWC [B][th][tw][3] -> rows [B gh gw][3 p^2 up to 16]
 // ---- vd3d_handoff.hip
 void vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,
                              uint8_t* out);

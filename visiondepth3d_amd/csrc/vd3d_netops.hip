@@ -319,3 +319,39 @@ bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const floa
                      total, (float4*)out);
   return true;
 }
+
+// k_patchify: the gather half of a ViT patch embedding (Conv2d(3, C, kernel_size=p, stride=p)) run as a GEMM -- kernel == stride, so every patch is one row:
+// x NHWC [B][th][tw][3] (what vd3d_depth_preprocess writes) -> rows [B * gh * gw][Kp], gh = th / p, gw = tw / p (the convolution drops a remainder), column
+// (c * p + ky) * p + kx = x[b][gy p + ky][gx p + kx][c] (F.unfold's order = the flattened weight [C][3][p][p]); the columns from 3 p^2 to Kp (3 p^2 rounded
+// up to the GEMM's K unit of 16) are written as zeros.  Exact copies.  One thread = 4 consecutive columns (one 16-byte store).
+__global__ __launch_bounds__(256) void k_patchify(const float* __restrict__ x, int th, int tw, int p, int gh, int gw, int kp4, long long total,
+                                                  float4* __restrict__ out) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int k4 = (int)(idx % kp4);
+  long long r = idx / kp4;
+  const int gx = (int)(r % gw); r /= gw;
+  const int gy = (int)(r % gh);
+  const long long b = r / gh;
+  const int pp = p * p, K = 3 * pp;
+  float v[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int k = k4 * 4 + e;
+    v[e] = 0.f;
+    if (k < K) {
+      const int c = k / pp, rem = k - c * pp, ky = rem / p, kx = rem - ky * p;
+      v[e] = x[((b * th + (gy * p + ky)) * tw + (gx * p + kx)) * 3 + c];
+    }
+  }
+  out[idx] = float4{v[0], v[1], v[2], v[3]};
+}
+bool vd_launch_patchify_f32(hipStream_t s, const float* x, int B, int th, int tw, int p, float* out) {
+  if (B < 1 || p < 1 || p > 64 || th < p || tw < p) return false;
+  if ((reinterpret_cast<uintptr_t>(x) & 3) || (reinterpret_cast<uintptr_t>(out) & 15)) return false;
+  const int gh = th / p, gw = tw / p, kp = (3 * p * p + 15) / 16 * 16;
+  const long long total = (long long)B * gh * gw * (kp / 4);
+  if ((total + 255) / 256 > 0x7fffffffLL) return false;
+  hipLaunchKernelGGL(k_patchify, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, th, tw, p, gh, gw, kp / 4, total, (float4*)out);
+  return true;
+}

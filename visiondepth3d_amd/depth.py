@@ -124,6 +124,13 @@ def conv_transpose_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     return w.detach().permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous()
 
 
+def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
+    """Patch-embedding weight [C, 3, p, p] (kernel == stride: every patch is one GEMM row) -> [C, Kp]: the flattened (c, ky, kx) columns, zero-padded from 3 p^2
+    to the next multiple of 16 (vd3d_gemm_x3's K unit; p = 14: 588 -> 592).  vd3d_patchify_f32 writes the matching rows, zero tail included."""
+    C, k = w.shape[0], w[0].numel()
+    return F.pad(w.detach().reshape(C, k), (0, (k + 15) // 16 * 16 - k)).contiguous()
+
+
 def _head_tail_operands(conv3: torch.nn.Conv2d):
     """() -> (w3, b3) of the head's 1x1 convolution to one channel, for vd3d_dpt_head_tail_f32.  The scalar bias is read on the host ONCE per parameter
     version (no per-call sync); an in-place update of the parameters (load_state_dict, .copy_) bumps their version counters and is picked up at the
@@ -184,7 +191,7 @@ class DepthPipe:
 
     def __init__(self, name: str = "depth-anything-v2-small", device="cuda", dtype=torch.float32, seed: int = 0,
                  channels_last: bool = True, renderer=None, fuse_backbone: bool = True, model=None, processor: dict | None = None,
-                 tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None):
+                 tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None, self_contained: bool = False):
         """``dtype``: float32 (the reference's precision, default) or bfloat16.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
         GEMMs and the attention (64-wide heads) is the library's exact-float32 kernel (``vd3d_attention_f32``: both products on the float32-input
@@ -217,21 +224,38 @@ class DepthPipe:
         MI355X; ignored when its library-version validators do not match; ``VD3D_TUNED_GEMM=0`` disables).  ``miopen_find``: MIOpen
         find mode (``torch.backends.cudnn.benchmark``) -- every convolution shape times its applicable solvers once, ~25 s at the
         first forward of a process, 4.5 % on the 4K float32 forward (profiles/r04_net_library_selection.md); opt-in, bench.py uses it.
-        The flag is PyTorch's process-wide one: True / False set it, None (default) leaves it as the caller has it."""
+        The flag is PyTorch's process-wide one: True / False set it, None (default) leaves it as the caller has it.
+        ``self_contained``: ``False`` (default) -- everything above.  ``True`` -- OPT-IN, only with ``gemm="bf16x3"``, ``conv="bf16x3"``, float32, a renderer on a
+        GPU and ``fuse_backbone=True`` (else ValueError naming what is missing), and only for ``DepthAnythingForDepthEstimation`` on ``Dinov2Backbone`` (else
+        NotImplementedError naming the model): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
+        as ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, the reassemble stage's 1 x 1 projections as ``vd3d_gemm_x3`` over the token rows, its transposed
+        convolutions as ``vd3d_gemm_x3`` + ``vd3d_depth_to_space_bias_nhwc_f32``, its 3 x 3 stride-2 convolution on ``vd3d_conv3x3_s2_x3``, the fusion layers'
+        1 x 1 projections as ``vd3d_gemm_x3`` over the pixel rows, and EVERY 3 x 3 stride-1 convolution on ``vd3d_conv3x3_x3`` (no size rule).  A module the
+        mode cannot route is refused by name, never handed to a library.  ``conv_routes`` names every routed module and holds no ``"library"`` value.  The
+        library selection is skipped: TunableOp is not enabled, ``torch.backends.cudnn.benchmark`` is not touched, ``tuned_gemm`` / ``miopen_find`` read
+        False.  Per output element every kernel sums in one fixed order and nothing is split along K, so a frame's prediction does not depend on the batch it
+        is in or on the ROCm release's solution tables."""
         self.name, self.device, self.dtype = name, torch.device(device), dtype
         if gemm not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
         if conv not in (None, "bf16x3"):
             raise ValueError("conv must be None or 'bf16x3'")
+        if self_contained:
+            missing = [what for what, ok in (("gemm='bf16x3'", gemm == "bf16x3"), ("conv='bf16x3'", conv == "bf16x3"), ("dtype=torch.float32", dtype == torch.float32),
+                                             ("a renderer on a GPU", renderer is not None and torch.device(device).type == "cuda"),
+                                             ("fuse_backbone=True", bool(fuse_backbone)),
+                                             ("the neck glue launches (VD3D_NECK_GLUE=0 is set)", os.environ.get("VD3D_NECK_GLUE", "1") != "0")) if not ok]
+            if missing:
+                raise ValueError("self_contained=True needs " + ", ".join(missing))
         if conv == "bf16x3" and gemm != "bf16x3":
             raise ValueError("conv='bf16x3' is the convolution half of gemm='bf16x3' and needs that mode")
         if gemm != "f32" and (dtype != torch.float32 or renderer is None or torch.device(device).type != "cuda"):
             raise ValueError("gemm='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
-        self.gemm, self.conv = gemm, conv
+        self.gemm, self.conv, self.self_contained = gemm, conv, bool(self_contained)
         self.conv_routes = {}
         self.tuned_gemm = self.miopen_find = False
         self._flop_count = None
-        if self.device.type == "cuda":
+        if self.device.type == "cuda" and not self.self_contained:   # self-contained: no library call to select for
             self._library_selection(tuned_gemm, miopen_find)
         if dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("DepthPipe runs in float32 (reference precision) or bfloat16")
@@ -245,6 +269,15 @@ class DepthPipe:
             synthetic_weights_(model, seed)
             processor = processor or PROCESSORS[MODEL_ZOO[name]["arch"]]
         self.arch = "da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "generic"
+        if self.self_contained and not (self.arch == "da" and type(model.backbone).__name__ == "Dinov2Backbone"):
+            bname = type(getattr(model, "backbone", None)).__name__ if getattr(model, "backbone", None) is not None else "its own encoder"
+            raise NotImplementedError(f"self_contained=True: {name!r} ({type(model).__name__} on {bname}) -- the mode is built for DepthAnythingForDepthEstimation "
+                                      "on Dinov2Backbone (Depth-Anything V1 / V2, Distill-Any-Depth) only; DPT-Large keeps gemm='bf16x3' without it")
+        if self.self_contained:
+            bc = model.config.backbone_config
+            if int(bc.hidden_size) not in (384, 768, 1024) or int(bc.hidden_size) != 64 * int(bc.num_attention_heads):
+                raise NotImplementedError(f"self_contained=True: {name!r}: hidden size {bc.hidden_size} with {bc.num_attention_heads} heads -- vd3d_attention_x3 and "
+                                          "vd3d_add_layernorm are built for 384 / 768 / 1024 with 64-wide heads; anything else would run library attention")
         self.proc = dict(PROCESSORS["da"] if processor is None else processor)
         self.model = model.eval().to(self.device, dtype)
         if channels_last and self.device.type == "cuda":
@@ -264,6 +297,8 @@ class DepthPipe:
                 self._fuse_backbone_layers()
             if self.renderer is not None:
                 self._patch_dpt_upsampling()
+            if self.self_contained:
+                self._patch_patch_embedding()
 
     def _library_selection(self, tuned_gemm: bool, miopen_find):
         if miopen_find is not None:
@@ -358,6 +393,7 @@ class DepthPipe:
         R = self.renderer
         f32 = self.dtype == torch.float32 and os.environ.get("VD3D_NECK_GLUE", "1") != "0"   # 0: A/B switch back to the module graph's own passes
         CL = torch.channels_last
+        sc = self.self_contained   # no library call: what cannot be routed to a kernel of this library is refused (the constructor has checked float32 + glue)
 
         def up(x, size):
             if x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] % 8 == 0 and x.is_contiguous(memory_format=CL):
@@ -391,8 +427,13 @@ class DepthPipe:
             if key not in conv3_img:
                 conv3_img[key] = R.conv3x3_x3_pack(m.weight)
             if conv3_img[key] is None:
+                if sc:
+                    raise NotImplementedError(f"self_contained=True: {names[key]}: vd3d_conv3x3_x3 does not build {m.in_channels} -> {m.out_channels} channels")
                 self.conv_routes[names[key]] = ("library", f"shape not built: {m.in_channels} -> {m.out_channels} channels")
                 return None
+            if sc:   # no size rule: every map, the 19 x 33 ones included
+                self.conv_routes[names[key]] = ("bf16x3", "self-contained")
+                return R.conv3x3_x3(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
             tiles = x.shape[0] * ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)   # one workgroup per 8 x 32 output tile
             if tiles < CONV_X3_MIN_TILES:
                 self.conv_routes[names[key]] = ("library", f"size rule: {tiles} tiles < {CONV_X3_MIN_TILES}")
@@ -402,9 +443,13 @@ class DepthPipe:
 
         if self.conv == "bf16x3" and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
             for m in self.model.neck.convs:
+                if sc and m.bias is not None:
+                    raise NotImplementedError(f"self_contained=True: {names[id(m)]} has a bias (the stock neck convolutions have none) -- not built")
                 if m.bias is None:
                     def neck_conv_fwd(x, m=m):
                         y = conv_x3(m, x)
+                        if y is None and sc:
+                            raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 3 x 3 / stride 1 / padding 1 convolution -- not built")
                         return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups) if y is None else y
                     m.forward = neck_conv_fwd
 
@@ -412,10 +457,27 @@ class DepthPipe:
             y = conv_x2(m, x)
             if y is None:
                 y = conv_x3(m, x)
+            if y is None and sc:
+                raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 3 x 3 / stride 1 / padding 1 convolution -- not built")
             if y is None:
                 y = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups).contiguous(memory_format=CL)
             if self._flop_count is not None:   # flops_per_frame: these calls bypass the modules' forward hooks
                 self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1]
+            return y
+
+        gemm_img = {}   # self-contained: packed weights of the 1 x 1 projections / transposed convolutions per module
+
+        def conv1x1_x3(m, x):
+            """Self-contained: a 1 x 1 convolution WITHOUT its bias as vd3d_gemm_x3 over the pixel rows of a channels_last map (its NHWC storage is the row matrix)."""
+            if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.padding != (0, 0) or m.groups != 1 or m.in_channels % 16 or x.dtype != torch.float32:
+                raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 1 x 1 convolution with C_in a multiple of 16 -- not built")
+            if id(m) not in gemm_img:
+                gemm_img[id(m)] = R.gemm_x3_pack(m.weight.reshape(m.out_channels, m.in_channels), "bf16x3")
+            rows = x.contiguous(memory_format=CL).permute(0, 2, 3, 1)   # [B, h, w, C] contiguous
+            y = R.linear_x3(rows, gemm_img[id(m)], m.out_channels, None).permute(0, 3, 1, 2)
+            self.conv_routes[names[id(m)]] = ("bf16x3", "self-contained: vd3d_gemm_x3 over the pixel rows")
+            if self._flop_count is not None:   # flops_per_frame: what conv_nb adds for the same module
+                self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * m.in_channels
             return y
 
         def res_unit(unit, x, x_relu=None, extra=None, want_relu=False):
@@ -441,8 +503,10 @@ class DepthPipe:
                 else:
                     hidden_state = res_unit(layer.residual_layer2, hidden_state) if fused else layer.residual_layer2(hidden_state)
                 tgt = (2 * hidden_state.shape[2], 2 * hidden_state.shape[3]) if size is None else tuple(size)
+                if sc and not (fused and layer.projection.bias is not None):
+                    raise NotImplementedError(f"self_contained=True: {names[id(layer)]}: a float32 map with channels in multiples of 4 and a projection with a bias expected")
                 if fused and layer.projection.bias is not None:
-                    return R.upsample_bilinear_bias(conv_nb(layer.projection, hidden_state), tgt, layer.projection.bias)
+                    return R.upsample_bilinear_bias((conv1x1_x3 if sc else conv_nb)(layer.projection, hidden_state), tgt, layer.projection.bias)
                 return layer.projection(up(hidden_state, tgt))
             layer.forward = fusion_fwd
         if getattr(self, "dpt_vit", False):
@@ -453,6 +517,8 @@ class DepthPipe:
         if (f32 and isinstance(head.activation2, torch.nn.ReLU) and head.conv2.out_channels in (16, 32, 64) and head.conv3.kernel_size == (1, 1)
                 and head.conv2.bias is not None and head.conv3.bias is not None and head.conv1.bias is not None):
             tail_operands = _head_tail_operands(head.conv3)
+        if sc and tail_operands is None:
+            raise NotImplementedError("self_contained=True: a depth head other than [conv 3 x 3, up-sampling, conv 3 x 3 -> 16 / 32 / 64, ReLU, conv 1 x 1, ReLU] with biases -- not built")
 
         # float32 mode: up-sampling + conv2 + tail as ONE exact-float32 MFMA launch (vd3d_dpt_head_conv_f32); VD3D_HEAD_FUSED=0: A/B switch back to the three launches
         head_fused = self.gemm == "f32" and self.conv != "bf16x3" and self.device.type == "cuda"   # (the kernel reads device memory: a pipe on the CPU keeps its graph)
@@ -512,7 +578,97 @@ class DepthPipe:
                 x = hs[:, 1:].reshape(B, patch_height, patch_width, Cn).permute(0, 3, 1, 2)   # NHWC storage, NCHW view: channels_last
                 out.append(stage.layers[i](x))
             return out
-        stage.forward = reassemble_fwd
+        stage.forward = self._self_contained_reassemble(names) if sc else reassemble_fwd
+
+    def _self_contained_reassemble(self, names):
+        """The DINOv2 reassemble stage without a library call (self_contained=True) -- DPT-Large's route (_patch_dpt_vit_reassemble_head) without the readout: per
+        hook, the tokens minus CLS are the rows of the 1 x 1 projection (linear_x3 with its bias; [B, T-1, C_i] is NHWC storage); ConvTranspose2d (kernel == stride,
+        no padding) is a linear_x3 on conv_transpose_gemm_weight + vd3d_depth_to_space_bias_nhwc_f32; Identity stays; the 3 x 3 / stride 2 / padding 1 convolution
+        runs on vd3d_conv3x3_s2_x3 with its bias through bias_act.  Any other resize module is refused by name, here, at construction."""
+        R, CL = self.renderer, torch.channels_last
+        stage = self.model.neck.reassemble_stage
+        hooks = []
+        for lay in stage.layers:
+            pm, rz = lay.projection, lay.resize
+            if pm.kernel_size != (1, 1) or pm.stride != (1, 1) or pm.padding != (0, 0) or pm.groups != 1 or pm.in_channels % 16:
+                raise NotImplementedError(f"self_contained=True: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
+            hk = dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), "bf16x3"), kind="identity", img=None)
+            if isinstance(rz, torch.nn.ConvTranspose2d):
+                if not (rz.kernel_size == rz.stride and rz.kernel_size[0] == rz.kernel_size[1] and rz.padding == (0, 0) and rz.output_padding == (0, 0)
+                        and rz.dilation == (1, 1) and rz.groups == 1 and rz.in_channels % 16 == 0 and rz.out_channels % 4 == 0):
+                    raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a ConvTranspose2d with kernel {rz.kernel_size} / stride {rz.stride} / padding "
+                                              f"{rz.padding}, {rz.in_channels} -> {rz.out_channels} channels (built: square kernel == stride, no padding, C_in % 16) -- not built")
+                hk["kind"], hk["img"] = "ct", R.gemm_x3_pack(conv_transpose_gemm_weight(rz.weight), "bf16x3")
+            elif isinstance(rz, torch.nn.Conv2d):
+                img = None
+                if rz.kernel_size == (3, 3) and rz.stride == (2, 2) and rz.padding == (1, 1) and rz.dilation == (1, 1) and rz.groups == 1:
+                    img = R.conv3x3_s2_x3_pack(rz.weight)
+                if img is None:
+                    raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a Conv2d with kernel {rz.kernel_size} / stride {rz.stride} / padding {rz.padding}, "
+                                              f"{rz.in_channels} -> {rz.out_channels} channels (built: 3 x 3 / stride 2 / padding 1, C_in % 16, C_out % 128 up to 1024) -- not built")
+                hk["kind"], hk["img"] = "s2", img
+            elif not isinstance(rz, torch.nn.Identity):
+                raise NotImplementedError(f"self_contained=True: {names[id(rz)]} ({type(rz).__name__}) is no resize module the mode routes -- not built")
+            hooks.append(hk)
+
+        def count(m, y):   # flops_per_frame: the routed modules bypass the counting hooks; this is the hook's own formula for module m with output y, so
+            if self._flop_count is not None:   # that the figure equals the library mode's
+                self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1]
+
+        def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
+            out = []
+            for hk, hs in zip(hooks, hidden_states):
+                B, T, _ = hs.shape
+                if patch_height is None or patch_width is None:
+                    raise ValueError("the DINOv2 reassemble stage needs the patch grid")
+                gh, gw = int(patch_height), int(patch_width)
+                if gh * gw != T - 1:
+                    raise ValueError(f"{T - 1} patch tokens do not form a {gh} x {gw} grid")
+                pm, rz = hk["pm"], hk["rz"]
+                n = pm.out_channels
+                x = R.linear_x3(hs[:, 1:].contiguous(), hk["proj"], n, pm.bias)                  # [B, T-1, C_i]: NHWC storage
+                self.conv_routes[names[id(pm)]] = ("bf16x3", "self-contained: vd3d_gemm_x3 over the token rows")
+                x = x.view(B, gh, gw, n).permute(0, 3, 1, 2)
+                count(pm, x)
+                if hk["kind"] == "ct":
+                    s = rz.kernel_size[0]
+                    y = R.linear_x3(x.permute(0, 2, 3, 1), hk["img"], s * s * rz.out_channels, None)
+                    x = R.depth_to_space_bias(y.view(B * gh * gw, s * s * rz.out_channels), B, gh, gw, s, rz.bias)
+                    self.conv_routes[names[id(rz)]] = ("bf16x3", "self-contained: vd3d_gemm_x3 + vd3d_depth_to_space_bias_nhwc_f32")
+                    count(rz, x)
+                elif hk["kind"] == "s2":
+                    x = R.conv3x3_s2_x3(x, hk["img"], rz.out_channels)
+                    if rz.bias is not None:
+                        x = R.bias_act(x, rz.bias)
+                    self.conv_routes[names[id(rz)]] = ("bf16x3", "self-contained: vd3d_conv3x3_s2_x3")
+                    count(rz, x)
+                out.append(x)
+            return out
+        return reassemble_fwd
+
+    def _patch_patch_embedding(self):
+        """Self-contained: Dinov2PatchEmbeddings (Conv2d(3, C, kernel_size=p, stride=p)) as vd3d_patchify_f32 + vd3d_gemm_x3 on the weight reshaped to [C, 3 p^2] and
+        zero-padded to the GEMM's K unit (p = 14: 588 -> 592), with its bias: [B, T-1, C] directly.  CLS, the cached position embedding and the final LayerNorm
+        stay ATen element-wise / native kernels."""
+        R = self.renderer
+        pe = self.model.backbone.embeddings.patch_embeddings
+        m = pe.projection
+        name = next(n for n, mod in self.model.named_modules() if mod is m)
+        p = m.kernel_size[0]
+        if not (isinstance(m, torch.nn.Conv2d) and m.kernel_size == (p, p) and m.stride == (p, p) and m.padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1
+                and m.in_channels == 3 and p <= 64):
+            raise NotImplementedError(f"self_contained=True: {name}: a patch embedding other than Conv2d(3, C, kernel_size=p, stride=p), p <= 64 -- not built")
+        img = R.gemm_x3_pack(patch_embedding_gemm_weight(m.weight), "bf16x3")
+
+        def patch_fwd(pixel_values):
+            if pixel_values.dtype != torch.float32 or pixel_values.shape[1] != 3:
+                raise NotImplementedError("self_contained=True: the patch embedding takes a float32 [B, 3, th, tw] image")
+            rows = R.patchify(pixel_values.contiguous(memory_format=torch.channels_last), p)   # what depth_preprocess hands over is taken as it is
+            self.conv_routes[name] = ("bf16x3", "self-contained: vd3d_patchify_f32 + vd3d_gemm_x3")
+            if self._flop_count is not None:   # flops_per_frame: the counting hook's formula for the bypassed Conv2d
+                self._flop_count[0] += 2.0 * rows.shape[1] * m.out_channels * 3 * p * p
+            return R.linear_x3(rows, img, m.out_channels, m.bias)
+        pe.forward = patch_fwd
 
     def _patch_dpt_vit_reassemble_head(self, conv_nb, f32):
         """DPT-Large's reassemble stage and head on the library path (split modes; called by _patch_dpt_upsampling, whose fusion-stage rewrite DPT shares):

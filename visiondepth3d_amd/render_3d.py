@@ -928,6 +928,30 @@ class Renderer:
         _lib.check(self._L.vd3d_conv3x3_x3(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
         return out
 
+    def conv3x3_s2_x3_pack(self, weight: torch.Tensor):
+        """Split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_s2_x3``; ``None`` when the shape is not built (Cin % 16, Cout a multiple of
+        128 up to 1024)."""
+        w = weight.detach().to(self.device, torch.float32).contiguous()
+        Cout, Cin, kh, kw = w.shape
+        nb = int(self._L.vd3d_conv3x3_s2_x3_weight_bytes(Cin, Cout)) if (kh, kw) == (3, 3) else -1
+        if nb < 0:
+            return None
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(self._L.vd3d_conv3x3_s2_x3_pack_weights(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
+        return img
+
+    def conv3x3_s2_x3(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
+        """F.conv2d(x, W, None, stride 2, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_s2_x3_pack(W)``: bf16x3 MFMA
+        arithmetic, float32 accumulation (include/vd3d.h vd3d_conv3x3_s2_x3); returns a channels_last [B, Cout, (H+1)//2, (W+1)//2] tensor."""
+        B, Cin, H, W = x.shape
+        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
+            raise AssertionError("conv3x3_s2_x3: float32 channels_last input")
+        out = torch.empty((B, int(Cout), (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        self._enter(x, w_image, out)
+        _lib.check(self._L.vd3d_conv3x3_s2_x3(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
+        return out
+
     def conv_ifn_pack(self, kind: int, weight: torch.Tensor):
         """Split + pack a float32 weight for ``conv_ifn``: ``[Cout, Cin, 3, 3]`` for ``_abi.IFN_K3S1`` / ``IFN_K3S2``, ``[Cin, Cout, 4, 4]`` (ConvTranspose2d's layout) for
         ``IFN_T4S2``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 96})."""
@@ -1100,6 +1124,22 @@ class Renderer:
         self._enter(y, bias, out)
         _lib.check(self._L.vd3d_depth_to_space_bias_nhwc_f32(self._ctx, _ptr(y), _ptr(bias) if bias is not None else None, int(B), int(H), int(W), int(s), Cc,
                                                              _ptr(out)))
+        return out
+
+    def patchify(self, x: torch.Tensor, p: int) -> torch.Tensor:
+        """The rows of a patch embedding run as a GEMM: float32 ``x`` of logical shape [B, 3, th, tw] in channels_last memory (what ``depth_preprocess`` returns) ->
+        contiguous [B, (th // p) * (tw // p), Kp], column (c * p + ky) * p + kx = x[b, c, gy * p + ky, gx * p + kx] (``F.unfold``'s order), Kp = 3 p^2 rounded up
+        to a multiple of 16 with the tail written as zeros (include/vd3d.h vd3d_patchify_f32)."""
+        B, Cc, th, tw = x.shape
+        if x.dtype != torch.float32 or Cc != 3 or not x.permute(0, 2, 3, 1).is_contiguous():
+            raise ValueError("patchify: a float32 [B, 3, th, tw] tensor in channels_last memory expected")
+        p = int(p)
+        if p < 1 or th < p or tw < p:
+            raise ValueError(f"patchify: a {th} x {tw} image holds no {p} x {p} patch")
+        kp = (3 * p * p + 15) // 16 * 16
+        out = torch.empty((B, (th // p) * (tw // p), kp), dtype=torch.float32, device=x.device)
+        self._enter(x, out)
+        _lib.check(self._L.vd3d_patchify_f32(self._ctx, _ptr(x), B, th, tw, p, _ptr(out)))
         return out
 
     def detect_black_bars(self, frame_bgr: torch.Tensor):
