@@ -36,7 +36,7 @@ extern "C" {
  * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
  * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32, vd3d_attention_f32_form,
  *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs, vd3d_conv3x3_s2_x3_weight_bytes,
- *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)). */
+ *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)), vd3d_depth_handoff_form, vd3d_depth_preprocess_form. */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -396,6 +396,10 @@ int vd3d_nhwc_f16_to_planar3_f32(vd3d_ctx* ctx, const void* t_nhwc32, int H, int
  * (core/render_depth.py:585-611,1914-1916) for a batch of B predictions [B][ph][pw] float32 -> uint8 [B][H][W].
  * Replaces the reference's 8-bit depth video on disk while keeping its quantisation. */
 int vd3d_depth_handoff(vd3d_ctx* ctx, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint8_t* out_gray);
+/* The same with the kernel named.  form 0: the library's choice (what vd3d_depth_handoff runs), 1: the general kernel (any size), 2: the separable
+ * kernel, which keeps the horizontally interpolated prediction rows of a band of output rows in registers -- up-scaling only (ph <= H, pw <= W, not both
+ * equal), VD3D_E_UNSUPPORTED elsewhere.  The forms give the same bytes. */
+int vd3d_depth_handoff_form(vd3d_ctx* ctx, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint8_t* out_gray, int form);
 
 /* ---- tiled high-resolution depth (core/render_depth.py:62-66,102-194: infer_depth_tile, _normalize_to_u8).  The inference-size frame is cut into
  * `tile`-pixel tiles on a grid of core = max(1, tile - 2*pad), each cropped with a `pad` apron, resized so that both sides are multiples of 14, run
@@ -482,6 +486,11 @@ typedef enum vd3d_dtype { VD3D_DT_BF16 = 0, VD3D_DT_F32 = 1, VD3D_DT_F16 = 2 /* 
  * Returns VD3D_E_UNSUPPORTED when the down-scale factor exceeds the kernel's tap budget (scale > ~5.5). */
 int vd3d_depth_preprocess(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
                           const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc);
+/* The same with the kernel named.  form 0: the library's choice (what vd3d_depth_preprocess runs), 1: the general tile kernel, 2: the strip kernel
+ * (a workgroup filters a 32-column strip of a band of up to 32 output rows) -- down-scaling on both axes within its LDS plan (scale up to ~5.3),
+ * VD3D_E_UNSUPPORTED elsewhere.  The forms give the same bits; a scale past the tap budget is VD3D_E_UNSUPPORTED whatever the form. */
+int vd3d_depth_preprocess_form(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
+                               const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc, int form);
 
 /* Transformer-block glue of the depth network (a25): s = x + y, n = LayerNorm(s)*gamma + beta on [rows][cols] device arrays
  * of `dtype` in one pass (y == NULL: LayerNorm only, out_sum unused).  cols in {384, 768, 1024} (DA-V2 S/B/L), else

@@ -7,7 +7,7 @@ db = sqlite3.connect(sys.argv[1])
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 top = int(sys.argv[3]) if len(sys.argv) > 3 else 40
 rows = db.execute("select name,start,end from kernels order by start").fetchall()
-marks = [i for i, r in enumerate(rows) if r[0].startswith("void k_handoff<false>")]
+marks = [i for i, r in enumerate(rows) if r[0].startswith(("void k_handoff<false>", "void k_handoff_sep<false>"))]
 if len(marks) <= n:
     marks = [i for i, r in enumerate(rows) if r[0].startswith("k_chain_ingest")][::16]
 sel = rows[marks[-n - 1]:marks[-1]]

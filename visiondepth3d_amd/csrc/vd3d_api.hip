@@ -1426,14 +1426,19 @@ VD3D_EXPORT int vd3d_add_weighted_u8(vd3d_ctx* c, const uint8_t* a, double alpha
 }
 
 // a24: depth-net prediction [B][ph][pw] float32 -> uint8 depth planes [B][H][W] (bicubic post-process + per-frame min-max)
-VD3D_EXPORT int vd3d_depth_handoff(vd3d_ctx* c, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint8_t* out_gray) {
+VD3D_EXPORT int vd3d_depth_handoff_form(vd3d_ctx* c, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint8_t* out_gray, int form) {
   if (!c || !pred || !out_gray || B < 1 || ph < 1 || pw < 1 || H < 1 || W < 1) return set_err(VD3D_E_INVALID, "bad argument");
+  if (form < 0 || form > 2) return set_err(VD3D_E_INVALID, "depth_handoff: form %d (0 = choose, 1 = general, 2 = separable)", form);
   HIPCHK(hipSetDevice(c->device));
   if (B > c->mm_cap) { HIPCHK(re_alloc(&c->mm, (size_t)3 * B)); c->mm_cap = B; }
   StageTimer t(c, "handoff");
-  vd_launch_depth_handoff(c->stream, pred, B, ph, pw, H, W, invert ? 1 : 0, c->mm, out_gray);
+  if (!vd_launch_depth_handoff(c->stream, pred, B, ph, pw, H, W, invert ? 1 : 0, c->mm, out_gray, form))
+    return set_err(VD3D_E_UNSUPPORTED, "depth_handoff: the separable form is for up-scaling only (%dx%d -> %dx%d)", pw, ph, W, H);
   HIPCHK(hipGetLastError());
   return 0;
+}
+VD3D_EXPORT int vd3d_depth_handoff(vd3d_ctx* c, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint8_t* out_gray) {
+  return vd3d_depth_handoff_form(c, pred, B, ph, pw, H, W, invert, out_gray, 0);
 }
 
 // tiled high-resolution depth (vd3d_tiles.hip): infer_depth_tile's crops and blend, _normalize_to_u8 (core/render_depth.py:102-194)
@@ -1579,17 +1584,23 @@ VD3D_EXPORT int vd3d_depth_letterbox_fill_u8(vd3d_ctx* c, const uint8_t* depth, 
   return 0;
 }
 
-VD3D_EXPORT int vd3d_depth_preprocess(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
-                                      const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc) {
+VD3D_EXPORT int vd3d_depth_preprocess_form(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
+                                           const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc, int form) {
+  if (form < 0 || form > 2) return set_err(VD3D_E_INVALID, "depth_preprocess: form %d (0 = choose, 1 = general, 2 = strip)", form);
   if (dtype != VD3D_DT_BF16 && dtype != VD3D_DT_F32) return set_err(VD3D_E_INVALID, "bad dtype %d", dtype);
   if (!c || !frames_bgr || !mean3_host || !std3_host || !out_nhwc || B < 1 || H < 1 || W < 1 || th < 1 || tw < 1)
     return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));
   StageTimer t(c, "depth_prep");
-  if (!vd_launch_depth_prep(c->stream, frames_bgr, B, H, W, th, tw, mean3_host, std3_host, dtype, out_nhwc))
-    return set_err(VD3D_E_UNSUPPORTED, "depth_preprocess: %dx%d -> %dx%d exceeds the antialias tap budget", W, H, tw, th);
+  const int rc = vd_launch_depth_prep(c->stream, frames_bgr, B, H, W, th, tw, mean3_host, std3_host, dtype, out_nhwc, form);
+  if (rc == 1) return set_err(VD3D_E_UNSUPPORTED, "depth_preprocess: %dx%d -> %dx%d exceeds the antialias tap budget", W, H, tw, th);
+  if (rc) return set_err(VD3D_E_UNSUPPORTED, "depth_preprocess: the strip form does not hold %dx%d -> %dx%d (down-scaling within its LDS plan only)", W, H, tw, th);
   HIPCHK(hipGetLastError());
   return 0;
+}
+VD3D_EXPORT int vd3d_depth_preprocess(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
+                                      const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc) {
+  return vd3d_depth_preprocess_form(c, frames_bgr, B, H, W, th, tw, mean3_host, std3_host, dtype, out_nhwc, 0);
 }
 
 VD3D_EXPORT int vd3d_add_layernorm(vd3d_ctx* c, int dtype, const void* x, const void* y_or_null, const void* gamma, const void* beta,

@@ -223,8 +223,10 @@ void vd_launch_blank_eye(hipStream_t s, const uint8_t* src, int h, int w, const 
 
 bool vd_launch_preview(hipStream_t s, int type, const uint8_t* L, const uint8_t* R, int h, int w, uint8_t* out);
 // ---- vd3d_depthprep.hip
-bool vd_launch_depth_prep(hipStream_t s, const uint8_t* frames, int B, int H, int W, int th, int tw, const float mean[3],
-                          const float stdv[3], int dtype, void* out_nhwc);
+// form: 0 = the library's choice (the strip kernel for down-scaling within its LDS plan), 1 = the general tile kernel, 2 = the strip kernel;
+// returns 0 = launched, 1 = outside the tap budget (every form), 2 = form 2 asked for where the strip kernel does not apply
+int vd_launch_depth_prep(hipStream_t s, const uint8_t* frames, int B, int H, int W, int th, int tw, const float mean[3],
+                         const float stdv[3], int dtype, void* out_nhwc, int form);
 // ---- vd3d_netops.hip
 // vd3d_gemm.hip: the transformer linears as a split-bf16 (bf16x3, six products) GEMM with float32 accumulation
 long long vd_gemm_x3_weight_bytes(int N, int K, int mode);
@@ -272,8 +274,9 @@ bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, con
 bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const float* bias, int B, int H, int W, int f, int C, float* out);
 bool vd_launch_patchify_f32(hipStream_t s, const float* x, int B, int th, int tw, int p, float* out);   // NHWC [B][th][tw][3] -> rows [B gh gw][3 p^2 up to 16]
 // ---- vd3d_handoff.hip
-void vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,
-                             uint8_t* out);
+// form: 0 = the library's choice (the separable kernel for up-scaling), 1 = the general kernel, 2 = the separable kernel (false where it does not apply)
+bool vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,
+                             uint8_t* out, int form);
 
 // ---- vd3d_tiles.hip: tiled high-resolution depth (gather of apron crops, Hann blend of tile centres, percentile-clip normalisation)
 #define VD_PCLIP_NR 6                              // order statistics per frame: min, two around each percentile, max

@@ -147,40 +147,93 @@ __global__ __launch_bounds__(256) void k_upsample_bilinear_nhwc(const uint4* __r
   }
   out[idx] = make_uint4(o[0], o[1], o[2], o[3]);
 }
-// float32 variant: one thread = 4 channels (16 B), ATen's association
-__global__ __launch_bounds__(256) void k_upsample_bilinear_nhwc_f32(const float4* __restrict__ in, float4* __restrict__ out, int ih, int iw,
-                                                                    int oh, int ow, int c4, float sh, float sw, long long total) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % c4);
-  long long r = idx / c4;
-  const int x = (int)(r % ow); r /= ow;
-  const int y = (int)(r % oh);
-  const long long b = r / oh;
-  const float fy = sh * (float)y, fx = sw * (float)x;
-  const int y0 = (int)fy, x0 = (int)fx;
-  const int y1 = y0 + (y0 < ih - 1 ? 1 : 0), x1 = x0 + (x0 < iw - 1 ? 1 : 0);
-  const float ly1 = fy - (float)y0, ly0 = 1.f - ly1, lx1 = fx - (float)x0, lx0 = 1.f - lx1;
-  const float4* base = in + (size_t)b * ih * iw * c4 + c;
-  const float4 p00 = base[((size_t)y0 * iw + x0) * c4], p01 = base[((size_t)y0 * iw + x1) * c4];
-  const float4 p10 = base[((size_t)y1 * iw + x0) * c4], p11 = base[((size_t)y1 * iw + x1) * c4];
-  float4 o;
-  o.x = ly0 * (lx0 * p00.x + lx1 * p01.x) + ly1 * (lx0 * p10.x + lx1 * p11.x);
-  o.y = ly0 * (lx0 * p00.y + lx1 * p01.y) + ly1 * (lx0 * p10.y + lx1 * p11.y);
-  o.z = ly0 * (lx0 * p00.z + lx1 * p01.z) + ly1 * (lx0 * p10.z + lx1 * p11.z);
-  o.w = ly0 * (lx0 * p00.w + lx1 * p01.w) + ly1 * (lx0 * p10.w + lx1 * p11.w);
-  out[idx] = o;
+// float32 variant: one thread = 4 channels (16 B) of one output column in UP_YT consecutive output rows, ATen's association.  The grid runs over
+// (span of UP_SPAN quads along an output row, group of UP_YT rows, image): the row taps (fy, y0, y1, ly0, ly1) and the three row bases are uniform per
+// workgroup and live in scalar registers (64-bit only there), the column taps and every per-thread offset are 32-bit (IT = int; long long only for rows of
+// 2^31 quads and more).  cshift = log2(c4) where c4 is a power of two, else -1 (one 32-bit division).  Same expression as ever, operation for operation:
+// sh * (float)y, (int) truncation, the < ih - 1 clamp, 1.f - l, (ly0 * (lx0 * p00 + lx1 * p01) + ly1 * (lx0 * p10 + lx1 * p11)) [+ bias].
+#define UP_YT 2
+#define UP_SPAN 256
+template <typename IT, bool BIAS>
+VD_DEV void upsample_bilinear_f32_body(const float4* __restrict__ in, const float4* __restrict__ bias, float4* __restrict__ out, int B, int ih, int iw,
+                                       int oh, int ow, int c4, int cshift, float sh, float sw) {
+  const IT e = (IT)blockIdx.x * UP_SPAN + (IT)threadIdx.x;      // quad index inside the output row
+  if (e >= (IT)ow * c4) return;
+  int x, c;
+  if (cshift >= 0) { x = (int)(e >> cshift); c = (int)e & (c4 - 1); }
+  else { x = (int)(e / c4); c = (int)(e - (IT)x * c4); }
+  const float fx = sw * (float)x;
+  const int x0 = (int)fx;
+  const int x1 = x0 + (x0 < iw - 1 ? 1 : 0);
+  const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
+  const IT o0 = (IT)x0 * c4 + c, o1 = (IT)x1 * c4 + c;
+  float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (BIAS) bb = bias[c];
+  for (int b = blockIdx.z; b < B; b += gridDim.z) {
+    for (int yb = blockIdx.y * UP_YT; yb < oh; yb += gridDim.y * UP_YT) {
+      float4 p00[UP_YT], p01[UP_YT], p10[UP_YT], p11[UP_YT];
+      float ly0[UP_YT], ly1[UP_YT];
+#pragma unroll
+      for (int r = 0; r < UP_YT; ++r) {
+        const int y = yb + r < oh ? yb + r : oh - 1;            // a row past the end recomputes the last one and is not stored
+        const float fy = sh * (float)y;
+        const int y0 = __builtin_amdgcn_readfirstlane((int)fy);   // uniform: the row bases below are scalar arithmetic
+        const int y1 = y0 + (y0 < ih - 1 ? 1 : 0);
+        ly1[r] = fy - (float)y0; ly0[r] = 1.f - ly1[r];
+        const float4* r0 = in + ((size_t)b * ih + y0) * iw * c4;
+        const float4* r1 = in + ((size_t)b * ih + y1) * iw * c4;
+        p00[r] = r0[o0]; p01[r] = r0[o1]; p10[r] = r1[o0]; p11[r] = r1[o1];
+      }
+#pragma unroll
+      for (int r = 0; r < UP_YT; ++r) {
+        if (yb + r >= oh) break;
+        float4 o;
+        o.x = ly0[r] * (lx0 * p00[r].x + lx1 * p01[r].x) + ly1[r] * (lx0 * p10[r].x + lx1 * p11[r].x);
+        o.y = ly0[r] * (lx0 * p00[r].y + lx1 * p01[r].y) + ly1[r] * (lx0 * p10[r].y + lx1 * p11[r].y);
+        o.z = ly0[r] * (lx0 * p00[r].z + lx1 * p01[r].z) + ly1[r] * (lx0 * p10[r].z + lx1 * p11[r].z);
+        o.w = ly0[r] * (lx0 * p00[r].w + lx1 * p01[r].w) + ly1[r] * (lx0 * p10[r].w + lx1 * p11[r].w);
+        if (BIAS) { o.x = o.x + bb.x; o.y = o.y + bb.y; o.z = o.z + bb.z; o.w = o.w + bb.w; }
+        (out + ((size_t)b * oh + (yb + r)) * ow * c4)[e] = o;
+      }
+    }
+  }
+}
+template <typename IT>
+__global__ __launch_bounds__(UP_SPAN) void k_upsample_bilinear_nhwc_f32(const float4* __restrict__ in, float4* __restrict__ out, int B, int ih, int iw,
+                                                                        int oh, int ow, int c4, int cshift, float sh, float sw) {
+  upsample_bilinear_f32_body<IT, false>(in, nullptr, out, B, ih, iw, oh, ow, c4, cshift, sh, sw);
+}
+// ... with the producing convolution's bias added to the interpolated value: the interpolation weights sum to one, so up(conv + b) == up(conv) + b;
+// the convolution in front runs without its bias pass.
+template <typename IT>
+__global__ __launch_bounds__(UP_SPAN) void k_upsample_bilinear_bias_nhwc_f32(const float4* __restrict__ in, const float4* __restrict__ bias,
+                                                                             float4* __restrict__ out, int B, int ih, int iw, int oh, int ow, int c4,
+                                                                             int cshift, float sh, float sw) {
+  upsample_bilinear_f32_body<IT, true>(in, bias, out, B, ih, iw, oh, ow, c4, cshift, sh, sw);
+}
+static bool launch_upsample_bilinear_f32(hipStream_t s, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C) {
+  if (C % 4 || oh < 2 || ow < 2) return false;
+  const int c4 = C / 4;
+  const int cshift = (c4 & (c4 - 1)) ? -1 : __builtin_ctz((unsigned)c4);
+  const float sh = (float)(ih - 1) / (float)(oh - 1), sw = (float)(iw - 1) / (float)(ow - 1);   // area_pixel_compute_scale, align_corners
+  const long long rowq = (long long)ow * c4, inq = (long long)iw * c4;                            // quads per output / input row
+  const long long gx = (rowq + UP_SPAN - 1) / UP_SPAN, gy = ((long long)oh + UP_YT - 1) / UP_YT;
+  if (gx > 0x7fffffffll) return false;
+  const dim3 g((unsigned)gx, (unsigned)(gy < 65535 ? gy : 65535), (unsigned)(B < 65535 ? B : 65535));
+  const bool wide = rowq >= (1ll << 31) - UP_SPAN || inq >= (1ll << 31);
+  const float4 *i4 = (const float4*)in, *b4 = (const float4*)bias;
+  float4* o4 = (float4*)out;
+  if (bias) {
+    if (wide) hipLaunchKernelGGL(k_upsample_bilinear_bias_nhwc_f32<long long>, g, dim3(UP_SPAN), 0, s, i4, b4, o4, B, ih, iw, oh, ow, c4, cshift, sh, sw);
+    else hipLaunchKernelGGL(k_upsample_bilinear_bias_nhwc_f32<int>, g, dim3(UP_SPAN), 0, s, i4, b4, o4, B, ih, iw, oh, ow, c4, cshift, sh, sw);
+  } else {
+    if (wide) hipLaunchKernelGGL(k_upsample_bilinear_nhwc_f32<long long>, g, dim3(UP_SPAN), 0, s, i4, o4, B, ih, iw, oh, ow, c4, cshift, sh, sw);
+    else hipLaunchKernelGGL(k_upsample_bilinear_nhwc_f32<int>, g, dim3(UP_SPAN), 0, s, i4, o4, B, ih, iw, oh, ow, c4, cshift, sh, sw);
+  }
+  return true;
 }
 bool vd_launch_upsample_bilinear_nhwc(hipStream_t s, int dtype, const void* in, void* out, int B, int ih, int iw, int oh, int ow, int C) {
-  if (dtype == VD3D_DT_F32) {
-    if (C % 4 || oh < 2 || ow < 2) return false;
-    const int c4 = C / 4;
-    const long long total = (long long)B * oh * ow * c4;
-    const float sh = (float)(ih - 1) / (float)(oh - 1), sw = (float)(iw - 1) / (float)(ow - 1);
-    hipLaunchKernelGGL(k_upsample_bilinear_nhwc_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float4*)in, (float4*)out,
-                       ih, iw, oh, ow, c4, sh, sw, total);
-    return true;
-  }
+  if (dtype == VD3D_DT_F32) return launch_upsample_bilinear_f32(s, (const float*)in, nullptr, (float*)out, B, ih, iw, oh, ow, C);
   if (dtype != VD3D_DT_BF16) return false;
   if (C % 8 || oh < 2 || ow < 2) return false;
   const int c8 = C / 8;
@@ -220,41 +273,9 @@ bool vd_launch_bias_act_f32(hipStream_t s, const float* y, const float* bias, co
   return true;
 }
 
-// k_upsample_bilinear_nhwc_f32 with the producing convolution's bias added to the interpolated value: the interpolation weights sum to one,
-// so up(conv + b) == up(conv) + b; the convolution in front runs without its bias pass.
-__global__ __launch_bounds__(256) void k_upsample_bilinear_bias_nhwc_f32(const float4* __restrict__ in, const float4* __restrict__ bias,
-                                                                         float4* __restrict__ out, int ih, int iw, int oh, int ow, int c4, float sh,
-                                                                         float sw, long long total) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % c4);
-  long long r = idx / c4;
-  const int x = (int)(r % ow); r /= ow;
-  const int y = (int)(r % oh);
-  const long long b = r / oh;
-  const float fy = sh * (float)y, fx = sw * (float)x;
-  const int y0 = (int)fy, x0 = (int)fx;
-  const int y1 = y0 + (y0 < ih - 1 ? 1 : 0), x1 = x0 + (x0 < iw - 1 ? 1 : 0);
-  const float ly1 = fy - (float)y0, ly0 = 1.f - ly1, lx1 = fx - (float)x0, lx0 = 1.f - lx1;
-  const float4* base = in + (size_t)b * ih * iw * c4 + c;
-  const float4 p00 = base[((size_t)y0 * iw + x0) * c4], p01 = base[((size_t)y0 * iw + x1) * c4];
-  const float4 p10 = base[((size_t)y1 * iw + x0) * c4], p11 = base[((size_t)y1 * iw + x1) * c4];
-  const float4 bb = bias[c];
-  float4 o;
-  o.x = (ly0 * (lx0 * p00.x + lx1 * p01.x) + ly1 * (lx0 * p10.x + lx1 * p11.x)) + bb.x;
-  o.y = (ly0 * (lx0 * p00.y + lx1 * p01.y) + ly1 * (lx0 * p10.y + lx1 * p11.y)) + bb.y;
-  o.z = (ly0 * (lx0 * p00.z + lx1 * p01.z) + ly1 * (lx0 * p10.z + lx1 * p11.z)) + bb.z;
-  o.w = (ly0 * (lx0 * p00.w + lx1 * p01.w) + ly1 * (lx0 * p10.w + lx1 * p11.w)) + bb.w;
-  out[idx] = o;
-}
 bool vd_launch_upsample_bilinear_bias_nhwc_f32(hipStream_t s, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C) {
-  if (C % 4 || oh < 2 || ow < 2 || !bias) return false;
-  const int c4 = C / 4;
-  const long long total = (long long)B * oh * ow * c4;
-  const float sh = (float)(ih - 1) / (float)(oh - 1), sw = (float)(iw - 1) / (float)(ow - 1);
-  hipLaunchKernelGGL(k_upsample_bilinear_bias_nhwc_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float4*)in, (const float4*)bias,
-                     (float4*)out, ih, iw, oh, ow, c4, sh, sw, total);
-  return true;
+  if (!bias) return false;
+  return launch_upsample_bilinear_f32(s, in, bias, out, B, ih, iw, oh, ow, C);
 }
 
 // k_head_tail: everything behind the head's second convolution -- its bias, ReLU, the 1x1 convolution to ONE channel (a C-term dot product per

@@ -332,8 +332,9 @@ class Renderer:
                 out.record_stream(ps)
         return out
 
-    def depth_handoff(self, pred: torch.Tensor, H: int, W: int, invert: bool = False, out: torch.Tensor | None = None):
-        """a24 on device: predictions float32 [B,ph,pw] -> uint8 depth planes [B,H,W] (bicubic + per-frame min-max)."""
+    def depth_handoff(self, pred: torch.Tensor, H: int, W: int, invert: bool = False, out: torch.Tensor | None = None, form: int = 0):
+        """a24 on device: predictions float32 [B,ph,pw] -> uint8 depth planes [B,H,W] (bicubic + per-frame min-max).
+        ``form``: 0 = the library's choice, 1 = the general kernel, 2 = the separable up-scaling kernel (vd3d_depth_handoff_form; the same bytes)."""
         p = pred.to(self.device, torch.float32).contiguous()
         if p.dim() == 2:
             p = p[None]
@@ -341,7 +342,7 @@ class Renderer:
         if out is None:
             out = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
         self._enter(p, out)
-        _lib.check(self._L.vd3d_depth_handoff(self._ctx, _ptr(p), B, ph, pw, int(H), int(W), int(bool(invert)), _ptr(out)))
+        _lib.check(self._L.vd3d_depth_handoff_form(self._ctx, _ptr(p), B, ph, pw, int(H), int(W), int(bool(invert)), _ptr(out), int(form)))
         return out
 
     # ---- tiled high-resolution depth (core/render_depth.py:102-194; tables from visiondepth3d_amd.depth_tiles) ----
@@ -801,15 +802,16 @@ class Renderer:
             return DT_BF16
         raise TypeError(f"depth-net glue kernels are built for float32 and bfloat16, not {dtype}")
 
-    def depth_preprocess(self, frames_bgr: torch.Tensor, th: int, tw: int, mean, std, dtype=torch.float32) -> torch.Tensor:
+    def depth_preprocess(self, frames_bgr: torch.Tensor, th: int, tw: int, mean, std, dtype=torch.float32, form: int = 0) -> torch.Tensor:
         """DPT image-processor front end fused in one launch: uint8 BGR [B,H,W,3] -> ``dtype`` tensor of logical shape
-        [B,3,th,tw] in channels_last memory (antialiased bicubic resize, 1/255, ImageNet normalise)."""
+        [B,3,th,tw] in channels_last memory (antialiased bicubic resize, 1/255, ImageNet normalise).
+        ``form``: 0 = the library's choice, 1 = the general tile kernel, 2 = the strip kernel for down-scaling (vd3d_depth_preprocess_form; the same bits)."""
         f = frames_bgr.to(self.device, torch.uint8).contiguous()
         B, H, W, _ = f.shape
         out = torch.empty((B, th, tw, 3), dtype=dtype, device=self.device)
         m = (C.c_float * 3)(*[float(v) for v in mean]); s = (C.c_float * 3)(*[float(v) for v in std])
         self._enter(f, out)
-        _lib.check(self._L.vd3d_depth_preprocess(self._ctx, _ptr(f), B, H, W, int(th), int(tw), m, s, self._dt(dtype), _ptr(out)))
+        _lib.check(self._L.vd3d_depth_preprocess_form(self._ctx, _ptr(f), B, H, W, int(th), int(tw), m, s, self._dt(dtype), _ptr(out), int(form)))
         return out.permute(0, 3, 1, 2)   # NCHW view of NHWC storage == torch.channels_last
 
     def add_layernorm(self, x: torch.Tensor, y, norm: torch.nn.LayerNorm):
