@@ -36,7 +36,8 @@ extern "C" {
  * 4 (round 5): vd3d_render_params::reserved0 became aten_sum_threads (same layout).
  * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32, vd3d_attention_f32_form,
  *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs, vd3d_conv3x3_s2_x3_weight_bytes,
- *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)), vd3d_depth_handoff_form, vd3d_depth_preprocess_form. */
+ *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)), vd3d_depth_handoff_form, vd3d_depth_preprocess_form,
+ *    vd3d_conv3x3_s1_x2_* and vd3d_conv3x3_s2_x2_* (weight_bytes, pack_weights and the convolution each: DepthPipe(conv="fp16x2")). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -572,6 +573,30 @@ int vd3d_conv3x3_x3(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin,
 int64_t vd3d_conv3x3_s2_x3_weight_bytes(int Cin, int Cout);
 int vd3d_conv3x3_s2_x3_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
 int vd3d_conv3x3_s2_x3(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
+/* The two tile convolutions above in the fp16x2 arithmetic of vd3d_gemm_x3 in mode VD3D_X3_FP16X2 -- the convolutions of DepthPipe(gemm="fp16x2",
+ * conv="fp16x2"): the same kernel plan (8 x 32 output tile, every channel count and map size the bf16x3 forms take), the same layouts and rules.
+ *   vd3d_conv3x3_s1_x2  3 x 3, stride 1, zero padding 1: X [B][H][W][Cin] -> Y [B][H][W][Cout], Cout 32, 64, 128 or 256 (256 as two slices of 128).
+ *   vd3d_conv3x3_s2_x2  3 x 3, stride 2, zero padding 1: X [B][H][W][Cin] -> Y [B][(H+1)/2][(W+1)/2][Cout], Cout a positive multiple of 128, at most 1024; the
+ *                       space-to-depth view with no tap on a zero weight, so a non-finite input reaches exactly the outputs whose window holds it.
+ * No bias, groups 1, float32 NHWC in and out, W the module's float32 weight [Cout][Cin][3][3].  Cin a positive multiple of 16 (at most 65 536), H, W >= 1,
+ * 1 <= B <= 65 535, X and the image 16-byte aligned (Y 4-byte); anything else is VD3D_E_UNSUPPORTED with a message that names the rule, and nothing is launched.
+ * Arithmetic contract: 22 significant bits per operand.  x ~ h1 + h2 with h1 = fp16(x), h2 = fp16(x - h1), both round to nearest; the weights of output channel
+ * oc are scaled by 2^e(oc), e = 13 - floor(log2 max |W[oc]|) clamped to [-100, 100] (0 for an all-zero or non-finite channel), and split the same way into g1 + g2,
+ * so that second terms stay normal fp16 numbers.  Three products per MAC on v_mfma_f32_32x32x16_f16: h1 g1 into one float32 accumulator, h1 g2 and h2 g1 into a
+ * second one; h2 g2 is dropped.  The two are summed once and multiplied by 2^-e (exact).  One fixed summation order per output (16-channel chunk, then tap): bit for
+ * bit repeatable and independent of B.  Range: |x| < 65 504; a larger |x|, Inf or NaN makes every output whose window holds it Inf / NaN over all channels -- never a
+ * finite wrong number -- and touches no other output.  |x| below 2^-14 loses its second term gradually (fp16 subnormals are kept, not flushed): the absolute
+ * error per operand stays <= 2^-25.
+ * Weight image, vd3d_conv3x3_s{1,2}_x2_weight_bytes(Cin, Cout) = (Cin / 16) * 9 * Cout * 64 + 4 * Cout + 64 bytes (host-only; < 0: shape not built):
+ *   [slice Cout / CK][K step 9 Cin / 16][term 2][k-half 2][oc CK][8 fp16], CK = min(Cout, 128), K step = (16-channel chunk, tap) in the order a workgroup runs
+ *   them (stride 1: taps row-major; stride 2: the sub-pixel order of vd3d_conv3x3_s2_x3), channel 16 chunk + 8 k-half + element;
+ *   then colscale[Cout] = 2^-e as float32; then a 64-byte zero page.  The image is only valid for this library version. */
+int64_t vd3d_conv3x3_s1_x2_weight_bytes(int Cin, int Cout);
+int vd3d_conv3x3_s1_x2_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
+int vd3d_conv3x3_s1_x2(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
+int64_t vd3d_conv3x3_s2_x2_weight_bytes(int Cin, int Cout);
+int vd3d_conv3x3_s2_x2_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
+int vd3d_conv3x3_s2_x2(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
 
 /* The convolutions of the RIFE interpolation network (IFNet HDv3; RifeSession(conv="bf16x3")) in the same bf16x3 arithmetic: exact three-term truncation
  * split of every float32 operand, the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 into one float32 accumulator and x1 w1 into another, summed in the epilogue

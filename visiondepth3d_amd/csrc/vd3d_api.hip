@@ -1693,6 +1693,47 @@ VD3D_EXPORT int vd3d_conv3x3_s2_x3(vd3d_ctx* c, const float* X, int B, int H, in
   return 0;
 }
 
+// the two tile convolutions in the fp16x2 arithmetic (vd3d_conv_x2t.hip): the rules of their bf16x3 forms, one body for both strides
+static const char* conv_x2t_name(bool s2) { return s2 ? "conv3x3_s2_x2" : "conv3x3_s1_x2"; }
+static long long conv_x2t_bytes(bool s2, int Cin, int Cout) { return s2 ? vd_conv3x3_s2_x2_weight_bytes(Cin, Cout) : vd_conv3x3_s1_x2_weight_bytes(Cin, Cout); }
+static int conv_x2t_shape_err(bool s2, int Cin, int Cout) {
+  return set_err(VD3D_E_UNSUPPORTED, "%s: shape not built: C_in %d must be a positive multiple of 16 (at most 65536) and C_out %d %s", conv_x2t_name(s2), Cin, Cout,
+                 s2 ? "a positive multiple of 128 (at most 1024)" : "one of 32, 64, 128, 256");
+}
+static int conv_x2t_pack(bool s2, vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
+  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  if (conv_x2t_bytes(s2, Cin, Cout) < 0) return conv_x2t_shape_err(s2, Cin, Cout);
+  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "%s: the weight image must be 16-byte aligned", conv_x2t_name(s2));
+  HIPCHK(hipSetDevice(c->device));
+  if (!(s2 ? vd_launch_conv3x3_s2_x2_pack : vd_launch_conv3x3_s1_x2_pack)(c->stream, W, Cin, Cout, image))
+    return set_err(VD3D_E_HIP, "%s: the weight pack launch failed", conv_x2t_name(s2));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+static int conv_x2t_run(bool s2, vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
+  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
+  if (conv_x2t_bytes(s2, Cin, Cout) < 0) return conv_x2t_shape_err(s2, Cin, Cout);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "%s: batch %d must be 1 .. 65535 (one grid row per frame)", conv_x2t_name(s2), B);
+  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "%s: map %d x %d must be at least 1 x 1", conv_x2t_name(s2), H, W);
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "%s: the input and the weight image must be 16-byte aligned (the output 4-byte)", conv_x2t_name(s2));
+  HIPCHK(hipSetDevice(c->device));
+  if (!(s2 ? vd_launch_conv3x3_s2_x2 : vd_launch_conv3x3_s1_x2)(c->stream, X, B, H, W, Cin, w_image, Cout, Y))
+    return set_err(VD3D_E_HIP, "%s: the dynamic LDS opt-in or the launch failed", conv_x2t_name(s2));
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int64_t vd3d_conv3x3_s1_x2_weight_bytes(int Cin, int Cout) { return (int64_t)conv_x2t_bytes(false, Cin, Cout); }
+VD3D_EXPORT int vd3d_conv3x3_s1_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return conv_x2t_pack(false, c, W, Cin, Cout, image); }
+VD3D_EXPORT int vd3d_conv3x3_s1_x2(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
+  return conv_x2t_run(false, c, X, B, H, W, Cin, w_image, Cout, Y);
+}
+VD3D_EXPORT int64_t vd3d_conv3x3_s2_x2_weight_bytes(int Cin, int Cout) { return (int64_t)conv_x2t_bytes(true, Cin, Cout); }
+VD3D_EXPORT int vd3d_conv3x3_s2_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return conv_x2t_pack(true, c, W, Cin, Cout, image); }
+VD3D_EXPORT int vd3d_conv3x3_s2_x2(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
+  return conv_x2t_run(true, c, X, B, H, W, Cin, w_image, Cout, Y);
+}
+
 // the convolutions of the interpolation network (vd3d_conv_ifn.hip): every rule of include/vd3d.h is checked here, before anything is launched
 VD3D_EXPORT int64_t vd3d_conv_ifn_weight_bytes(int kind, int Cin, int Cout) { return (int64_t)vd_conv_ifn_weight_bytes(kind, Cin, Cout); }
 

@@ -19,7 +19,7 @@ bool vd_launch_conv3x3_s2_x3(hipStream_t s, const float* X, int B, int H, int W,
   const uint8_t* wi = reinterpret_cast<const uint8_t*>(wimg);
   a.X = X; a.Wimg = wi; a.zero16 = reinterpret_cast<const float*>(wi + wb - 64); a.bias = nullptr; a.slope = nullptr; a.R = nullptr; a.Y = Y;
   a.B = B; a.H = H; a.W = W; a.Ho = (H + 1) / 2; a.Wo = (W + 1) / 2;
-  a.x_stride = Cin; a.y_stride = Cout; a.y_offset = 0; a.r_stride = 0; a.nchunk = Cin / 16;
+  a.x_stride = Cin; a.y_stride = Cout; a.y_offset = 0; a.r_stride = 0; a.nchunk = Cin / 16; a.colscale = nullptr;
   a.ntx = (a.Wo + CX_TW - 1) / CX_TW;   // the tile grid is the output
   const dim3 grid((unsigned)(a.ntx * ((a.Ho + CX_TH - 1) / CX_TH)), (unsigned)B, (unsigned)(Cout / 128));
   hipLaunchKernelGGL((k_conv_x3<CX_K3S2, 4, 2, false>), grid, dim3(CX_NT), cx_lds(128), s, a);

@@ -1,6 +1,10 @@
 // vd3d_conv_x3.h -- the tile-convolution kernel of vd3d_conv_x3.hip (its header comment describes the plan): the LDS layout constants, the argument block and
-// k_conv_x3 itself, shared by the translation units that instantiate it: vd3d_conv_x3.hip (vd3d_conv3x3_x3, vd3d_conv_ifn) and vd3d_conv_s2.hip
-// (vd3d_conv3x3_s2_x3).
+// the kernel body cx_conv<MODE, ...>, shared by the translation units that instantiate it: vd3d_conv_x3.hip (vd3d_conv3x3_x3, vd3d_conv_ifn) and vd3d_conv_s2.hip
+// (vd3d_conv3x3_s2_x3) as k_conv_x3 = MODE 0 (bf16x3), vd3d_conv_x2t.hip (vd3d_conv3x3_s1_x2, vd3d_conv3x3_s2_x2) as k_conv_x2 = MODE 1 (fp16x2, vd3d_x3.h).
+// MODE 1 differs in four places and nowhere else: two operand terms instead of three (a chunk image of 2 x 2 planes = 21 760 bytes, a K step of 64 CK bytes:
+// one DMA round per stage for every CK), the round-to-nearest fp16 split of the staged pixels, three products per K step (x1 w2, x2 w1 into `lo`, x1 w1 into `acc`;
+// x2 w2 dropped) on v_mfma_f32_32x32x16_f16, and an epilogue that multiplies acc + lo by colscale[oc], the exact power of two the packer divided the channel's
+// weights by.  The DMA counts behind the counted waits are NBP and CX_A_ITERS in both modes (the staging buffer is float32 either way).
 #pragma once
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
@@ -21,6 +25,14 @@
 __host__ __device__ constexpr int cx_b_stage(int ck) { return (3 * 2 * ck * 16 + 8191) / 8192 * 8192; }   // 8 192 (32, 64), 16 384 (96, 128)
 #define CX_B_OFF (2 * CX_A_BUF + CX_A_STG)
 __host__ __device__ constexpr int cx_lds(int ck) { return CX_B_OFF + CX_NS * cx_b_stage(ck); }
+// the same plan by MODE (0: the numbers above)
+__host__ __device__ constexpr int cx_terms(int mode) { return mode == 0 ? 3 : 2; }
+__host__ __device__ constexpr int cx_a_buf(int mode) { return cx_terms(mode) * 2 * CX_PLANE; }                // 32 640 | 21 760
+__host__ __device__ constexpr int cx_b_step(int mode, int ck) { return cx_terms(mode) * 2 * ck * 16; }       // 96 CK | 64 CK bytes
+__host__ __device__ constexpr int cx_b_stage_m(int mode, int ck) { return (cx_b_step(mode, ck) + 8191) / 8192 * 8192; }   // MODE 1: 8 192 for every CK
+__host__ __device__ constexpr int cx_b_off(int mode) { return 2 * cx_a_buf(mode) + CX_A_STG; }               // 89 856 | 68 096
+__host__ __device__ constexpr int cx_lds_m(int mode, int ck) { return cx_b_off(mode) + CX_NS * cx_b_stage_m(mode, ck); }   // MODE 1: 100 864
+static_assert(cx_a_buf(0) == CX_A_BUF && cx_b_off(0) == CX_B_OFF && cx_lds_m(0, 128) == cx_lds(128) && cx_lds_m(0, 32) == cx_lds(32), "MODE 0 is the plan above");
 
 enum { CX_K3S1 = 0, CX_K3S2 = 1, CX_T4S2 = 2 };   // include/vd3d.h VD3D_IFN_*
 
@@ -31,14 +43,17 @@ struct vd_cx_args {
   int x_stride, y_stride, y_offset, r_stride;
   int ntx;                  // tiles per row of the tile grid
   int nchunk;               // C_in / 16
+  const float* colscale;    // MODE 1: 2^-e per output channel (the weight image holds 2^e W); MODE 0: not read
 };
 
 // EPI: the entry points' thin variants of the one body.  true (vd3d_conv_ifn): + bias (never null there), optional slope and residual, at most 96 output
 // channels.  false (vd3d_conv3x3_x3: K3S1; vd3d_conv3x3_s2_x3: K3S2): the bare sum -- nothing is added, not even a zero -- and CK-channel slices of C_out on
 // the grid's z axis (K3S1: 256 as two slices of 128; K3S2: 128 n as n slices).
-template <int KIND, int WM, int NWN, bool EPI>
-__global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
-  constexpr int NS = CX_NS, WN = 8 / WM, MR = CX_TH / WM, CK = 32 * WN * NWN, BST = cx_b_stage(CK), NBP = BST / (CX_NT * 16), B_ITEMS = 6 * CK;
+template <int MODE, int KIND, int WM, int NWN, bool EPI>
+VD_DEV void cx_conv(const vd_cx_args a) {
+  constexpr int NTM = cx_terms(MODE), A_BUF = cx_a_buf(MODE), B_OFF = cx_b_off(MODE);
+  constexpr int NS = CX_NS, WN = 8 / WM, MR = CX_TH / WM, CK = 32 * WN * NWN, BST = cx_b_stage_m(MODE, CK), NBP = BST / (CX_NT * 16), B_ITEMS = 2 * NTM * CK;
+  static_assert(MODE == 0 || !EPI, "the fp16x2 form has the bare epilogue only");
   constexpr int A_FLY = NS - 2;   // the taps of a chunk whose counted wait leaves the next chunk's pixel DMAs in flight
   constexpr int SUBS = KIND == CX_K3S2 ? 4 : 1, ST = KIND == CX_K3S2 ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) uint8_t cx_smem[];   // the only LDS object: [A buffer 0][A buffer 1][float32 staging][B ring]
@@ -74,37 +89,47 @@ __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
       const int gy = ST * aty[it] + sy, gx = ST * atx[it] + sx;
       const bool in = gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
       const float* p = in ? xb + ((size_t)gy * a.W + gx) * a.x_stride + c16 * 16 : a.zero16;
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)p, (x3_lds_vp)(cx_smem + 2 * CX_A_BUF + it * (CX_NT * 16) + wave_base), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)p, (x3_lds_vp)(cx_smem + 2 * A_BUF + it * (CX_NT * 16) + wave_base), 16, 0, 0);
     }
   };
-  auto write_a = [&](int buf) {   // staging (float32) -> exact three-term split -> three 8-byte LDS stores per item
-    uint8_t* dst = cx_smem + buf * CX_A_BUF;
-    const uint8_t* stg = cx_smem + 2 * CX_A_BUF + tid * 16;
+  auto write_a = [&](int buf) {   // staging (float32) -> exact three-term split (MODE 1: round-to-nearest two-term split) -> one 8-byte LDS store per term and item
+    uint8_t* dst = cx_smem + buf * A_BUF;
+    const uint8_t* stg = cx_smem + 2 * A_BUF + tid * 16;
 #pragma unroll
     for (int it = 0; it < CX_A_ITERS; ++it) {
       const x3_s8 raw = *reinterpret_cast<const x3_s8*>(stg + it * (CX_NT * 16));   // a short vector, bit-cast: not ordered behind the DMAs in flight (vd3d_x3.h)
       const float4 f = __builtin_bit_cast(float4, raw);
-      uint32_t t1[4], t2[4], t3[4];
-      x3_split(f.x, t1[0], t2[0], t3[0]); x3_split(f.y, t1[1], t2[1], t3[1]); x3_split(f.z, t1[2], t2[2], t3[2]); x3_split(f.w, t1[3], t2[3], t3[3]);
-      if (adst[it] >= 0) {
-        *reinterpret_cast<x3_u2*>(dst + adst[it]) = x3_u2{x3_pack(t1[0], t1[1]), x3_pack(t1[2], t1[3])};
-        *reinterpret_cast<x3_u2*>(dst + 2 * CX_PLANE + adst[it]) = x3_u2{x3_pack(t2[0], t2[1]), x3_pack(t2[2], t2[3])};
-        *reinterpret_cast<x3_u2*>(dst + 4 * CX_PLANE + adst[it]) = x3_u2{x3_pack(t3[0], t3[1]), x3_pack(t3[2], t3[3])};
+      if constexpr (MODE == 1) {
+        const float v[4] = {f.x, f.y, f.z, f.w};
+        x3_h4 h1, h2;
+        x3_split4_h(v, h1, h2);
+        if (adst[it] >= 0) {
+          *reinterpret_cast<x3_h4*>(dst + adst[it]) = h1;
+          *reinterpret_cast<x3_h4*>(dst + 2 * CX_PLANE + adst[it]) = h2;
+        }
+      } else {
+        uint32_t t1[4], t2[4], t3[4];
+        x3_split(f.x, t1[0], t2[0], t3[0]); x3_split(f.y, t1[1], t2[1], t3[1]); x3_split(f.z, t1[2], t2[2], t3[2]); x3_split(f.w, t1[3], t2[3], t3[3]);
+        if (adst[it] >= 0) {
+          *reinterpret_cast<x3_u2*>(dst + adst[it]) = x3_u2{x3_pack(t1[0], t1[1]), x3_pack(t1[2], t1[3])};
+          *reinterpret_cast<x3_u2*>(dst + 2 * CX_PLANE + adst[it]) = x3_u2{x3_pack(t2[0], t2[1]), x3_pack(t2[2], t2[3])};
+          *reinterpret_cast<x3_u2*>(dst + 4 * CX_PLANE + adst[it]) = x3_u2{x3_pack(t3[0], t3[1]), x3_pack(t3[2], t3[3])};
+        }
       }
     }
   };
-  // ---- B staging: the slice's K steps are contiguous in the packed image, [step][term 3][k-half 2][oc CK][8 bf16]; item i = p * 512 + tid is 16 bytes of a
-  // step; the items behind the step's 96 CK bytes read the zero page
+  // ---- B staging: the slice's K steps are contiguous in the packed image, [step][term NTM][k-half 2][oc CK][8 bf16 | fp16]; item i = p * 512 + tid is 16 bytes
+  // of a step; the items behind the step's 96 CK (MODE 1: 64 CK) bytes read the zero page
   const int NCH = a.nchunk * SUBS;
   const int KS = KIND == CX_T4S2 ? a.nchunk * 4 : a.nchunk * 9;
-  const size_t bstep = (size_t)CK * 96;
+  const size_t bstep = (size_t)cx_b_step(MODE, CK);
   const uint8_t* wbase = a.Wimg + (SLICED ? (size_t)slice * KS * bstep : (size_t)0);
   auto stage_b = [&](int ks, int slot) {
 #pragma unroll
     for (int p = 0; p < NBP; ++p) {
       const int i = p * CX_NT + tid;
       const uint8_t* src = i < B_ITEMS ? wbase + (size_t)ks * bstep + i * 16 : reinterpret_cast<const uint8_t*>(a.zero16);
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)src, (x3_lds_vp)(cx_smem + CX_B_OFF + slot * BST + p * (CX_NT * 16) + wave_base), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((x3_glb_vp)src, (x3_lds_vp)(cx_smem + B_OFF + slot * BST + p * (CX_NT * 16) + wave_base), 16, 0, 0);
     }
   };
 
@@ -129,12 +154,12 @@ __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
 
   // fragment base offsets: A: k-half plane, tile row MR wm + m (+ 1 halo + dy), column li (+ 1 + dx); B: k-half plane, output channel (wn * NWN + n) * 32 + li
   const int fa_base = (kh * CX_NPIX + (MR * wm + 1) * CX_PW + li + 1) * 16;
-  const int fb_base = CX_B_OFF + (kh * CK + wn * NWN * 32 + li) * 16;
+  const int fb_base = B_OFF + (kh * CK + wn * NWN * 32 + li) * 16;
   int ks = 0;
   for (int chunk = 0; chunk < NCH; ++chunk) {
     const bool more_a = chunk + 1 < NCH;   // uniform
     if (more_a) load_a(chunk + 1);
-    const uint8_t* sa = cx_smem + (chunk & 1) * CX_A_BUF;
+    const uint8_t* sa = cx_smem + (chunk & 1) * A_BUF;
     const int sy = KIND == CX_K3S2 ? (chunk >> 1) & 1 : 0, sx = KIND == CX_K3S2 ? chunk & 1 : 0;
     const int T = KIND == CX_K3S1 ? 9 : KIND == CX_T4S2 ? 4 : (1 + sy) * (1 + sx);
 #pragma unroll 1
@@ -147,19 +172,20 @@ __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
       stage_b(ks + NS - 1 < KS ? ks + NS - 1 : KS - 1, (ks + NS - 1) % NS);   // behind the last step: a harmless re-fetch (straight-line code, one counted wait)
       const uint8_t* sb = cx_smem + slot * BST;
       const uint8_t* sat = sa + fa_base + (dy * CX_PW + dx) * 16;
-      x3_s8 af[MR][3];
+      x3_s8 af[MR][NTM];
 #pragma unroll
       for (int m = 0; m < MR; ++m)
 #pragma unroll
-        for (int t = 0; t < 3; ++t) af[m][t] = *reinterpret_cast<const x3_s8*>(sat + t * (2 * CX_PLANE) + m * (CX_PW * 16));
+        for (int t = 0; t < NTM; ++t) af[m][t] = *reinterpret_cast<const x3_s8*>(sat + t * (2 * CX_PLANE) + m * (CX_PW * 16));
 #pragma unroll
       for (int n = 0; n < NWN; ++n) {
-        x3_s8 bf[3];
+        x3_s8 bf[NTM];
 #pragma unroll
-        for (int t = 0; t < 3; ++t) bf[t] = *reinterpret_cast<const x3_s8*>(sb + fb_base + t * (2 * CK * 16) + n * 512);
+        for (int t = 0; t < NTM; ++t) bf[t] = *reinterpret_cast<const x3_s8*>(sb + fb_base + t * (2 * CK * 16) + n * 512);
         // small products first, into their own accumulator; the M tiles alternate so that dependent MFMAs are not back to back
-#define CX_MM(ACC, ta, tb) _Pragma("unroll") for (int m = 0; m < MR; ++m) ACC[m][n] = x3_mfma<0>(af[m][ta], bf[tb], ACC[m][n]);
-        CX_MM(lo, 0, 2) CX_MM(lo, 2, 0) CX_MM(lo, 1, 1) CX_MM(lo, 0, 1) CX_MM(lo, 1, 0) CX_MM(acc, 0, 0)
+#define CX_MM(ACC, ta, tb) _Pragma("unroll") for (int m = 0; m < MR; ++m) ACC[m][n] = x3_mfma<MODE>(af[m][ta], bf[tb], ACC[m][n]);
+        if constexpr (MODE == 0) { CX_MM(lo, 0, 2) CX_MM(lo, 2, 0) CX_MM(lo, 1, 1) CX_MM(lo, 0, 1) CX_MM(lo, 1, 0) CX_MM(acc, 0, 0) }
+        else { CX_MM(lo, 0, 1) CX_MM(lo, 1, 0) CX_MM(acc, 0, 0) }   // x1 w2, x2 w1; x1 w1
 #undef CX_MM
       }
       // Counted wait.  In flight, oldest first: B (ks + 1) .. B (ks + NS - 1), with the next chunk's CX_A_ITERS pixel DMAs issued in front of this chunk's tap 0
@@ -187,6 +213,8 @@ __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
     const int oc = oc0 + (wn * NWN + n) * 32 + li;
     float bv = 0.f, sv = 1.f;
     if constexpr (EPI) { bv = a.bias[oc]; sv = a.slope ? a.slope[oc] : 1.f; }
+    float cs = 1.f;
+    if constexpr (MODE == 1) { cs = a.colscale[oc]; asm volatile("" : "+v"(cs)); }   // consumed in front of the masked stores (vd3d_gemm.hip: else one s_waitcnt vmcnt(0) per store)
 #pragma unroll
     for (int m = 0; m < MR; ++m) {
       const int ty = y0 + MR * wm + m;
@@ -197,6 +225,7 @@ __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
         if (oy < a.Ho && ox < a.Wo) {
           const size_t pix = ((size_t)b * a.Ho + oy) * a.Wo + ox;
           float v = acc[m][n][r] + lo[m][n][r];
+          if constexpr (MODE == 1) v *= cs;
           if constexpr (EPI) {
             v += bv;
             if (a.slope) v = v >= 0.f ? v : sv * v;
@@ -208,3 +237,9 @@ __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) {
     }
   }
 }
+
+// the bf16x3 kernel of vd3d_conv_x3.hip / vd3d_conv_s2.hip / vd3d_conv_ifn.hip and the fp16x2 kernel of vd3d_conv_x2t.hip
+template <int KIND, int WM, int NWN, bool EPI>
+__global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) { cx_conv<0, KIND, WM, NWN, EPI>(a); }
+template <int KIND, int WM, int NWN>
+__global__ __launch_bounds__(CX_NT) void k_conv_x2(const vd_cx_args a) { cx_conv<1, KIND, WM, NWN, false>(a); }

@@ -3,7 +3,8 @@
 //   vd3d_conv_ifn    the convolutions of the RIFE interpolation network (IFNet HDv3: three IFBlocks of 14; C_out 32 / 64 / 96; bias, per-channel PReLU and
 //                    residual in the epilogue, channel slices of strided NHWC buffers).
 // and a third one, vd3d_conv3x3_s2_x3 (the reassemble stage's 3 x 3 stride-2 convolution, C_out = 128 n), whose launch is vd3d_conv_s2.hip's and whose weight
-// image is packed here.
+// image is packed here.  The kernel body (cx_conv, vd3d_conv_x3.h) carries a MODE parameter; everything in this file is MODE 0, the fp16x2 form (MODE 1) is
+// vd3d_conv_x2t.hip's.
 // Arithmetic: every float32 operand is split EXACTLY into three bf16 terms by truncation (x3_split); the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 go into a `lo`
 // accumulator and x1 w1 into `acc` (v_mfma_f32_32x32x16_bf16, float32 accumulation, small products first), summed in the epilogue; x2 w3, x3 w2, x3 w3 <= 2^-24
 // relative are dropped, as in the GEMM.  Float32 NHWC in and out, no weight pre-scaling, no range limit, NaN / Inf in gives NaN out.
@@ -117,7 +118,7 @@ static bool cx_launch(hipStream_t s, bool epi, int kind, const float* X, int B, 
   a.B = B; a.H = H; a.W = W;
   a.Ho = kind == CX_K3S2 ? (H + 1) / 2 : kind == CX_T4S2 ? 2 * H : H;
   a.Wo = kind == CX_K3S2 ? (W + 1) / 2 : kind == CX_T4S2 ? 2 * W : W;
-  a.x_stride = x_stride; a.y_stride = y_stride; a.y_offset = y_offset; a.r_stride = r_stride; a.nchunk = Cin / 16;
+  a.x_stride = x_stride; a.y_stride = y_stride; a.y_offset = y_offset; a.r_stride = r_stride; a.nchunk = Cin / 16; a.colscale = nullptr;
   const int gh = kind == CX_K3S2 ? a.Ho : H, gw = kind == CX_K3S2 ? a.Wo : W;   // the tile grid
   a.ntx = (gw + CX_TW - 1) / CX_TW;
   const dim3 grid((unsigned)(a.ntx * ((gh + CX_TH - 1) / CX_TH)), (unsigned)B, kind == CX_T4S2 ? 4u : 1u);

@@ -244,6 +244,13 @@ bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, in
 long long vd_conv3x3_s2_x3_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_s2_x3_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_s2_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+// vd3d_conv_x2t.hip: the two tile convolutions above in the fp16x2 arithmetic (two fp16 terms, three products; weights pre-scaled per output channel)
+long long vd_conv3x3_s1_x2_weight_bytes(int Cin, int Cout);
+bool vd_launch_conv3x3_s1_x2_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
+bool vd_launch_conv3x3_s1_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+long long vd_conv3x3_s2_x2_weight_bytes(int Cin, int Cout);
+bool vd_launch_conv3x3_s2_x2_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
+bool vd_launch_conv3x3_s2_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
 // vd3d_conv_head.hip: conv3x3(up(x) + b_in) [+ the head's tail] in exact float32 (v_mfma_f32_32x32x2_f32); b2 == nullptr: plain NHWC output
 long long vd_dpt_head_conv_weight_bytes(int Cin, int Cout);
 bool vd_launch_dpt_head_conv_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);

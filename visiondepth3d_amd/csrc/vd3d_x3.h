@@ -7,7 +7,7 @@
 // (x1 + x2 + x3)(w1 + w2 + w3), each exact in float32, the kernels keep six and drop x2 w3 + x3 w2 + x3 w3 <= 2^-23 |x w| (the size of one float32 rounding).
 // fp16x2 (MODE 1).  a ~ h1 + h2 with h1 = fp16(a), h2 = fp16(a - h1), both round-to-nearest: 22 significant bits, |a - h1 - h2| <= 2^-22 |a| while h2 stays a
 // normal fp16 number (|a| >= 2^-2 for unscaled data; below that the absolute error is <= 2^-25).  |a| must stay below 65 504: the callers scale by exact powers of
-// two where their data needs it (weight rows in the GEMM and vd3d_conv2.hip, q / k / v and the probabilities in the attention).
+// two where their data needs it (weight rows in the GEMM, vd3d_conv2.hip and vd3d_conv_x2t.hip, q / k / v and the probabilities in the attention).
 #pragma once
 #include "vd3d_dev.h"
 

@@ -181,6 +181,14 @@ def _tunable_scratch_dir() -> str:
 # fewer (the 19 x 33 and 37 x 66 maps, where the library's split-K kernels fill the chip) in 1.06 - 2.76 of it; nothing was measured in between, so the rule
 # is the smallest size that won.
 CONV_X3_MIN_TILES = 200
+# DepthPipe(gemm="fp16x2", conv="fp16x2") without self_contained: a 3 x 3 convolution takes vd3d_conv3x3_s1_x2 from this many 8 x 32 output tiles PER FRAME;
+# below it the float32 library convolution stays.  The rule reads the map (and, through the weight image, the module), never the batch size: a frame's routes and
+# bits do not depend on what it is batched with.  Measured on the DA-V2-Small / -Base / -Large neck, fusion and head shapes at the 4K patch grid, one frame
+# and sixteen (tools/probe_fp16x2_self_contained.py --shapes, profiles/r18_fp16x2_self_contained.md; MIOpen find mode on), as kernel / library time: 171 tiles
+# and more 0.39 - 0.71 at both batch sizes; 50 tiles (74 x 132) 0.45 - 0.73 at sixteen frames and 0.86 - 1.20 at one (break-even: four shapes win, two lose);
+# 15 tiles (37 x 66) 0.49 - 0.63 at sixteen frames but 0.96 - 2.99 at one; 6 tiles 0.76 - 8.37.  Nothing was measured between 15 and 50, so the rule is the
+# smallest size that did not lose on balance at one frame -- the batch a batch-blind rule has to be safe for.
+CONV_X2_MIN_TILES = 50
 
 
 class DepthPipe:
@@ -211,7 +219,11 @@ class DepthPipe:
         two (DA and DPT-Large alike) -- run on ``vd3d_conv3x3_x3``, the same three-term / six-product arithmetic as the GEMM (include/vd3d.h), for 32 / 64 /
         128 / 256 output channels and input channels in multiples of 16.  Maps below the measured launch-size rule (``CONV_X3_MIN_TILES``) stay on the
         library; nothing else falls back.  ``conv_routes`` (module name -> ("bf16x3" | "library", reason)) records, per forward, where each of these
-        convolutions ran and why.  In the default float32 mode (``gemm="f32"``, ``conv=None``, with a renderer) the head's up-sampling, its second
+        convolutions ran and why.  ``"fp16x2"`` -- OPT-IN, only with ``gemm="fp16x2"`` (else ValueError): the same convolutions, for the same channel
+        counts, on ``vd3d_conv3x3_s1_x2`` -- the same 8 x 32 tile kernel in the two-term fp16 arithmetic of the mode (three products per MAC, weights
+        pre-scaled per output channel by an exact power of two, |x| < 65 504).  One kernel takes every routed convolution (``vd3d_conv3x3_x2`` stays the route
+        of ``conv=None``); maps below ``CONV_X2_MIN_TILES`` tiles PER FRAME stay on the library -- the rule reads the map and the module, never the batch
+        size; ``conv_routes`` reads ("fp16x2" | "library", reason).  In the default float32 mode (``gemm="f32"``, ``conv=None``, with a renderer) the head's up-sampling, its second
         convolution and everything behind it run as ONE exact-float32 MFMA launch (``vd3d_dpt_head_conv_f32``: 32 | 64 | 128 -> 32 channels);
         ``conv_routes["head.conv2"]`` is then ``("f32-fused", ...)``, or ``("library", reason)`` where the three launches stay (a shape that is not
         built, ``VD3D_HEAD_FUSED=0``).
@@ -225,7 +237,7 @@ class DepthPipe:
         find mode (``torch.backends.cudnn.benchmark``) -- every convolution shape times its applicable solvers once, ~25 s at the
         first forward of a process, 4.5 % on the 4K float32 forward (profiles/r04_net_library_selection.md); opt-in, bench.py uses it.
         The flag is PyTorch's process-wide one: True / False set it, None (default) leaves it as the caller has it.
-        ``self_contained``: ``False`` (default) -- everything above.  ``True`` -- OPT-IN, only with ``gemm="bf16x3"``, ``conv="bf16x3"``, float32, a renderer on a
+        ``self_contained``: ``False`` (default) -- everything above.  ``True`` -- OPT-IN, only with ``gemm="bf16x3"``, ``conv="bf16x3"`` or ``gemm="fp16x2"``, ``conv="fp16x2"``, float32, a renderer on a
         GPU and ``fuse_backbone=True`` (else ValueError naming what is missing), and only for ``DepthAnythingForDepthEstimation`` on ``Dinov2Backbone`` (else
         NotImplementedError naming the model): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
         as ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, the reassemble stage's 1 x 1 projections as ``vd3d_gemm_x3`` over the token rows, its transposed
@@ -234,21 +246,26 @@ class DepthPipe:
         mode cannot route is refused by name, never handed to a library.  ``conv_routes`` names every routed module and holds no ``"library"`` value.  The
         library selection is skipped: TunableOp is not enabled, ``torch.backends.cudnn.benchmark`` is not touched, ``tuned_gemm`` / ``miopen_find`` read
         False.  Per output element every kernel sums in one fixed order and nothing is split along K, so a frame's prediction does not depend on the batch it
-        is in or on the ROCm release's solution tables."""
+        is in or on the ROCm release's solution tables.  With the fp16x2 pair every route above takes that mode's kernels (``vd3d_gemm_x3`` and
+        ``vd3d_attention_x3`` in mode fp16x2, ``vd3d_conv3x3_s2_x2``, ``vd3d_conv3x3_s1_x2``), the route labels read ``("fp16x2", "self-contained...")`` and
+        the mode's range contract holds in front of every one of them.  DPT-Large stays refused by name under the keyword."""
         self.name, self.device, self.dtype = name, torch.device(device), dtype
         if gemm not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
-        if conv not in (None, "bf16x3"):
-            raise ValueError("conv must be None or 'bf16x3'")
+        if conv not in (None, "bf16x3", "fp16x2"):
+            raise ValueError("conv must be None, 'bf16x3' or 'fp16x2'")
         if self_contained:
-            missing = [what for what, ok in (("gemm='bf16x3'", gemm == "bf16x3"), ("conv='bf16x3'", conv == "bf16x3"), ("dtype=torch.float32", dtype == torch.float32),
+            # the two pairs of the mode; the bf16x3 pair leads the wording, a half-given bf16x3 pair names its missing half alone
+            pair = (gemm, conv) in (("bf16x3", "bf16x3"), ("fp16x2", "fp16x2"))
+            missing = [what for what, ok in (("gemm='bf16x3', conv='bf16x3' (or gemm='fp16x2', conv='fp16x2')", pair or gemm == "bf16x3"),
+                                             ("conv='bf16x3'", pair or gemm != "bf16x3"), ("dtype=torch.float32", dtype == torch.float32),
                                              ("a renderer on a GPU", renderer is not None and torch.device(device).type == "cuda"),
                                              ("fuse_backbone=True", bool(fuse_backbone)),
                                              ("the neck glue launches (VD3D_NECK_GLUE=0 is set)", os.environ.get("VD3D_NECK_GLUE", "1") != "0")) if not ok]
             if missing:
                 raise ValueError("self_contained=True needs " + ", ".join(missing))
-        if conv == "bf16x3" and gemm != "bf16x3":
-            raise ValueError("conv='bf16x3' is the convolution half of gemm='bf16x3' and needs that mode")
+        if conv is not None and gemm != conv:
+            raise ValueError(f"conv={conv!r} is the convolution half of gemm={conv!r} and needs that mode")
         if gemm != "f32" and (dtype != torch.float32 or renderer is None or torch.device(device).type != "cuda"):
             raise ValueError("gemm='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
         self.gemm, self.conv, self.self_contained = gemm, conv, bool(self_contained)
@@ -272,7 +289,7 @@ class DepthPipe:
         if self.self_contained and not (self.arch == "da" and type(model.backbone).__name__ == "Dinov2Backbone"):
             bname = type(getattr(model, "backbone", None)).__name__ if getattr(model, "backbone", None) is not None else "its own encoder"
             raise NotImplementedError(f"self_contained=True: {name!r} ({type(model).__name__} on {bname}) -- the mode is built for DepthAnythingForDepthEstimation "
-                                      "on Dinov2Backbone (Depth-Anything V1 / V2, Distill-Any-Depth) only; DPT-Large keeps gemm='bf16x3' without it")
+                                      "on Dinov2Backbone (Depth-Anything V1 / V2, Distill-Any-Depth) only; DPT-Large keeps the split modes without it")
         if self.self_contained:
             bc = model.config.backbone_config
             if int(bc.hidden_size) not in (384, 768, 1024) or int(bc.hidden_size) != 64 * int(bc.num_attention_heads):
@@ -403,7 +420,7 @@ class DepthPipe:
         conv_img = {}   # fp16x2 mode: packed weights per convolution module (None = shape not built: the library convolution stays)
 
         def conv_x2(m, x):
-            if (self.gemm != "fp16x2" or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
+            if (self.gemm != "fp16x2" or self.conv is not None or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
                     or x.dtype != torch.float32):
                 return None
             key = id(m)
@@ -416,32 +433,40 @@ class DepthPipe:
                 return None
             return R.conv3x3_x2(x.contiguous(memory_format=CL), conv_img[key], m.out_channels)
 
-        conv3_img = {}   # conv="bf16x3": packed weights per convolution module (None = shape not built)
+        conv3_img = {}   # conv="bf16x3" / "fp16x2": packed weights per convolution module (None = shape not built)
         names = {id(m): n for n, m in self.model.named_modules()}
+        cm = self.conv   # the tile convolution of the mode: vd3d_conv3x3_x3 | vd3d_conv3x3_s1_x2, one kernel for every routed convolution
+        tile_fn, min_tiles = ("conv3x3_s1_x2", CONV_X2_MIN_TILES) if cm == "fp16x2" else ("conv3x3_x3", CONV_X3_MIN_TILES)   # Renderer methods, looked up per call
+
+        def tile_conv(x, img, n):
+            return getattr(R, tile_fn)(x, img, n)
 
         def conv_x3(m, x):
-            if (self.conv != "bf16x3" or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
+            if (cm is None or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
                     or x.dtype != torch.float32):
                 return None
             key = id(m)
             if key not in conv3_img:
-                conv3_img[key] = R.conv3x3_x3_pack(m.weight)
+                conv3_img[key] = getattr(R, tile_fn + "_pack")(m.weight)
             if conv3_img[key] is None:
                 if sc:
-                    raise NotImplementedError(f"self_contained=True: {names[key]}: vd3d_conv3x3_x3 does not build {m.in_channels} -> {m.out_channels} channels")
+                    raise NotImplementedError(f"self_contained=True: {names[key]}: vd3d_{tile_fn} does not build {m.in_channels} -> {m.out_channels} channels")
                 self.conv_routes[names[key]] = ("library", f"shape not built: {m.in_channels} -> {m.out_channels} channels")
                 return None
             if sc:   # no size rule: every map, the 19 x 33 ones included
-                self.conv_routes[names[key]] = ("bf16x3", "self-contained")
-                return R.conv3x3_x3(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
-            tiles = x.shape[0] * ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)   # one workgroup per 8 x 32 output tile
-            if tiles < CONV_X3_MIN_TILES:
-                self.conv_routes[names[key]] = ("library", f"size rule: {tiles} tiles < {CONV_X3_MIN_TILES}")
+                self.conv_routes[names[key]] = (cm, "self-contained")
+                return tile_conv(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
+            if cm == "fp16x2":   # the rule of this mode reads the map alone, never the batch: a frame's route and bits do not depend on what it is batched with
+                tiles = ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)
+            else:
+                tiles = x.shape[0] * ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)   # one workgroup per 8 x 32 output tile
+            if tiles < min_tiles:
+                self.conv_routes[names[key]] = ("library", f"size rule: {tiles} tiles < {min_tiles}")
                 return None
-            self.conv_routes[names[key]] = ("bf16x3", f"{tiles} tiles")
-            return R.conv3x3_x3(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
+            self.conv_routes[names[key]] = (cm, f"{tiles} tiles")
+            return tile_conv(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
 
-        if self.conv == "bf16x3" and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
+        if cm is not None and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
             for m in self.model.neck.convs:
                 if sc and m.bias is not None:
                     raise NotImplementedError(f"self_contained=True: {names[id(m)]} has a bias (the stock neck convolutions have none) -- not built")
@@ -472,10 +497,10 @@ class DepthPipe:
             if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.padding != (0, 0) or m.groups != 1 or m.in_channels % 16 or x.dtype != torch.float32:
                 raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 1 x 1 convolution with C_in a multiple of 16 -- not built")
             if id(m) not in gemm_img:
-                gemm_img[id(m)] = R.gemm_x3_pack(m.weight.reshape(m.out_channels, m.in_channels), "bf16x3")
+                gemm_img[id(m)] = R.gemm_x3_pack(m.weight.reshape(m.out_channels, m.in_channels), self.gemm)
             rows = x.contiguous(memory_format=CL).permute(0, 2, 3, 1)   # [B, h, w, C] contiguous
-            y = R.linear_x3(rows, gemm_img[id(m)], m.out_channels, None).permute(0, 3, 1, 2)
-            self.conv_routes[names[id(m)]] = ("bf16x3", "self-contained: vd3d_gemm_x3 over the pixel rows")
+            y = R.linear_x3(rows, gemm_img[id(m)], m.out_channels, None, mode=self.gemm).permute(0, 3, 1, 2)
+            self.conv_routes[names[id(m)]] = (self.gemm, "self-contained: vd3d_gemm_x3 over the pixel rows")
             if self._flop_count is not None:   # flops_per_frame: what conv_nb adds for the same module
                 self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * m.in_channels
             return y
@@ -585,24 +610,25 @@ class DepthPipe:
         hook, the tokens minus CLS are the rows of the 1 x 1 projection (linear_x3 with its bias; [B, T-1, C_i] is NHWC storage); ConvTranspose2d (kernel == stride,
         no padding) is a linear_x3 on conv_transpose_gemm_weight + vd3d_depth_to_space_bias_nhwc_f32; Identity stays; the 3 x 3 / stride 2 / padding 1 convolution
         runs on vd3d_conv3x3_s2_x3 with its bias through bias_act.  Any other resize module is refused by name, here, at construction."""
-        R, CL = self.renderer, torch.channels_last
+        R, CL, gm = self.renderer, torch.channels_last, self.gemm
+        s2_fn = "conv3x3_s2_x2" if gm == "fp16x2" else "conv3x3_s2_x3"   # the Renderer method of the mode
         stage = self.model.neck.reassemble_stage
         hooks = []
         for lay in stage.layers:
             pm, rz = lay.projection, lay.resize
             if pm.kernel_size != (1, 1) or pm.stride != (1, 1) or pm.padding != (0, 0) or pm.groups != 1 or pm.in_channels % 16:
                 raise NotImplementedError(f"self_contained=True: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
-            hk = dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), "bf16x3"), kind="identity", img=None)
+            hk = dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm), kind="identity", img=None)
             if isinstance(rz, torch.nn.ConvTranspose2d):
                 if not (rz.kernel_size == rz.stride and rz.kernel_size[0] == rz.kernel_size[1] and rz.padding == (0, 0) and rz.output_padding == (0, 0)
                         and rz.dilation == (1, 1) and rz.groups == 1 and rz.in_channels % 16 == 0 and rz.out_channels % 4 == 0):
                     raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a ConvTranspose2d with kernel {rz.kernel_size} / stride {rz.stride} / padding "
                                               f"{rz.padding}, {rz.in_channels} -> {rz.out_channels} channels (built: square kernel == stride, no padding, C_in % 16) -- not built")
-                hk["kind"], hk["img"] = "ct", R.gemm_x3_pack(conv_transpose_gemm_weight(rz.weight), "bf16x3")
+                hk["kind"], hk["img"] = "ct", R.gemm_x3_pack(conv_transpose_gemm_weight(rz.weight), gm)
             elif isinstance(rz, torch.nn.Conv2d):
                 img = None
                 if rz.kernel_size == (3, 3) and rz.stride == (2, 2) and rz.padding == (1, 1) and rz.dilation == (1, 1) and rz.groups == 1:
-                    img = R.conv3x3_s2_x3_pack(rz.weight)
+                    img = getattr(R, s2_fn + "_pack")(rz.weight)
                 if img is None:
                     raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a Conv2d with kernel {rz.kernel_size} / stride {rz.stride} / padding {rz.padding}, "
                                               f"{rz.in_channels} -> {rz.out_channels} channels (built: 3 x 3 / stride 2 / padding 1, C_in % 16, C_out % 128 up to 1024) -- not built")
@@ -626,21 +652,21 @@ class DepthPipe:
                     raise ValueError(f"{T - 1} patch tokens do not form a {gh} x {gw} grid")
                 pm, rz = hk["pm"], hk["rz"]
                 n = pm.out_channels
-                x = R.linear_x3(hs[:, 1:].contiguous(), hk["proj"], n, pm.bias)                  # [B, T-1, C_i]: NHWC storage
-                self.conv_routes[names[id(pm)]] = ("bf16x3", "self-contained: vd3d_gemm_x3 over the token rows")
+                x = R.linear_x3(hs[:, 1:].contiguous(), hk["proj"], n, pm.bias, mode=gm)         # [B, T-1, C_i]: NHWC storage
+                self.conv_routes[names[id(pm)]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
                 x = x.view(B, gh, gw, n).permute(0, 3, 1, 2)
                 count(pm, x)
                 if hk["kind"] == "ct":
                     s = rz.kernel_size[0]
-                    y = R.linear_x3(x.permute(0, 2, 3, 1), hk["img"], s * s * rz.out_channels, None)
+                    y = R.linear_x3(x.permute(0, 2, 3, 1), hk["img"], s * s * rz.out_channels, None, mode=gm)
                     x = R.depth_to_space_bias(y.view(B * gh * gw, s * s * rz.out_channels), B, gh, gw, s, rz.bias)
-                    self.conv_routes[names[id(rz)]] = ("bf16x3", "self-contained: vd3d_gemm_x3 + vd3d_depth_to_space_bias_nhwc_f32")
+                    self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_gemm_x3 + vd3d_depth_to_space_bias_nhwc_f32")
                     count(rz, x)
                 elif hk["kind"] == "s2":
-                    x = R.conv3x3_s2_x3(x, hk["img"], rz.out_channels)
+                    x = getattr(R, s2_fn)(x, hk["img"], rz.out_channels)
                     if rz.bias is not None:
                         x = R.bias_act(x, rz.bias)
-                    self.conv_routes[names[id(rz)]] = ("bf16x3", "self-contained: vd3d_conv3x3_s2_x3")
+                    self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_" + s2_fn)
                     count(rz, x)
                 out.append(x)
             return out
@@ -658,16 +684,16 @@ class DepthPipe:
         if not (isinstance(m, torch.nn.Conv2d) and m.kernel_size == (p, p) and m.stride == (p, p) and m.padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1
                 and m.in_channels == 3 and p <= 64):
             raise NotImplementedError(f"self_contained=True: {name}: a patch embedding other than Conv2d(3, C, kernel_size=p, stride=p), p <= 64 -- not built")
-        img = R.gemm_x3_pack(patch_embedding_gemm_weight(m.weight), "bf16x3")
+        img = R.gemm_x3_pack(patch_embedding_gemm_weight(m.weight), self.gemm)
 
         def patch_fwd(pixel_values):
             if pixel_values.dtype != torch.float32 or pixel_values.shape[1] != 3:
                 raise NotImplementedError("self_contained=True: the patch embedding takes a float32 [B, 3, th, tw] image")
             rows = R.patchify(pixel_values.contiguous(memory_format=torch.channels_last), p)   # what depth_preprocess hands over is taken as it is
-            self.conv_routes[name] = ("bf16x3", "self-contained: vd3d_patchify_f32 + vd3d_gemm_x3")
+            self.conv_routes[name] = (self.gemm, "self-contained: vd3d_patchify_f32 + vd3d_gemm_x3")
             if self._flop_count is not None:   # flops_per_frame: the counting hook's formula for the bypassed Conv2d
                 self._flop_count[0] += 2.0 * rows.shape[1] * m.out_channels * 3 * p * p
-            return R.linear_x3(rows, img, m.out_channels, m.bias)
+            return R.linear_x3(rows, img, m.out_channels, m.bias, mode=self.gemm)
         pe.forward = patch_fwd
 
     def _patch_dpt_vit_reassemble_head(self, conv_nb, f32):

@@ -954,6 +954,48 @@ class Renderer:
         _lib.check(self._L.vd3d_conv3x3_s2_x3(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
         return out
 
+    def _conv3x3_x2t_pack(self, st: str, weight: torch.Tensor):
+        w = weight.detach().to(self.device, torch.float32).contiguous()
+        Cout, Cin, kh, kw = w.shape
+        nb = int(getattr(self._L, f"vd3d_conv3x3_{st}_x2_weight_bytes")(Cin, Cout)) if (kh, kw) == (3, 3) else -1
+        if nb < 0:
+            return None
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(getattr(self._L, f"vd3d_conv3x3_{st}_x2_pack_weights")(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
+        return img
+
+    def _conv3x3_x2t(self, st: str, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
+        B, Cin, H, W = x.shape
+        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
+            raise AssertionError(f"conv3x3_{st}_x2: float32 channels_last input")
+        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if st == "s2" else (H, W)
+        out = torch.empty((B, int(Cout), Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        self._enter(x, w_image, out)
+        _lib.check(getattr(self._L, f"vd3d_conv3x3_{st}_x2")(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
+        return out
+
+    def conv3x3_s1_x2_pack(self, weight: torch.Tensor):
+        """Scale, split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_s1_x2``; ``None`` when the shape is not built (Cin % 16, Cout in
+        {32, 64, 128, 256})."""
+        return self._conv3x3_x2t_pack("s1", weight)
+
+    def conv3x3_s1_x2(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
+        """F.conv2d(x, W, None, stride 1, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_s1_x2_pack(W)``: fp16x2 MFMA arithmetic
+        (two fp16 terms per operand, three products per MAC, |x| < 65 504), float32 accumulation, on the 8 x 32 tile kernel that takes every map size
+        (include/vd3d.h vd3d_conv3x3_s1_x2); returns a channels_last [B, Cout, H, W] tensor."""
+        return self._conv3x3_x2t("s1", x, w_image, Cout)
+
+    def conv3x3_s2_x2_pack(self, weight: torch.Tensor):
+        """Scale, split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_s2_x2``; ``None`` when the shape is not built (Cin % 16, Cout a
+        multiple of 128 up to 1024)."""
+        return self._conv3x3_x2t_pack("s2", weight)
+
+    def conv3x3_s2_x2(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
+        """F.conv2d(x, W, None, stride 2, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_s2_x2_pack(W)``: fp16x2 MFMA
+        arithmetic, float32 accumulation (include/vd3d.h vd3d_conv3x3_s2_x2); returns a channels_last [B, Cout, (H+1)//2, (W+1)//2] tensor."""
+        return self._conv3x3_x2t("s2", x, w_image, Cout)
+
     def conv_ifn_pack(self, kind: int, weight: torch.Tensor):
         """Split + pack a float32 weight for ``conv_ifn``: ``[Cout, Cin, 3, 3]`` for ``_abi.IFN_K3S1`` / ``IFN_K3S2``, ``[Cin, Cout, 4, 4]`` (ConvTranspose2d's layout) for
         ``IFN_T4S2``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 96})."""
