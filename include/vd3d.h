@@ -37,7 +37,8 @@ extern "C" {
  * Additions since 6 that leave the version as it is (no struct or existing signature changed): vd3d_depth_to_space_bias_nhwc_f32, vd3d_attention_f32, vd3d_attention_f32_form,
  *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs, vd3d_conv3x3_s2_x3_weight_bytes,
  *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)), vd3d_depth_handoff_form, vd3d_depth_preprocess_form,
- *    vd3d_conv3x3_s1_x2_* and vd3d_conv3x3_s2_x2_* (weight_bytes, pack_weights and the convolution each: DepthPipe(conv="fp16x2")). */
+ *    vd3d_conv3x3_s1_x2_* and vd3d_conv3x3_s2_x2_* (weight_bytes, pack_weights and the convolution each: DepthPipe(conv="fp16x2")),
+ *    vd3d_resize_pil_bicubic_u8, vd3d_depth_preprocess_pil (DepthPipe(front_end="pil")). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -492,6 +493,23 @@ int vd3d_depth_preprocess(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H
  * VD3D_E_UNSUPPORTED elsewhere.  The forms give the same bits; a scale past the tap budget is VD3D_E_UNSUPPORTED whatever the form. */
 int vd3d_depth_preprocess_form(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
                                const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc, int form);
+
+/* ---- the reference's own 8-bit input path, exact (DepthPipe(front_end="pil")).  The reference hands its depth pipeline PIL images: an optional
+ * img.resize(inference_size, Image.BICUBIC) (core/render_depth.py:1113-1116) and the image processor's resize are both Pillow's ImagingResample on 8-bit
+ * pixels, which rounds to uint8 after the horizontal and again after the vertical pass.  vd3d_resize_pil_bicubic_u8: B uint8 frames [B][H][W][3] ->
+ * [B][h][w][3], channel order kept, the bytes Image.resize((w, h), Image.BICUBIC) gives (coefficients in double on the host, 22-bit fixed point, int32
+ * sums; the horizontal pass only if the width changes, then the vertical pass only if the height changes; equal sizes copy).  Coefficient tables are
+ * built at a geometry's first use (one blocking upload) and belong to the context.  VD3D_E_UNSUPPORTED, nothing launched, where an output index has
+ * more than 24 taps (down-scales past ~5.5) or 32 output columns span more than 213 input pixels: visiondepth3d_amd/pil_resample.py states the same
+ * operator for those. */
+int vd3d_resize_pil_bicubic_u8(vd3d_ctx* ctx, const uint8_t* src, int B, int H, int W, uint8_t* dst, int h, int w);
+/* The depth network's input from B uint8 BGR frames: that resize to (th, tw), BGR -> RGB, and the image processor's rescale and normalise as a table
+ * of the byte, float32(float64(v) * (1 / 255)) then (x - mean) / std in float32 (rounded to bf16, nearest even, for VD3D_DT_BF16) -- NHWC
+ * [B][th][tw][3] as vd3d_depth_preprocess writes it, equal to DPTImageProcessor's pixel_values bit for bit.  mid_h, mid_w > 0: the frames are first
+ * resized to (mid_h, mid_w) by the uint8 form (the depth tab's inference size), a second launch; 0, 0: one launch.  VD3D_E_UNSUPPORTED as above if
+ * either step is outside the plan. */
+int vd3d_depth_preprocess_pil(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, int mid_h, int mid_w, int th, int tw,
+                              const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc);
 
 /* Transformer-block glue of the depth network (a25): s = x + y, n = LayerNorm(s)*gamma + beta on [rows][cols] device arrays
  * of `dtype` in one pass (y == NULL: LayerNorm only, out_sum unused).  cols in {384, 768, 1024} (DA-V2 S/B/L), else

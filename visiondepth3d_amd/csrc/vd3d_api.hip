@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <list>
 #include <map>
 #include <string>
 #include <vector>
@@ -106,6 +107,13 @@ struct vd3d_ctx {
   // ... and the general table of the unfused dense kernel (k_dof_grade4: any odd tap count up to 31), same never-overwrite rule
   struct wk_tab { int ksz[4]; float kern[4][32]; float* dev; };
   std::vector<wk_tab> wk_tabs; int wk_cur = -1;
+  // Pillow-exact front end (vd3d_pilresample.hip): the per-axis coefficient tables of every (input size, output size) this context has met, the
+  // normalisation tables of every (mean, std), and the pre-resized frames of vd3d_depth_preprocess_pil.  A table is built once, never overwritten
+  // (a queued kernel may read it) and freed with the context; an axis outside the tap budget is remembered with dev == NULL.
+  std::list<vd_pil_axis> pil_axes;
+  struct pil_lut { float mean[3], stdv[3]; float* dev; };
+  std::vector<pil_lut> pil_luts;
+  uint8_t* pil_mid = nullptr; size_t pil_mid_cap = 0;
   // profiling
   bool profiling = false;
   std::vector<vd_prof_rec> recs;
@@ -261,6 +269,9 @@ VD3D_EXPORT int vd3d_ctx_destroy(vd3d_ctx* c) {
   for (const auto& e : c->aten_cache) { (void)hipFree(e.plan); (void)hipFree(e.scratch); }
   for (auto& t : c->w2_tabs) (void)hipFree(t.dev);
   for (auto& t : c->wk_tabs) (void)hipFree(t.dev);
+  for (auto& a : c->pil_axes) if (a.dev) (void)hipFree(a.dev);
+  for (auto& t : c->pil_luts) (void)hipFree(t.dev);
+  if (c->pil_mid) (void)hipFree(c->pil_mid);
   for (void* p : ptrs) if (p) (void)hipFree(p);
   vd_lb_free(c->lb);
   for (auto* v : {&c->slot_rgb, &c->slot_dn, &c->slot_D, &c->slot_tdf, &c->slot_tdfp})
@@ -1601,6 +1612,92 @@ VD3D_EXPORT int vd3d_depth_preprocess_form(vd3d_ctx* c, const uint8_t* frames_bg
 VD3D_EXPORT int vd3d_depth_preprocess(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int th, int tw,
                                       const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc) {
   return vd3d_depth_preprocess_form(c, frames_bgr, B, H, W, th, tw, mean3_host, std3_host, dtype, out_nhwc, 0);
+}
+
+// ---- the Pillow-exact front end (vd3d_pilresample.hip) ------------------------------------------------------------------------------------------
+// The context's table of one axis, built at its first use (std::list: an entry keeps its address).
+static int pil_axis(vd3d_ctx* c, int n_in, int n_out, const vd_pil_axis** out) {
+  for (const auto& a : c->pil_axes)
+    if (a.n_in == n_in && a.n_out == n_out) { *out = &a; return 0; }
+  vd_pil_axis a;
+  hipError_t e = hipSuccess;
+  if (vd_pil_axis_build(&a, n_in, n_out, &e) < 0) return set_err(VD3D_E_HIP, "pil tables %d -> %d: %s", n_in, n_out, hipGetErrorString(e));
+  c->pil_axes.push_back(a);
+  *out = &c->pil_axes.back();
+  return 0;
+}
+// A context that has met more than 256 axes starts its list over, once nothing queued can read a table (tiled depth meets a handful per clip).
+static int pil_axes_bound(vd3d_ctx* c) {
+  if (c->pil_axes.size() <= 256) return 0;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (auto& a : c->pil_axes) if (a.dev) (void)hipFree(a.dev);
+  c->pil_axes.clear();
+  return 0;
+}
+#define PIL_BUDGET_TEXT "exceeds the kernel's plan (24 taps per axis, 213 input pixels under 32 output columns, 65535 frames)"
+
+VD3D_EXPORT int vd3d_resize_pil_bicubic_u8(vd3d_ctx* c, const uint8_t* src, int B, int H, int W, uint8_t* dst, int h, int w) {
+  if (!c || !src || !dst) return set_err(VD3D_E_INVALID, "resize_pil_bicubic_u8: NULL argument");
+  if (B < 1 || H < 1 || W < 1 || h < 1 || w < 1) return set_err(VD3D_E_INVALID, "resize_pil_bicubic_u8: %d frames of %dx%d -> %dx%d", B, W, H, w, h);
+  HIPCHK(hipSetDevice(c->device));
+  int rc = pil_axes_bound(c);
+  if (rc) return rc;
+  const vd_pil_axis *aw = nullptr, *ah = nullptr;
+  if ((rc = pil_axis(c, W, w, &aw)) || (rc = pil_axis(c, H, h, &ah))) return rc;
+  int by = 0;
+  if (!vd_pil_plan(aw, ah, B, &by)) return set_err(VD3D_E_UNSUPPORTED, "resize_pil_bicubic_u8: %d x %dx%d -> %dx%d " PIL_BUDGET_TEXT, B, W, H, w, h);
+  StageTimer t(c, "resize_pil");
+  vd_launch_pil_resample(c->stream, src, B, H, W, aw, ah, 0, nullptr, dst);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+VD3D_EXPORT int vd3d_depth_preprocess_pil(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int mid_h, int mid_w, int th, int tw,
+                                          const float* mean3_host, const float* std3_host, int dtype, void* out_nhwc) {
+  if (!c || !frames_bgr || !out_nhwc || !mean3_host || !std3_host) return set_err(VD3D_E_INVALID, "depth_preprocess_pil: NULL argument");
+  if (B < 1 || H < 1 || W < 1 || th < 1 || tw < 1 || mid_h < 0 || mid_w < 0 || (mid_h > 0) != (mid_w > 0))
+    return set_err(VD3D_E_INVALID, "depth_preprocess_pil: %d frames of %dx%d -> %dx%d -> %dx%d", B, W, H, mid_w, mid_h, tw, th);
+  if (dtype != VD3D_DT_BF16 && dtype != VD3D_DT_F32) return set_err(VD3D_E_INVALID, "depth_preprocess_pil: dtype %d (float32 or bf16)", dtype);
+  HIPCHK(hipSetDevice(c->device));
+  int rc = pil_axes_bound(c);
+  if (rc) return rc;
+  const bool two = mid_h > 0;
+  const int sh = two ? mid_h : H, sw = two ? mid_w : W;
+  const vd_pil_axis *aw0 = nullptr, *ah0 = nullptr, *aw1 = nullptr, *ah1 = nullptr;
+  if (two && ((rc = pil_axis(c, W, sw, &aw0)) || (rc = pil_axis(c, H, sh, &ah0)))) return rc;
+  if ((rc = pil_axis(c, sw, tw, &aw1)) || (rc = pil_axis(c, sh, th, &ah1))) return rc;
+  int by = 0;
+  if ((two && !vd_pil_plan(aw0, ah0, B, &by)) || !vd_pil_plan(aw1, ah1, B, &by))
+    return set_err(VD3D_E_UNSUPPORTED, "depth_preprocess_pil: %d x %dx%d -> %dx%d -> %dx%d " PIL_BUDGET_TEXT, B, W, H, sw, sh, tw, th);
+  const float* lut = nullptr;
+  for (const auto& t : c->pil_luts)
+    if (!memcmp(t.mean, mean3_host, sizeof t.mean) && !memcmp(t.stdv, std3_host, sizeof t.stdv)) { lut = t.dev; break; }
+  if (!lut) {
+    if (c->pil_luts.size() >= 64) return set_err(VD3D_E_UNSUPPORTED, "depth_preprocess_pil: more than 64 (mean, std) pairs in one context");
+    vd3d_ctx::pil_lut t;
+    memcpy(t.mean, mean3_host, sizeof t.mean); memcpy(t.stdv, std3_host, sizeof t.stdv);
+    float host[768];
+    vd_pil_lut_fill(t.mean, t.stdv, host);
+    HIPCHK(hipMalloc((void**)&t.dev, sizeof host));
+    const hipError_t e = hipMemcpy(t.dev, host, sizeof host, hipMemcpyHostToDevice);   // blocking: there before any launch
+    if (e != hipSuccess) { (void)hipFree(t.dev); return set_err(VD3D_E_HIP, "depth_preprocess_pil: table upload: %s", hipGetErrorString(e)); }
+    c->pil_luts.push_back(t);
+    lut = t.dev;
+  }
+  const uint8_t* src = frames_bgr;
+  if (two) {
+    const size_t need = (size_t)B * sh * sw * 3 + 4;   // and the dword the last row's last bytes are fetched in
+    if (need > c->pil_mid_cap) { c->pil_mid_cap = 0; HIPCHK(re_alloc(&c->pil_mid, need)); c->pil_mid_cap = need; }   // hipFree waits for whatever still reads the old buffer
+    StageTimer t(c, "depth_prep_pil");
+    vd_launch_pil_resample(c->stream, frames_bgr, B, H, W, aw0, ah0, 0, nullptr, c->pil_mid);
+    src = c->pil_mid;
+  }
+  {
+    StageTimer t(c, "depth_prep_pil");
+    vd_launch_pil_resample(c->stream, src, B, sh, sw, aw1, ah1, dtype == VD3D_DT_F32 ? 1 : 2, lut, out_nhwc);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 VD3D_EXPORT int vd3d_add_layernorm(vd3d_ctx* c, int dtype, const void* x, const void* y_or_null, const void* gamma, const void* beta,

@@ -227,6 +227,22 @@ bool vd_launch_preview(hipStream_t s, int type, const uint8_t* L, const uint8_t*
 // returns 0 = launched, 1 = outside the tap budget (every form), 2 = form 2 asked for where the strip kernel does not apply
 int vd_launch_depth_prep(hipStream_t s, const uint8_t* frames, int B, int H, int W, int th, int tw, const float mean[3],
                          const float stdv[3], int dtype, void* out_nhwc, int form);
+// ---- vd3d_pilresample.hip: Pillow's 8-bit bicubic resampler and the depth front end on it (DepthPipe(front_end="pil"))
+#define VD_PIL_KMAX 24   // taps per output index: 3840 -> 924 needs 19; the budget ends near a 5.5-fold down-scale
+struct vd_pil_axis {     // one axis of one geometry: what the host knows of it and its device table (owned by the context that built it)
+  int n_in = 0, n_out = 0;
+  int taps = 0;          // the largest tap count of an output index
+  int span[6] = {0, 0, 0, 0, 0, 0};   // input samples an aligned run of 32, 16, 8, 4, 2, 1 outputs covers at most
+  int* dev = nullptr;    // [n_out] first tap, [n_out] tap count, [n_out][VD_PIL_KMAX] coefficients; NULL: outside the tap budget
+};
+// 0 = built, 1 = outside the tap budget (dev stays NULL), -1 = a HIP call failed (*herr)
+int vd_pil_axis_build(vd_pil_axis* a, int n_in, int n_out, hipError_t* herr);
+void vd_pil_lut_fill(const float mean[3], const float stdv[3], float* lut768);
+// whether the kernel's LDS plan holds B frames of this geometry (by_out: output rows of a band)
+bool vd_pil_plan(const vd_pil_axis* aw, const vd_pil_axis* ah, int B, int* by_out);
+// epi 0: uint8 [B][h][w][3], the input's channel order; 1 / 2: float32 / bf16 NHWC, BGR -> RGB through lut_dev [3][256].  false: vd_pil_plan refuses, nothing launched
+bool vd_launch_pil_resample(hipStream_t s, const uint8_t* frames, int B, int H, int W, const vd_pil_axis* aw, const vd_pil_axis* ah, int epi,
+                            const float* lut_dev, void* out);
 // ---- vd3d_netops.hip
 // vd3d_gemm.hip: the transformer linears as a split-bf16 (bf16x3, six products) GEMM with float32 accumulation
 long long vd_gemm_x3_weight_bytes(int N, int K, int mode);

@@ -199,8 +199,16 @@ class DepthPipe:
 
     def __init__(self, name: str = "depth-anything-v2-small", device="cuda", dtype=torch.float32, seed: int = 0,
                  channels_last: bool = True, renderer=None, fuse_backbone: bool = True, model=None, processor: dict | None = None,
-                 tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None, self_contained: bool = False):
+                 tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None, self_contained: bool = False,
+                 front_end: str = "float"):
         """``dtype``: float32 (the reference's precision, default) or bfloat16.
+        ``front_end``: ``"float"`` (default) -- the network input is the float32 statement of the image processor's antialiased bicubic resize, never
+        rounded (``vd3d_depth_preprocess`` with a renderer, ATen otherwise).  ``"pil"`` -- OPT-IN: the input the reference process builds, bit for bit.
+        The reference hands its pipeline PIL images, so the optional ``img.resize(inference_size, Image.BICUBIC)`` and the image processor's resize are
+        Pillow's 8-bit resampler, which rounds to uint8 after each pass; rescale and normalise are then a table of the byte.  With a renderer this is
+        one launch of ``vd3d_depth_preprocess_pil`` (two with an inference size); on the CPU, and for a geometry past the kernel's tap budget, the
+        integer statement ``pil_resample.pixel_values`` gives the same values.  ``front_end_route`` ("kernel" | "statement") says which ran last.
+        The mode takes uint8 frames only (TypeError otherwise).  Any other value of the keyword raises ValueError.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
         GEMMs and the attention (64-wide heads) is the library's exact-float32 kernel (``vd3d_attention_f32``: both products on the float32-input
         matrix cores, float32 online softmax); ``"bf16x3"`` -- OPT-IN: the library's own split-bf16 GEMM (``vd3d_gemm_x3``: every float32 operand exactly split into three bf16
@@ -268,6 +276,9 @@ class DepthPipe:
             raise ValueError(f"conv={conv!r} is the convolution half of gemm={conv!r} and needs that mode")
         if gemm != "f32" and (dtype != torch.float32 or renderer is None or torch.device(device).type != "cuda"):
             raise ValueError("gemm='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
+        if front_end not in ("float", "pil"):
+            raise ValueError("front_end must be 'float' or 'pil'")
+        self.front_end, self.front_end_route = front_end, None
         self.gemm, self.conv, self.self_contained = gemm, conv, bool(self_contained)
         self.conv_routes = {}
         self.tuned_gemm = self.miopen_find = False
@@ -965,6 +976,23 @@ class DepthPipe:
                                               att.num_attention_heads, att.attention_head_size, att.scaling, layer.layernorm_before, layer.layernorm_after,
                                               ffn.intermediate_act_fn, nxt)
 
+    def _pil_pixel_values(self, frames_bgr: torch.Tensor, inference_size=None) -> torch.Tensor:
+        """``front_end="pil"``: the pixel_values the reference's image processor makes of these frames as PIL images (pre-resized to
+        ``inference_size`` = (W', H') when given), [B,3,th,tw] of ``self.dtype``, channels_last on the GPU."""
+        if frames_bgr.dtype != torch.uint8 or frames_bgr.dim() != 4 or frames_bgr.shape[-1] != 3:
+            raise TypeError("front_end='pil' takes uint8 [B,H,W,3] BGR frames (the reference's 8-bit images)")
+        H, W = frames_bgr.shape[1:3]
+        sh, sw = (H, W) if inference_size is None else (int(inference_size[1]), int(inference_size[0]))
+        th, tw = self.resize_target(sh, sw)
+        if self.renderer is not None:
+            x = self.renderer.depth_preprocess_pil(frames_bgr, th, tw, self.proc["mean"], self.proc["std"], dtype=self.dtype, inference_size=inference_size)
+            self.front_end_route = self.renderer.pil_route
+            return x
+        from . import pil_resample
+        x = pil_resample.pixel_values(frames_bgr.to(self.device), th, tw, self.proc["mean"], self.proc["std"], self.dtype, inference_size).permute(0, 3, 1, 2)
+        self.front_end_route = "statement"
+        return x if self.device.type == "cuda" else x.contiguous()
+
     @torch.no_grad()
     def infer_bgr_u8(self, frames_bgr: torch.Tensor, inference_size=None, raw: bool = False, at_inference_size: bool = False) -> torch.Tensor:
         """uint8 [B,H,W,3] BGR frames in HBM -> float32 [B,H,W] predicted depth at the frame size (the
@@ -977,6 +1005,11 @@ class DepthPipe:
             oH, oW = int(inference_size[1]), int(inference_size[0])
         else:
             oH, oW = H, W
+        if self.front_end == "pil":
+            pred = self.model(pixel_values=self._pil_pixel_values(frames_bgr, inference_size)).predicted_depth
+            if raw:
+                return pred.float()
+            return F.interpolate(pred.float().unsqueeze(1), size=(oH, oW), mode="bicubic", align_corners=False).squeeze(1)
         if self.renderer is not None and inference_size is None and frames_bgr.dtype == torch.uint8:
             th, tw = self.resize_target(H, W)
             x = None

@@ -814,6 +814,56 @@ class Renderer:
         _lib.check(self._L.vd3d_depth_preprocess_form(self._ctx, _ptr(f), B, H, W, int(th), int(tw), m, s, self._dt(dtype), _ptr(out), int(form)))
         return out.permute(0, 3, 1, 2)   # NCHW view of NHWC storage == torch.channels_last
 
+    pil_route = None   # where the last resize_pil_bicubic_u8 / depth_preprocess_pil ran: "kernel" | "statement"
+
+    def resize_pil_bicubic_u8(self, frames: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """``Image.fromarray(f).resize((w, h), Image.BICUBIC)`` of every uint8 [B,H,W,3] frame (a single [H,W,3] frame comes back as one), on the
+        device, the same bytes (vd3d_resize_pil_bicubic_u8).  A geometry past the kernel's tap budget runs the integer statement of the same operator
+        (``pil_resample.resize``) on the device instead: the same values.  ``pil_route`` says which of the two ran."""
+        f = frames.to(self.device)
+        if f.dtype != torch.uint8 or f.dim() not in (3, 4) or f.shape[-1] != 3:
+            raise TypeError("resize_pil_bicubic_u8 takes uint8 [B,H,W,3] frames")
+        single = f.dim() == 3
+        f = (f[None] if single else f).contiguous()
+        B, H, W, _ = f.shape
+        out = torch.empty((B, int(h), int(w), 3), dtype=torch.uint8, device=self.device)
+        self._enter(f, out)
+        rc = self._L.vd3d_resize_pil_bicubic_u8(self._ctx, _ptr(f), B, H, W, _ptr(out), int(h), int(w))
+        if rc == -4:   # VD3D_E_UNSUPPORTED
+            from . import pil_resample
+            out = pil_resample.resize(f, int(w), int(h))
+            self.pil_route = "statement"
+        else:
+            _lib.check(rc)
+            self.pil_route = "kernel"
+        return out[0] if single else out
+
+    def depth_preprocess_pil(self, frames_bgr: torch.Tensor, th: int, tw: int, mean, std, dtype=torch.float32, inference_size=None) -> torch.Tensor:
+        """The reference's own input path, exact: uint8 BGR [B,H,W,3] -> what ``DPTImageProcessor`` makes of the PIL image (Pillow's 8-bit bicubic
+        resize to (th, tw), 1/255, normalise), ``dtype`` tensor of logical shape [B,3,th,tw] in channels_last memory, in one launch
+        (vd3d_depth_preprocess_pil; stage ``depth_prep_pil``).  ``inference_size`` = (W', H'): ``img.resize(inference_size, Image.BICUBIC)`` first, a
+        second launch.  Past the tap budget the integer statement (``pil_resample.pixel_values``) runs on the device; ``pil_route`` says which ran."""
+        f = frames_bgr.to(self.device)
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3:
+            raise TypeError("depth_preprocess_pil takes uint8 [B,H,W,3] BGR frames")
+        f = f.contiguous()
+        B, H, W, _ = f.shape
+        mw, mh = (0, 0) if inference_size is None else (int(inference_size[0]), int(inference_size[1]))
+        if inference_size is not None and (mw < 1 or mh < 1):
+            raise ValueError("inference_size is (W', H') with positive sides")
+        out = torch.empty((B, int(th), int(tw), 3), dtype=dtype, device=self.device)
+        m = (C.c_float * 3)(*[float(v) for v in mean]); s = (C.c_float * 3)(*[float(v) for v in std])
+        self._enter(f, out)
+        rc = self._L.vd3d_depth_preprocess_pil(self._ctx, _ptr(f), B, H, W, mh, mw, int(th), int(tw), m, s, self._dt(dtype), _ptr(out))
+        if rc == -4:   # VD3D_E_UNSUPPORTED
+            from . import pil_resample
+            out = pil_resample.pixel_values(f, int(th), int(tw), mean, std, dtype, inference_size)
+            self.pil_route = "statement"
+        else:
+            _lib.check(rc)
+            self.pil_route = "kernel"
+        return out.permute(0, 3, 1, 2)   # NCHW view of NHWC storage == torch.channels_last
+
     def add_layernorm(self, x: torch.Tensor, y, norm: torch.nn.LayerNorm):
         """(x + y, LayerNorm(x + y)) for contiguous float32 / bf16 [..., cols] tensors in one launch; y=None -> (x, LayerNorm(x))."""
         cols = x.shape[-1]
