@@ -1,7 +1,9 @@
-"""GPU test (-m gpu): vd3d_conv3x3_x3 and vd3d_conv_ifn (csrc/vd3d_conv_x3.hip) reproduce, bit for bit, the outputs recorded in tests/golden/x3_bits.json with a
-library built from the commit before the two kernels were merged into one (tools/record_x3_bits.py: the cases, the hashed inputs and the recorder).  One SHA-256
-of the raw output bytes per case: ragged and single-pixel tiles, wrapping chunk buffers, every geometry at every C_out, plain and with slope, residual, padded
-pitches and an output slice (whose surroundings are hashed too)."""
+"""GPU test (-m gpu): the tile convolutions reproduce, bit for bit, the outputs recorded in tests/golden/x3_bits.json (tools/record_x3_bits.py: the cases, the
+hashed inputs and the recorder).  vd3d_conv3x3_x3 and vd3d_conv_ifn (csrc/vd3d_conv_x3.hip) were recorded with a library built from the commit before the two
+kernels were merged into one; vd3d_conv3x3_s2_x3 (vd3d_conv_s2.hip), vd3d_conv3x3_s1_x2 and vd3d_conv3x3_s2_x2 (vd3d_conv_x2t.hip) with one built from the commit
+before their launch side was folded into one statement per layer.  One SHA-256 of the raw output bytes per case: ragged and single-pixel tiles, wrapping chunk
+buffers, every geometry at every C_out, one and two channel slices, odd and even stride-2 sizes, plain and with slope, residual, padded pitches and an output
+slice (whose surroundings are hashed too)."""
 import importlib.util
 import json
 import os

@@ -1,5 +1,6 @@
-"""The cases of tests/test_hip_x3_bits.py and the recorder of tests/golden/x3_bits.json: one SHA-256 of the raw output bytes per case of vd3d_conv3x3_x3 and
-vd3d_conv_ifn.  The hashes pin the BITS of the two bf16x3 tile convolutions across refactors of their kernel: record them with a library built from the commit
+"""The cases of tests/test_hip_x3_bits.py and the recorder of tests/golden/x3_bits.json: one SHA-256 of the raw output bytes per case of vd3d_conv3x3_x3,
+vd3d_conv_ifn, vd3d_conv3x3_s2_x3, vd3d_conv3x3_s1_x2 and vd3d_conv3x3_s2_x2.  The hashes pin the BITS of the tile convolutions (every entry point on the kernel
+body of csrc/vd3d_conv_x3.h) across refactors of their kernel and of their launch side: record them with a library built from the commit
 whose results are to be kept (a worktree build loaded through VD3D_LIB_PATH, as tools/build_ab.sh makes one), never with the library under test.
 
 Inputs: a closed-form integer hash of the element index (no library random generator), turned into float32 words with a random sign, all 23 stored mantissa bits
@@ -37,7 +38,8 @@ def hashed_f32(shape, channel_axis, seed):
 def cases():
     """(name, spec) in a fixed order.  conv3x3_x3: ragged tiles both ways, 2 x 2 tiles, three chunks (the A double buffer wraps), two frames; then one pixel, one
     chunk.  conv_ifn: every kind at every C_out, plain and with slope + residual + padded pitches + an output slice; stride 2 on an odd and an even size and at
-    C_in 16 (the one- and two-step chunks)."""
+    C_in 16 (the one- and two-step chunks).  conv3x3_s1_x2: conv3x3_x3's shapes.  conv3x3_s2_x3 / conv3x3_s2_x2: one and two 128-channel slices on an odd size
+    (output 13 x 47: ragged tiles both ways, 2 x 2 tiles, three chunks, two frames) and on 2 x 2 (even, one output pixel, one chunk).  New cases go at the end."""
     out = []
     for co in (32, 64, 128, 256):
         out.append((f"conv3x3_x3-2x13x47x48-{co}", dict(fn="c3", B=2, H=13, W=47, Cin=48, Cout=co)))
@@ -49,6 +51,13 @@ def cases():
             for full in (0, 1):
                 out.append((f"conv_ifn-{KNAME[kind]}-{B}x{H}x{W}x{ci}-{co}-{'full' if full else 'plain'}",
                             dict(fn="ifn", kind=kind, B=B, H=H, W=W, Cin=ci, Cout=co, full=full)))
+    for co in (32, 64, 128, 256):
+        out.append((f"conv3x3_s1_x2-2x13x47x48-{co}", dict(fn="s1_x2", B=2, H=13, W=47, Cin=48, Cout=co)))
+        out.append((f"conv3x3_s1_x2-1x1x1x16-{co}", dict(fn="s1_x2", B=1, H=1, W=1, Cin=16, Cout=co)))
+    for fn in ("s2_x3", "s2_x2"):
+        for co in (128, 256):
+            out.append((f"conv3x3_{fn}-2x25x93x48-{co}", dict(fn=fn, B=2, H=25, W=93, Cin=48, Cout=co)))
+            out.append((f"conv3x3_{fn}-1x2x2x16-{co}", dict(fn=fn, B=1, H=2, W=2, Cin=16, Cout=co)))
     return out
 
 
@@ -59,10 +68,11 @@ def run_case(R, spec):
     def dev(a):
         return torch.from_numpy(a).cuda()
     B, H, W, ci, co = spec["B"], spec["H"], spec["W"], spec["Cin"], spec["Cout"]
-    if spec["fn"] == "c3":
+    if spec["fn"] != "ifn":
+        fn = "x3" if spec["fn"] == "c3" else spec["fn"]
         x = dev(hashed_f32((B, H, W, ci), 3, 1)).permute(0, 3, 1, 2)
-        img = R.conv3x3_x3_pack(dev(hashed_f32((co, ci, 3, 3), 1, 2)))
-        y = R.conv3x3_x3(x, img, co).permute(0, 2, 3, 1)
+        img = getattr(R, f"conv3x3_{fn}_pack")(dev(hashed_f32((co, ci, 3, 3), 1, 2)))
+        y = getattr(R, f"conv3x3_{fn}")(x, img, co).permute(0, 2, 3, 1)
     else:
         kind, full = spec["kind"], spec["full"]
         Ho, Wo = {K3S1: (H, W), K3S2: ((H + 1) // 2, (W + 1) // 2), T4S2: (2 * H, 2 * W)}[kind]

@@ -126,23 +126,11 @@ def lib():
     L.vd3d_attention_x3.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, i32, vp, C.c_int64, vp]
     L.vd3d_attention_f32.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp]
     L.vd3d_attention_f32_form.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, i32]
-    L.vd3d_conv3x3_x2_weight_bytes.argtypes = [i32, i32]
-    L.vd3d_conv3x3_x2_weight_bytes.restype = C.c_int64
-    L.vd3d_conv3x3_x2_pack_weights.argtypes = [vp, vp, i32, i32, vp]
-    L.vd3d_conv3x3_x2.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
-    L.vd3d_conv3x3_x3_weight_bytes.argtypes = [i32, i32]
-    L.vd3d_conv3x3_x3_weight_bytes.restype = C.c_int64
-    L.vd3d_conv3x3_x3_pack_weights.argtypes = [vp, vp, i32, i32, vp]
-    L.vd3d_conv3x3_x3.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
-    L.vd3d_conv3x3_s2_x3_weight_bytes.argtypes = [i32, i32]
-    L.vd3d_conv3x3_s2_x3_weight_bytes.restype = C.c_int64
-    L.vd3d_conv3x3_s2_x3_pack_weights.argtypes = [vp, vp, i32, i32, vp]
-    L.vd3d_conv3x3_s2_x3.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
-    for st in ("s1", "s2"):   # the fp16x2 forms of the two tile convolutions
-        getattr(L, f"vd3d_conv3x3_{st}_x2_weight_bytes").argtypes = [i32, i32]
-        getattr(L, f"vd3d_conv3x3_{st}_x2_weight_bytes").restype = C.c_int64
-        getattr(L, f"vd3d_conv3x3_{st}_x2_pack_weights").argtypes = [vp, vp, i32, i32, vp]
-        getattr(L, f"vd3d_conv3x3_{st}_x2").argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
+    for fam in ("x2", "x3", "s2_x3", "s1_x2", "s2_x2"):   # the 3 x 3 convolutions on dense maps: one signature (render_3d.Renderer._conv3x3*)
+        getattr(L, f"vd3d_conv3x3_{fam}_weight_bytes").argtypes = [i32, i32]
+        getattr(L, f"vd3d_conv3x3_{fam}_weight_bytes").restype = C.c_int64
+        getattr(L, f"vd3d_conv3x3_{fam}_pack_weights").argtypes = [vp, vp, i32, i32, vp]
+        getattr(L, f"vd3d_conv3x3_{fam}").argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
     L.vd3d_conv_ifn_weight_bytes.argtypes = [i32, i32, i32]
     L.vd3d_conv_ifn_weight_bytes.restype = C.c_int64
     L.vd3d_conv_ifn_pack_weights.argtypes = [vp, i32, vp, i32, i32, vp]

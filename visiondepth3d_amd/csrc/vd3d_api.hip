@@ -1730,105 +1730,67 @@ VD3D_EXPORT int vd3d_conv3x3_x2(vd3d_ctx* c, const float* X, int B, int H, int W
   return 0;
 }
 
-VD3D_EXPORT int64_t vd3d_conv3x3_x3_weight_bytes(int Cin, int Cout) { return (int64_t)vd_conv3x3_x3_weight_bytes(Cin, Cout); }
+// the tile convolutions on dense, bias-free maps: one kernel body (vd3d_conv_x3.h) in two arithmetics and two strides, one checked entry point for all four.
+// x3: bf16x3, stride 1 (vd3d_conv_x3.hip); s2_x3: its stride-2 form for the reassemble stage's wide maps (launch: vd3d_conv_s2.hip), C_out in multiples of 128;
+// s1_x2 / s2_x2: the same two in the fp16x2 arithmetic (vd3d_conv_x2t.hip).
+struct tile_conv_desc {
+  const char* name;
+  const char* cin_cap;    // the shape message's C_in bound, where weight_bytes has one
+  const char* cout_rule;  // the shape message's C_out sentence
+  long long (*weight_bytes)(int Cin, int Cout);
+  bool (*pack)(hipStream_t s, const float* W, int Cin, int Cout, void* img);
+  bool (*launch)(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+};
+#define TILE_CONV(sfx, cap, rule) static const tile_conv_desc tc_##sfx = {"conv3x3_" #sfx, cap, rule, vd_conv3x3_##sfx##_weight_bytes, vd_launch_conv3x3_##sfx##_pack, vd_launch_conv3x3_##sfx}
+TILE_CONV(x3, "", "one of 32, 64, 128, 256");
+TILE_CONV(s2_x3, " (at most 65536)", "a positive multiple of 128 (at most 1024)");
+TILE_CONV(s1_x2, " (at most 65536)", "one of 32, 64, 128, 256");
+TILE_CONV(s2_x2, " (at most 65536)", "a positive multiple of 128 (at most 1024)");
+#undef TILE_CONV
 
-static int conv3x3_x3_shape_err(int Cin, int Cout) {
-  return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: shape not built: C_in %d must be a positive multiple of 16 and C_out %d one of 32, 64, 128, 256", Cin, Cout);
+static int tile_conv_shape_err(const tile_conv_desc& d, int Cin, int Cout) {
+  return set_err(VD3D_E_UNSUPPORTED, "%s: shape not built: C_in %d must be a positive multiple of 16%s and C_out %d %s", d.name, Cin, d.cin_cap, Cout, d.cout_rule);
 }
-
-VD3D_EXPORT int vd3d_conv3x3_x3_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
+static int tile_conv_pack(const tile_conv_desc& d, vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
   if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
-  if (vd_conv3x3_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_x3_shape_err(Cin, Cout);
-  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: the weight image must be 16-byte aligned");
+  if (d.weight_bytes(Cin, Cout) < 0) return tile_conv_shape_err(d, Cin, Cout);
+  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "%s: the weight image must be 16-byte aligned", d.name);
   HIPCHK(hipSetDevice(c->device));
-  if (!vd_launch_conv3x3_x3_pack(c->stream, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "conv3x3_x3: the weight pack launch failed");
+  if (!d.pack(c->stream, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "%s: the weight pack launch failed", d.name);
   HIPCHK(hipGetLastError());
   return 0;
 }
-
+static int tile_conv_run(const tile_conv_desc& d, vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
+  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
+  if (d.weight_bytes(Cin, Cout) < 0) return tile_conv_shape_err(d, Cin, Cout);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "%s: batch %d must be 1 .. 65535 (one grid row per frame)", d.name, B);
+  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "%s: map %d x %d must be at least 1 x 1", d.name, H, W);
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "%s: the input and the weight image must be 16-byte aligned (the output 4-byte)", d.name);
+  HIPCHK(hipSetDevice(c->device));
+  if (!d.launch(c->stream, X, B, H, W, Cin, w_image, Cout, Y)) return set_err(VD3D_E_HIP, "%s: the dynamic LDS opt-in or the launch failed", d.name);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int64_t vd3d_conv3x3_x3_weight_bytes(int Cin, int Cout) { return (int64_t)tc_x3.weight_bytes(Cin, Cout); }
+VD3D_EXPORT int vd3d_conv3x3_x3_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return tile_conv_pack(tc_x3, c, W, Cin, Cout, image); }
 VD3D_EXPORT int vd3d_conv3x3_x3(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
-  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
-  if (vd_conv3x3_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_x3_shape_err(Cin, Cout);
-  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: batch %d must be 1 .. 65535 (one grid row per frame)", B);
-  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: map %d x %d must be at least 1 x 1", H, W);
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
-    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_x3: the input and the weight image must be 16-byte aligned (the output 4-byte)");
-  HIPCHK(hipSetDevice(c->device));
-  if (!vd_launch_conv3x3_x3(c->stream, X, B, H, W, Cin, w_image, Cout, Y)) return set_err(VD3D_E_HIP, "conv3x3_x3: the dynamic LDS opt-in or the launch failed");
-  HIPCHK(hipGetLastError());
-  return 0;
+  return tile_conv_run(tc_x3, c, X, B, H, W, Cin, w_image, Cout, Y);
 }
-
-// the stride-2 form for the reassemble stage's wide maps (vd3d_conv_s2.hip): the same rules, C_out in multiples of 128
-VD3D_EXPORT int64_t vd3d_conv3x3_s2_x3_weight_bytes(int Cin, int Cout) { return (int64_t)vd_conv3x3_s2_x3_weight_bytes(Cin, Cout); }
-
-static int conv3x3_s2_x3_shape_err(int Cin, int Cout) {
-  return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: shape not built: C_in %d must be a positive multiple of 16 (at most 65536) and C_out %d a positive multiple of 128 (at most 1024)",
-                 Cin, Cout);
-}
-
-VD3D_EXPORT int vd3d_conv3x3_s2_x3_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
-  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
-  if (vd_conv3x3_s2_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_s2_x3_shape_err(Cin, Cout);
-  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: the weight image must be 16-byte aligned");
-  HIPCHK(hipSetDevice(c->device));
-  if (!vd_launch_conv3x3_s2_x3_pack(c->stream, W, Cin, Cout, image)) return set_err(VD3D_E_HIP, "conv3x3_s2_x3: the weight pack launch failed");
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
+VD3D_EXPORT int64_t vd3d_conv3x3_s2_x3_weight_bytes(int Cin, int Cout) { return (int64_t)tc_s2_x3.weight_bytes(Cin, Cout); }
+VD3D_EXPORT int vd3d_conv3x3_s2_x3_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return tile_conv_pack(tc_s2_x3, c, W, Cin, Cout, image); }
 VD3D_EXPORT int vd3d_conv3x3_s2_x3(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
-  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
-  if (vd_conv3x3_s2_x3_weight_bytes(Cin, Cout) < 0) return conv3x3_s2_x3_shape_err(Cin, Cout);
-  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: batch %d must be 1 .. 65535 (one grid row per frame)", B);
-  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: map %d x %d must be at least 1 x 1", H, W);
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
-    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_s2_x3: the input and the weight image must be 16-byte aligned (the output 4-byte)");
-  HIPCHK(hipSetDevice(c->device));
-  if (!vd_launch_conv3x3_s2_x3(c->stream, X, B, H, W, Cin, w_image, Cout, Y)) return set_err(VD3D_E_HIP, "conv3x3_s2_x3: the dynamic LDS opt-in or the launch failed");
-  HIPCHK(hipGetLastError());
-  return 0;
+  return tile_conv_run(tc_s2_x3, c, X, B, H, W, Cin, w_image, Cout, Y);
 }
-
-// the two tile convolutions in the fp16x2 arithmetic (vd3d_conv_x2t.hip): the rules of their bf16x3 forms, one body for both strides
-static const char* conv_x2t_name(bool s2) { return s2 ? "conv3x3_s2_x2" : "conv3x3_s1_x2"; }
-static long long conv_x2t_bytes(bool s2, int Cin, int Cout) { return s2 ? vd_conv3x3_s2_x2_weight_bytes(Cin, Cout) : vd_conv3x3_s1_x2_weight_bytes(Cin, Cout); }
-static int conv_x2t_shape_err(bool s2, int Cin, int Cout) {
-  return set_err(VD3D_E_UNSUPPORTED, "%s: shape not built: C_in %d must be a positive multiple of 16 (at most 65536) and C_out %d %s", conv_x2t_name(s2), Cin, Cout,
-                 s2 ? "a positive multiple of 128 (at most 1024)" : "one of 32, 64, 128, 256");
-}
-static int conv_x2t_pack(bool s2, vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {
-  if (!c || !W || !image) return set_err(VD3D_E_INVALID, "bad argument");
-  if (conv_x2t_bytes(s2, Cin, Cout) < 0) return conv_x2t_shape_err(s2, Cin, Cout);
-  if (reinterpret_cast<uintptr_t>(image) & 15) return set_err(VD3D_E_UNSUPPORTED, "%s: the weight image must be 16-byte aligned", conv_x2t_name(s2));
-  HIPCHK(hipSetDevice(c->device));
-  if (!(s2 ? vd_launch_conv3x3_s2_x2_pack : vd_launch_conv3x3_s1_x2_pack)(c->stream, W, Cin, Cout, image))
-    return set_err(VD3D_E_HIP, "%s: the weight pack launch failed", conv_x2t_name(s2));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-static int conv_x2t_run(bool s2, vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
-  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "bad argument");
-  if (conv_x2t_bytes(s2, Cin, Cout) < 0) return conv_x2t_shape_err(s2, Cin, Cout);
-  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "%s: batch %d must be 1 .. 65535 (one grid row per frame)", conv_x2t_name(s2), B);
-  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "%s: map %d x %d must be at least 1 x 1", conv_x2t_name(s2), H, W);
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3))
-    return set_err(VD3D_E_UNSUPPORTED, "%s: the input and the weight image must be 16-byte aligned (the output 4-byte)", conv_x2t_name(s2));
-  HIPCHK(hipSetDevice(c->device));
-  if (!(s2 ? vd_launch_conv3x3_s2_x2 : vd_launch_conv3x3_s1_x2)(c->stream, X, B, H, W, Cin, w_image, Cout, Y))
-    return set_err(VD3D_E_HIP, "%s: the dynamic LDS opt-in or the launch failed", conv_x2t_name(s2));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-VD3D_EXPORT int64_t vd3d_conv3x3_s1_x2_weight_bytes(int Cin, int Cout) { return (int64_t)conv_x2t_bytes(false, Cin, Cout); }
-VD3D_EXPORT int vd3d_conv3x3_s1_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return conv_x2t_pack(false, c, W, Cin, Cout, image); }
+VD3D_EXPORT int64_t vd3d_conv3x3_s1_x2_weight_bytes(int Cin, int Cout) { return (int64_t)tc_s1_x2.weight_bytes(Cin, Cout); }
+VD3D_EXPORT int vd3d_conv3x3_s1_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return tile_conv_pack(tc_s1_x2, c, W, Cin, Cout, image); }
 VD3D_EXPORT int vd3d_conv3x3_s1_x2(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
-  return conv_x2t_run(false, c, X, B, H, W, Cin, w_image, Cout, Y);
+  return tile_conv_run(tc_s1_x2, c, X, B, H, W, Cin, w_image, Cout, Y);
 }
-VD3D_EXPORT int64_t vd3d_conv3x3_s2_x2_weight_bytes(int Cin, int Cout) { return (int64_t)conv_x2t_bytes(true, Cin, Cout); }
-VD3D_EXPORT int vd3d_conv3x3_s2_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return conv_x2t_pack(true, c, W, Cin, Cout, image); }
+VD3D_EXPORT int64_t vd3d_conv3x3_s2_x2_weight_bytes(int Cin, int Cout) { return (int64_t)tc_s2_x2.weight_bytes(Cin, Cout); }
+VD3D_EXPORT int vd3d_conv3x3_s2_x2_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) { return tile_conv_pack(tc_s2_x2, c, W, Cin, Cout, image); }
 VD3D_EXPORT int vd3d_conv3x3_s2_x2(vd3d_ctx* c, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y) {
-  return conv_x2t_run(true, c, X, B, H, W, Cin, w_image, Cout, Y);
+  return tile_conv_run(tc_s2_x2, c, X, B, H, W, Cin, w_image, Cout, Y);
 }
 
 // the convolutions of the interpolation network (vd3d_conv_ifn.hip): every rule of include/vd3d.h is checked here, before anything is launched

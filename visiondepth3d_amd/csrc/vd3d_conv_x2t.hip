@@ -9,6 +9,7 @@
 // non-finite, never a finite wrong number.
 // Weight image: [slice][step][term 2][k-half 2][oc CK][8 fp16] (64 CK bytes per step, CK = min(C_out, 128), the steps of a slice contiguous and in the order a
 // workgroup runs them: vd3d_conv_x3.hip), then colscale[C_out] = 2^-e as float32, then 64 zero bytes (the zero page of the padding and of DMA lanes past a step).
+// c2t_launch selects the kernel; the checks, the argument block and the grid are cx_dense_args's (vd3d_conv_x3.h).
 #include "vd3d_dev.h"
 #include "vd3d_conv_x3.h"
 
@@ -87,26 +88,18 @@ bool vd_launch_conv3x3_s2_x2_pack(hipStream_t s, const float* W, int Cin, int Co
 
 // the entry points have checked the shape; false: a broken pointer rule, or the dynamic-LDS attribute could not be set
 static bool c2t_launch(hipStream_t s, int kind, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y) {
-  if (B < 1 || H < 1 || W < 1 || B > 65535) return false;
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3)) return false;
+  const float* cs = reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(wimg) + c2t_steps_bytes(Cin, Cout));   // colscale[C_out], then the zero page
+  vd_cx_args a;
+  dim3 grid;
+  if (!cx_dense_args(kind, X, B, H, W, Cin, wimg, Cout, Y, cs, cs + Cout, a, grid)) return false;
   static bool attr_set[64] = {};   // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute (vd3d_kernels.h)
   if (!vd_lds_optin({{reinterpret_cast<const void*>(k_conv_x2<CX_K3S1, 8, 1>), cx_lds_m(1, 32)}, {reinterpret_cast<const void*>(k_conv_x2<CX_K3S1, 4, 1>), cx_lds_m(1, 64)},
                      {reinterpret_cast<const void*>(k_conv_x2<CX_K3S1, 4, 2>), cx_lds_m(1, 128)}, {reinterpret_cast<const void*>(k_conv_x2<CX_K3S2, 4, 2>), cx_lds_m(1, 128)}},
                     attr_set)) return false;
-  vd_cx_args a;
-  const uint8_t* wi = reinterpret_cast<const uint8_t*>(wimg);
-  const long long sb = c2t_steps_bytes(Cin, Cout);
-  a.X = X; a.Wimg = wi; a.colscale = reinterpret_cast<const float*>(wi + sb); a.zero16 = reinterpret_cast<const float*>(wi + sb + (long long)Cout * 4);
-  a.bias = nullptr; a.slope = nullptr; a.R = nullptr; a.Y = Y;
-  a.B = B; a.H = H; a.W = W;
-  a.Ho = kind == CX_K3S2 ? (H + 1) / 2 : H; a.Wo = kind == CX_K3S2 ? (W + 1) / 2 : W;   // the tile grid is the output in both geometries
-  a.x_stride = Cin; a.y_stride = Cout; a.y_offset = 0; a.r_stride = 0; a.nchunk = Cin / 16;
-  a.ntx = (a.Wo + CX_TW - 1) / CX_TW;
-  const unsigned tiles = (unsigned)(a.ntx * ((a.Ho + CX_TH - 1) / CX_TH));
-  if (kind == CX_K3S2) hipLaunchKernelGGL((k_conv_x2<CX_K3S2, 4, 2>), dim3(tiles, (unsigned)B, (unsigned)(Cout / 128)), dim3(CX_NT), cx_lds_m(1, 128), s, a);
-  else if (Cout == 32) hipLaunchKernelGGL((k_conv_x2<CX_K3S1, 8, 1>), dim3(tiles, (unsigned)B), dim3(CX_NT), cx_lds_m(1, 32), s, a);   // the head's 64 -> 32
-  else if (Cout == 64) hipLaunchKernelGGL((k_conv_x2<CX_K3S1, 4, 1>), dim3(tiles, (unsigned)B), dim3(CX_NT), cx_lds_m(1, 64), s, a);
-  else hipLaunchKernelGGL((k_conv_x2<CX_K3S1, 4, 2>), dim3(tiles, (unsigned)B, (unsigned)(Cout / 128)), dim3(CX_NT), cx_lds_m(1, 128), s, a);   // 128, or 256 as two slices
+  if (kind == CX_K3S2) hipLaunchKernelGGL((k_conv_x2<CX_K3S2, 4, 2>), grid, dim3(CX_NT), cx_lds_m(1, 128), s, a);
+  else if (Cout == 32) hipLaunchKernelGGL((k_conv_x2<CX_K3S1, 8, 1>), grid, dim3(CX_NT), cx_lds_m(1, 32), s, a);   // the head's 64 -> 32
+  else if (Cout == 64) hipLaunchKernelGGL((k_conv_x2<CX_K3S1, 4, 1>), grid, dim3(CX_NT), cx_lds_m(1, 64), s, a);
+  else hipLaunchKernelGGL((k_conv_x2<CX_K3S1, 4, 2>), grid, dim3(CX_NT), cx_lds_m(1, 128), s, a);   // 128, or 256 as two slices
   return true;
 }
 bool vd_launch_conv3x3_s1_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y) {

@@ -5,6 +5,7 @@
 // one DMA round per stage for every CK), the round-to-nearest fp16 split of the staged pixels, three products per K step (x1 w2, x2 w1 into `lo`, x1 w1 into `acc`;
 // x2 w2 dropped) on v_mfma_f32_32x32x16_f16, and an epilogue that multiplies acc + lo by colscale[oc], the exact power of two the packer divided the channel's
 // weights by.  The DMA counts behind the counted waits are NBP and CX_A_ITERS in both modes (the staging buffer is float32 either way).
+// At the end, host side: cx_dense_args, the checks, argument block and grid of the four dense, bias-free entry points; their launchers keep the kernel selection.
 #pragma once
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
@@ -243,3 +244,20 @@ template <int KIND, int WM, int NWN, bool EPI>
 __global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) { cx_conv<0, KIND, WM, NWN, EPI>(a); }
 template <int KIND, int WM, int NWN>
 __global__ __launch_bounds__(CX_NT) void k_conv_x2(const vd_cx_args a) { cx_conv<1, KIND, WM, NWN, false>(a); }
+
+// ---- host: the dense, bias-free launch that vd3d_conv3x3_x3, vd3d_conv3x3_s2_x3, vd3d_conv3x3_s1_x2 and vd3d_conv3x3_s2_x2 share (kind K3S1 or K3S2; the tile
+// grid is the output in both).  Checks what they all check -- B 1 .. 65535 (one grid row per frame), a map of at least 1 x 1, X and the image 16-byte and Y
+// 4-byte aligned -- and fills the argument block for maps of pitch C_in / C_out and the grid: tiles x frames x 128-channel slices of C_out (one slice below 128).
+// zero16: the image's zero page; colscale: MODE 1's, nullptr in MODE 0.  The caller has checked C_in and C_out and keeps its kernel selection and LDS opt-in.
+inline bool cx_dense_args(int kind, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y, const float* colscale, const float* zero16,
+                          vd_cx_args& a, dim3& grid) {
+  if (B < 1 || H < 1 || W < 1 || B > 65535) return false;
+  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3)) return false;
+  a.X = X; a.Wimg = reinterpret_cast<const uint8_t*>(wimg); a.zero16 = zero16; a.bias = nullptr; a.slope = nullptr; a.R = nullptr; a.Y = Y;
+  a.B = B; a.H = H; a.W = W;
+  a.Ho = kind == CX_K3S2 ? (H + 1) / 2 : H; a.Wo = kind == CX_K3S2 ? (W + 1) / 2 : W;
+  a.x_stride = Cin; a.y_stride = Cout; a.y_offset = 0; a.r_stride = 0; a.nchunk = Cin / 16; a.colscale = colscale;
+  a.ntx = (a.Wo + CX_TW - 1) / CX_TW;
+  grid = dim3((unsigned)(a.ntx * ((a.Ho + CX_TH - 1) / CX_TH)), (unsigned)B, Cout > 128 ? (unsigned)(Cout / 128) : 1u);
+  return true;
+}

@@ -3,7 +3,8 @@
 //   vd3d_conv_ifn    the convolutions of the RIFE interpolation network (IFNet HDv3: three IFBlocks of 14; C_out 32 / 64 / 96; bias, per-channel PReLU and
 //                    residual in the epilogue, channel slices of strided NHWC buffers).
 // and a third one, vd3d_conv3x3_s2_x3 (the reassemble stage's 3 x 3 stride-2 convolution, C_out = 128 n), whose launch is vd3d_conv_s2.hip's and whose weight
-// image is packed here.  The kernel body (cx_conv, vd3d_conv_x3.h) carries a MODE parameter; everything in this file is MODE 0, the fp16x2 form (MODE 1) is
+// image is packed here.  vd3d_conv3x3_x3's launch takes its checks, argument block and grid from cx_dense_args (vd3d_conv_x3.h), as the other dense launches do;
+// vd3d_conv_ifn's strided launch with the epilogue options (cx_launch) fills its own.  The kernel body (cx_conv, vd3d_conv_x3.h) carries a MODE parameter; everything in this file is MODE 0, the fp16x2 form (MODE 1) is
 // vd3d_conv_x2t.hip's.
 // Arithmetic: every float32 operand is split EXACTLY into three bf16 terms by truncation (x3_split); the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 go into a `lo`
 // accumulator and x1 w1 into `acc` (v_mfma_f32_32x32x16_bf16, float32 accumulation, small products first), summed in the epilogue; x2 w3, x3 w2, x3 w3 <= 2^-24
@@ -97,20 +98,18 @@ static void cx_launch_kind(hipStream_t s, dim3 grid, int Cout, const vd_cx_args&
   else if (Cout == 64) hipLaunchKernelGGL((k_conv_x3<KIND, 4, 1, true>), grid, dim3(CX_NT), cx_lds(64), s, a);
   else hipLaunchKernelGGL((k_conv_x3<KIND, 8, 3, true>), grid, dim3(CX_NT), cx_lds(96), s, a);
 }
-static void cx_launch_plain(hipStream_t s, dim3 grid, int Cout, const vd_cx_args& a) {
+static void cx_launch_plain(hipStream_t s, dim3 grid, int Cout, const vd_cx_args& a) {   // grid: cx_dense_args's, with C_out's 128-channel slices on z
   if (Cout == 32) hipLaunchKernelGGL((k_conv_x3<CX_K3S1, 8, 1, false>), grid, dim3(CX_NT), cx_lds(32), s, a);   // the head's 64 -> 32
   else if (Cout == 64) hipLaunchKernelGGL((k_conv_x3<CX_K3S1, 4, 1, false>), grid, dim3(CX_NT), cx_lds(64), s, a);
-  else hipLaunchKernelGGL((k_conv_x3<CX_K3S1, 4, 2, false>), dim3(grid.x, grid.y, Cout / 128), dim3(CX_NT), cx_lds(128), s, a);   // 128, or 256 as two slices
+  else hipLaunchKernelGGL((k_conv_x3<CX_K3S1, 4, 2, false>), grid, dim3(CX_NT), cx_lds(128), s, a);   // 128, or 256 as two slices
 }
-// epi: with the epilogue options (vd3d_conv_ifn).  false: the dynamic-LDS attribute could not be set
-static bool cx_launch(hipStream_t s, bool epi, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* wimg, const float* bias, const float* slope,
+// the strided launch with the epilogue options (vd3d_conv_ifn).  false: the dynamic-LDS attribute could not be set
+static bool cx_launch(hipStream_t s, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* wimg, const float* bias, const float* slope,
                       int Cout, const float* R, int r_stride, float* Y, int y_stride, int y_offset) {
   static bool attr_set[64] = {};   // per device: the > 64 KB dynamic-LDS opt-in is a per-device function attribute (vd3d_kernels.h)
 #define CX_FN(K) {reinterpret_cast<const void*>(k_conv_x3<K, 8, 1, true>), cx_lds(32)}, {reinterpret_cast<const void*>(k_conv_x3<K, 4, 1, true>), cx_lds(64)}, \
                  {reinterpret_cast<const void*>(k_conv_x3<K, 8, 3, true>), cx_lds(96)}
-  if (!vd_lds_optin({CX_FN(CX_K3S1), CX_FN(CX_K3S2), CX_FN(CX_T4S2), {reinterpret_cast<const void*>(k_conv_x3<CX_K3S1, 8, 1, false>), cx_lds(32)},
-                     {reinterpret_cast<const void*>(k_conv_x3<CX_K3S1, 4, 1, false>), cx_lds(64)},
-                     {reinterpret_cast<const void*>(k_conv_x3<CX_K3S1, 4, 2, false>), cx_lds(128)}}, attr_set)) return false;
+  if (!vd_lds_optin({CX_FN(CX_K3S1), CX_FN(CX_K3S2), CX_FN(CX_T4S2)}, attr_set)) return false;
 #undef CX_FN
   vd_cx_args a;
   const uint8_t* wi = reinterpret_cast<const uint8_t*>(wimg);
@@ -122,8 +121,7 @@ static bool cx_launch(hipStream_t s, bool epi, int kind, const float* X, int B, 
   const int gh = kind == CX_K3S2 ? a.Ho : H, gw = kind == CX_K3S2 ? a.Wo : W;   // the tile grid
   a.ntx = (gw + CX_TW - 1) / CX_TW;
   const dim3 grid((unsigned)(a.ntx * ((gh + CX_TH - 1) / CX_TH)), (unsigned)B, kind == CX_T4S2 ? 4u : 1u);
-  if (!epi) cx_launch_plain(s, grid, Cout, a);
-  else if (kind == CX_K3S1) cx_launch_kind<CX_K3S1>(s, grid, Cout, a);
+  if (kind == CX_K3S1) cx_launch_kind<CX_K3S1>(s, grid, Cout, a);
   else if (kind == CX_K3S2) cx_launch_kind<CX_K3S2>(s, grid, Cout, a);
   else cx_launch_kind<CX_T4S2>(s, grid, Cout, a);
   return true;
@@ -138,9 +136,16 @@ bool vd_launch_conv3x3_x3_pack(hipStream_t s, const float* W, int Cin, int Cout,
   return vd_conv3x3_x3_weight_bytes(Cin, Cout) >= 0 && cx_pack(s, CX_K3S1, W, Cin, Cout, img);
 }
 bool vd_launch_conv3x3_x3(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y) {
-  if (vd_conv3x3_x3_weight_bytes(Cin, Cout) < 0 || B < 1 || H < 1 || W < 1 || B > 65535) return false;
-  if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(wimg) & 15) || (reinterpret_cast<uintptr_t>(Y) & 3)) return false;
-  return cx_launch(s, false, CX_K3S1, X, B, H, W, Cin, Cin, wimg, nullptr, nullptr, Cout, nullptr, 0, Y, Cout, 0);
+  const long long wb = vd_conv3x3_x3_weight_bytes(Cin, Cout);
+  vd_cx_args a;
+  dim3 grid;
+  if (wb < 0 || !cx_dense_args(CX_K3S1, X, B, H, W, Cin, wimg, Cout, Y, nullptr, reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(wimg) + wb - 64), a, grid))
+    return false;
+  static bool attr_set[64] = {};   // per device, as in cx_launch
+  if (!vd_lds_optin({{reinterpret_cast<const void*>(k_conv_x3<CX_K3S1, 8, 1, false>), cx_lds(32)}, {reinterpret_cast<const void*>(k_conv_x3<CX_K3S1, 4, 1, false>), cx_lds(64)},
+                     {reinterpret_cast<const void*>(k_conv_x3<CX_K3S1, 4, 2, false>), cx_lds(128)}}, attr_set)) return false;
+  cx_launch_plain(s, grid, Cout, a);
+  return true;
 }
 
 // ---- vd3d_conv3x3_s2_x3 (host half; the launch is vd3d_conv_s2.hip's): K3S2 on dense maps, C_out = 128 n as n channel slices
@@ -163,5 +168,5 @@ bool vd_launch_conv_ifn_pack(hipStream_t s, int kind, const float* W, int Cin, i
 bool vd_launch_conv_ifn(hipStream_t s, int kind, const float* X, int B, int H, int W, int x_stride, int Cin, const void* wimg, const float* bias,
                         const float* slope, int Cout, const float* R, int r_stride, float* Y, int y_stride, int y_offset) {
   if (vd_conv_ifn_weight_bytes(kind, Cin, Cout) < 0 || B < 1 || B > 65535 || H < 1 || W < 1) return false;
-  return cx_launch(s, true, kind, X, B, H, W, x_stride, Cin, wimg, bias, slope, Cout, R, r_stride, Y, y_stride, y_offset);
+  return cx_launch(s, kind, X, B, H, W, x_stride, Cin, wimg, bias, slope, Cout, R, r_stride, Y, y_stride, y_offset);
 }

@@ -124,6 +124,25 @@ def conv_transpose_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     return w.detach().permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous()
 
 
+class _ConvTransposeGemm:
+    """ConvTranspose2d ``m`` with kernel == stride s and no padding (the caller has checked) on renderer R: packed once as conv_transpose_gemm_weight for
+    vd3d_gemm_x3 in ``mode``; a call takes the pixel rows [..., C_in] of a B x gh x gw map through the GEMM (``n`` = s s C_out columns, no bias) and
+    vd3d_depth_to_space_bias_nhwc_f32, which adds the module's bias: the channels_last [B, C_out, s gh, s gw] map."""
+
+    def __init__(self, R, m, mode):
+        self.R, self.m, self.mode, self.n = R, m, mode, m.kernel_size[0] * m.kernel_size[1] * m.out_channels
+        self.img = R.gemm_x3_pack(conv_transpose_gemm_weight(m.weight), mode)
+
+    def __call__(self, rows, B, gh, gw):
+        y = self.R.linear_x3(rows, self.img, self.n, None, mode=self.mode)
+        return self.R.depth_to_space_bias(y.view(B * gh * gw, self.n), B, gh, gw, self.m.kernel_size[0], self.m.bias)
+
+
+def _is_conv(m, k, s, p):
+    """Module m convolves with a k x k kernel at stride s and padding p, dilation 1, in one group."""
+    return m.kernel_size == (k, k) and m.stride == (s, s) and m.padding == (p, p) and m.dilation == (1, 1) and m.groups == 1
+
+
 def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     """Patch-embedding weight [C, 3, p, p] (kernel == stride: every patch is one GEMM row) -> [C, Kp]: the flattened (c, ky, kx) columns, zero-padded from 3 p^2
     to the next multiple of 16 (vd3d_gemm_x3's K unit; p = 14: 588 -> 592).  vd3d_patchify_f32 writes the matching rows, zero tail included."""
@@ -404,6 +423,11 @@ class DepthPipe:
 
         emb.interpolate_pos_encoding = cached
 
+    def _count_conv(self, m, y):
+        """flops_per_frame: a convolution module m that a rewrite runs without calling it adds, for its output y, what the counting hook would have added."""
+        if self._flop_count is not None:
+            self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1]
+
     def _patch_dpt_upsampling(self):
         """The DPT neck / head between the library convolutions (transformers DepthAnythingReassembleStage / PreActResidualLayer /
         FeatureFusionLayer / DepthEstimationHead; the module graphs are otherwise reproduced verbatim):
@@ -431,8 +455,7 @@ class DepthPipe:
         conv_img = {}   # fp16x2 mode: packed weights per convolution module (None = shape not built: the library convolution stays)
 
         def conv_x2(m, x):
-            if (self.gemm != "fp16x2" or self.conv is not None or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
-                    or x.dtype != torch.float32):
+            if self.gemm != "fp16x2" or self.conv is not None or not f32 or not _is_conv(m, 3, 1, 1) or x.dtype != torch.float32:
                 return None
             key = id(m)
             if key not in conv_img:
@@ -446,27 +469,23 @@ class DepthPipe:
 
         conv3_img = {}   # conv="bf16x3" / "fp16x2": packed weights per convolution module (None = shape not built)
         names = {id(m): n for n, m in self.model.named_modules()}
-        cm = self.conv   # the tile convolution of the mode: vd3d_conv3x3_x3 | vd3d_conv3x3_s1_x2, one kernel for every routed convolution
-        tile_fn, min_tiles = ("conv3x3_s1_x2", CONV_X2_MIN_TILES) if cm == "fp16x2" else ("conv3x3_x3", CONV_X3_MIN_TILES)   # Renderer methods, looked up per call
-
-        def tile_conv(x, img, n):
-            return getattr(R, tile_fn)(x, img, n)
+        cm = self.conv   # the tile convolution of the mode (Renderer.TILE_CONVS: vd3d_conv3x3_x3 | vd3d_conv3x3_s1_x2), one kernel for every routed convolution
+        min_tiles = CONV_X2_MIN_TILES if cm == "fp16x2" else CONV_X3_MIN_TILES
 
         def conv_x3(m, x):
-            if (cm is None or not f32 or m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1
-                    or x.dtype != torch.float32):
+            if cm is None or not f32 or not _is_conv(m, 3, 1, 1) or x.dtype != torch.float32:
                 return None
             key = id(m)
             if key not in conv3_img:
-                conv3_img[key] = getattr(R, tile_fn + "_pack")(m.weight)
+                conv3_img[key] = R.conv3x3_tile_pack(m.weight, cm, 1)
             if conv3_img[key] is None:
                 if sc:
-                    raise NotImplementedError(f"self_contained=True: {names[key]}: vd3d_{tile_fn} does not build {m.in_channels} -> {m.out_channels} channels")
+                    raise NotImplementedError(f"self_contained=True: {names[key]}: vd3d_conv3x3_{R.TILE_CONVS[cm, 1]} does not build {m.in_channels} -> {m.out_channels} channels")
                 self.conv_routes[names[key]] = ("library", f"shape not built: {m.in_channels} -> {m.out_channels} channels")
                 return None
             if sc:   # no size rule: every map, the 19 x 33 ones included
                 self.conv_routes[names[key]] = (cm, "self-contained")
-                return tile_conv(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
+                return R.conv3x3_tile(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels, cm, 1)
             if cm == "fp16x2":   # the rule of this mode reads the map alone, never the batch: a frame's route and bits do not depend on what it is batched with
                 tiles = ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)
             else:
@@ -475,7 +494,7 @@ class DepthPipe:
                 self.conv_routes[names[key]] = ("library", f"size rule: {tiles} tiles < {min_tiles}")
                 return None
             self.conv_routes[names[key]] = (cm, f"{tiles} tiles")
-            return tile_conv(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels)
+            return R.conv3x3_tile(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels, cm, 1)
 
         if cm is not None and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
             for m in self.model.neck.convs:
@@ -497,23 +516,21 @@ class DepthPipe:
                 raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 3 x 3 / stride 1 / padding 1 convolution -- not built")
             if y is None:
                 y = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups).contiguous(memory_format=CL)
-            if self._flop_count is not None:   # flops_per_frame: these calls bypass the modules' forward hooks
-                self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1]
+            self._count_conv(m, y)   # these calls bypass the modules' forward hooks
             return y
 
         gemm_img = {}   # self-contained: packed weights of the 1 x 1 projections / transposed convolutions per module
 
         def conv1x1_x3(m, x):
             """Self-contained: a 1 x 1 convolution WITHOUT its bias as vd3d_gemm_x3 over the pixel rows of a channels_last map (its NHWC storage is the row matrix)."""
-            if m.kernel_size != (1, 1) or m.stride != (1, 1) or m.padding != (0, 0) or m.groups != 1 or m.in_channels % 16 or x.dtype != torch.float32:
+            if not _is_conv(m, 1, 1, 0) or m.in_channels % 16 or x.dtype != torch.float32:
                 raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 1 x 1 convolution with C_in a multiple of 16 -- not built")
             if id(m) not in gemm_img:
                 gemm_img[id(m)] = R.gemm_x3_pack(m.weight.reshape(m.out_channels, m.in_channels), self.gemm)
             rows = x.contiguous(memory_format=CL).permute(0, 2, 3, 1)   # [B, h, w, C] contiguous
             y = R.linear_x3(rows, gemm_img[id(m)], m.out_channels, None, mode=self.gemm).permute(0, 3, 1, 2)
             self.conv_routes[names[id(m)]] = (self.gemm, "self-contained: vd3d_gemm_x3 over the pixel rows")
-            if self._flop_count is not None:   # flops_per_frame: what conv_nb adds for the same module
-                self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * m.in_channels
+            self._count_conv(m, y)   # what conv_nb adds for the same module
             return y
 
         def res_unit(unit, x, x_relu=None, extra=None, want_relu=False):
@@ -564,7 +581,7 @@ class DepthPipe:
             m = head.conv2
             if os.environ.get("VD3D_HEAD_FUSED", "1") == "0":
                 return None, "VD3D_HEAD_FUSED=0"
-            if m.kernel_size != (3, 3) or m.stride != (1, 1) or m.padding != (1, 1) or m.dilation != (1, 1) or m.groups != 1:
+            if not _is_conv(m, 3, 1, 1):
                 return None, "not a 3 x 3 / stride 1 / padding 1 convolution"
             try:
                 key = (m.weight.data_ptr(), m.weight._version)
@@ -617,17 +634,16 @@ class DepthPipe:
         stage.forward = self._self_contained_reassemble(names) if sc else reassemble_fwd
 
     def _self_contained_reassemble(self, names):
-        """The DINOv2 reassemble stage without a library call (self_contained=True) -- DPT-Large's route (_patch_dpt_vit_reassemble_head) without the readout: per
-        hook, the tokens minus CLS are the rows of the 1 x 1 projection (linear_x3 with its bias; [B, T-1, C_i] is NHWC storage); ConvTranspose2d (kernel == stride,
-        no padding) is a linear_x3 on conv_transpose_gemm_weight + vd3d_depth_to_space_bias_nhwc_f32; Identity stays; the 3 x 3 / stride 2 / padding 1 convolution
-        runs on vd3d_conv3x3_s2_x3 with its bias through bias_act.  Any other resize module is refused by name, here, at construction."""
-        R, CL, gm = self.renderer, torch.channels_last, self.gemm
-        s2_fn = "conv3x3_s2_x2" if gm == "fp16x2" else "conv3x3_s2_x3"   # the Renderer method of the mode
+        """The DINOv2 reassemble stage without a library call (self_contained=True): per hook, the tokens minus CLS are the rows of the 1 x 1 projection (linear_x3
+        with its bias; [B, T-1, C_i] is NHWC storage); ConvTranspose2d (kernel == stride, no padding) is a _ConvTransposeGemm, as on DPT-Large's route
+        (_patch_dpt_vit_reassemble_head); Identity stays; the 3 x 3 / stride 2 / padding 1 convolution runs on the stride-2 tile convolution of the mode
+        (vd3d_conv3x3_s2_x3 | vd3d_conv3x3_s2_x2) with its bias through bias_act.  Any other resize module is refused by name, here, at construction."""
+        R, gm = self.renderer, self.gemm
         stage = self.model.neck.reassemble_stage
         hooks = []
         for lay in stage.layers:
             pm, rz = lay.projection, lay.resize
-            if pm.kernel_size != (1, 1) or pm.stride != (1, 1) or pm.padding != (0, 0) or pm.groups != 1 or pm.in_channels % 16:
+            if not _is_conv(pm, 1, 1, 0) or pm.in_channels % 16:
                 raise NotImplementedError(f"self_contained=True: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
             hk = dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm), kind="identity", img=None)
             if isinstance(rz, torch.nn.ConvTranspose2d):
@@ -635,11 +651,9 @@ class DepthPipe:
                         and rz.dilation == (1, 1) and rz.groups == 1 and rz.in_channels % 16 == 0 and rz.out_channels % 4 == 0):
                     raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a ConvTranspose2d with kernel {rz.kernel_size} / stride {rz.stride} / padding "
                                               f"{rz.padding}, {rz.in_channels} -> {rz.out_channels} channels (built: square kernel == stride, no padding, C_in % 16) -- not built")
-                hk["kind"], hk["img"] = "ct", R.gemm_x3_pack(conv_transpose_gemm_weight(rz.weight), gm)
+                hk["kind"], hk["img"] = "ct", _ConvTransposeGemm(R, rz, gm)
             elif isinstance(rz, torch.nn.Conv2d):
-                img = None
-                if rz.kernel_size == (3, 3) and rz.stride == (2, 2) and rz.padding == (1, 1) and rz.dilation == (1, 1) and rz.groups == 1:
-                    img = getattr(R, s2_fn + "_pack")(rz.weight)
+                img = R.conv3x3_tile_pack(rz.weight, gm, 2) if _is_conv(rz, 3, 2, 1) else None
                 if img is None:
                     raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a Conv2d with kernel {rz.kernel_size} / stride {rz.stride} / padding {rz.padding}, "
                                               f"{rz.in_channels} -> {rz.out_channels} channels (built: 3 x 3 / stride 2 / padding 1, C_in % 16, C_out % 128 up to 1024) -- not built")
@@ -647,10 +661,6 @@ class DepthPipe:
             elif not isinstance(rz, torch.nn.Identity):
                 raise NotImplementedError(f"self_contained=True: {names[id(rz)]} ({type(rz).__name__}) is no resize module the mode routes -- not built")
             hooks.append(hk)
-
-        def count(m, y):   # flops_per_frame: the routed modules bypass the counting hooks; this is the hook's own formula for module m with output y, so
-            if self._flop_count is not None:   # that the figure equals the library mode's
-                self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1]
 
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
@@ -666,19 +676,17 @@ class DepthPipe:
                 x = R.linear_x3(hs[:, 1:].contiguous(), hk["proj"], n, pm.bias, mode=gm)         # [B, T-1, C_i]: NHWC storage
                 self.conv_routes[names[id(pm)]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
                 x = x.view(B, gh, gw, n).permute(0, 3, 1, 2)
-                count(pm, x)
+                self._count_conv(pm, x)   # the routed modules bypass the counting hooks: the figure equals the library mode's
                 if hk["kind"] == "ct":
-                    s = rz.kernel_size[0]
-                    y = R.linear_x3(x.permute(0, 2, 3, 1), hk["img"], s * s * rz.out_channels, None, mode=gm)
-                    x = R.depth_to_space_bias(y.view(B * gh * gw, s * s * rz.out_channels), B, gh, gw, s, rz.bias)
+                    x = hk["img"](x.permute(0, 2, 3, 1), B, gh, gw)
                     self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_gemm_x3 + vd3d_depth_to_space_bias_nhwc_f32")
-                    count(rz, x)
+                    self._count_conv(rz, x)
                 elif hk["kind"] == "s2":
-                    x = getattr(R, s2_fn)(x, hk["img"], rz.out_channels)
+                    x = R.conv3x3_tile(x, hk["img"], rz.out_channels, gm, 2)
                     if rz.bias is not None:
                         x = R.bias_act(x, rz.bias)
-                    self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_" + s2_fn)
-                    count(rz, x)
+                    self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_conv3x3_" + R.TILE_CONVS[gm, 2])
+                    self._count_conv(rz, x)
                 out.append(x)
             return out
         return reassemble_fwd
@@ -702,9 +710,9 @@ class DepthPipe:
                 raise NotImplementedError("self_contained=True: the patch embedding takes a float32 [B, 3, th, tw] image")
             rows = R.patchify(pixel_values.contiguous(memory_format=torch.channels_last), p)   # what depth_preprocess hands over is taken as it is
             self.conv_routes[name] = (self.gemm, "self-contained: vd3d_patchify_f32 + vd3d_gemm_x3")
-            if self._flop_count is not None:   # flops_per_frame: the counting hook's formula for the bypassed Conv2d
-                self._flop_count[0] += 2.0 * rows.shape[1] * m.out_channels * 3 * p * p
-            return R.linear_x3(rows, img, m.out_channels, m.bias, mode=self.gemm)
+            y = R.linear_x3(rows, img, m.out_channels, m.bias, mode=self.gemm)
+            self._count_conv(m, y)   # the bypassed Conv2d: 2 (T - 1) C 3 p^2
+            return y
         pe.forward = patch_fwd
 
     def _patch_dpt_vit_reassemble_head(self, conv_nb, f32):
@@ -726,15 +734,13 @@ class DepthPipe:
             gelu = isinstance(ract, torch.nn.GELU) and getattr(ract, "approximate", "none") == "none" or type(ract).__name__ == "GELUActivation"
             pw = lay.projection.weight
             hk = dict(readout=(R.gemm_x3_pack(rl.weight, gm), rl.out_features, rl.bias, gelu, ract),
-                      proj=(R.gemm_x3_pack(pw.reshape(pw.shape[0], -1), gm), pw.shape[0], lay.projection.bias), resize=lay.resize, ct=None)
-            if isinstance(lay.resize, torch.nn.ConvTranspose2d):
-                hk["ct"] = (R.gemm_x3_pack(conv_transpose_gemm_weight(lay.resize.weight), gm), lay.resize.kernel_size[0])
+                      proj=(R.gemm_x3_pack(pw.reshape(pw.shape[0], -1), gm), pw.shape[0], lay.projection.bias), resize=lay.resize,
+                      ct=_ConvTransposeGemm(R, lay.resize, gm) if isinstance(lay.resize, torch.nn.ConvTranspose2d) else None)
             hooks.append(hk)
 
-        def lin(t, img, n, bias, gelu=False, conv=True):
-            if conv and self._flop_count is not None:   # flops_per_frame: the 1x1 projections and transposed convolutions (EXECUTED: P x C_out x C_in) bypass
-                self._flop_count[0] += 2.0 * t.numel() / t.shape[0] * n   # the module hooks; the readout Linear is not a convolution (not counted, as in the stock graph)
-            return R.linear_x3(t, img, n, bias, gelu=gelu, mode=gm)
+        def count_rows(t, n):   # flops_per_frame: the 1x1 projections and transposed convolutions (EXECUTED: P x C_out x C_in) bypass the module hooks;
+            if self._flop_count is not None:   # the readout Linear is not a convolution (not counted, as in the stock graph)
+                self._flop_count[0] += 2.0 * t.numel() / t.shape[0] * n
 
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
@@ -747,13 +753,13 @@ class DepthPipe:
                     raise ValueError(f"{T - 1} patch tokens do not form a {gh} x {gw} grid")
                 img, n, bias, gelu, act = hk["readout"]
                 x = torch.cat((hs[:, 1:], hs[:, :1].expand(B, T - 1, d)), -1)
-                x = lin(x, img, n, bias, gelu=True, conv=False) if gelu else act(lin(x, img, n, bias, conv=False))
+                x = R.linear_x3(x, img, n, bias, gelu=True, mode=gm) if gelu else act(R.linear_x3(x, img, n, bias, mode=gm))
                 img, n, bias = hk["proj"]
-                x = lin(x, img, n, bias)                                                          # [B, T-1, C_i]
+                count_rows(x, n)
+                x = R.linear_x3(x, img, n, bias, mode=gm)                                                       # [B, T-1, C_i]
                 if hk["ct"] is not None:
-                    ct_img, s = hk["ct"]
-                    y = lin(x, ct_img, s * s * n, None)
-                    x = R.depth_to_space_bias(y.view(B * gh * gw, s * s * n), B, gh, gw, s, hk["resize"].bias)
+                    count_rows(x, hk["ct"].n)
+                    x = hk["ct"](x, B, gh, gw)
                 else:
                     x = x.view(B, gh, gw, n).permute(0, 3, 1, 2)   # NHWC storage, NCHW view: channels_last
                     x = hk["resize"](x)                             # identity, or the library's 3 x 3 stride-2 convolution
@@ -1176,10 +1182,8 @@ class DepthPipe:
         backbone = 2.0 * lin * T + 4.0 * T * T * d * L
         total = [0.0]
 
-        def hook(mod, inp, out):
-            if isinstance(mod, (torch.nn.Conv2d, torch.nn.ConvTranspose2d)):
-                k = mod.kernel_size[0] * mod.kernel_size[1]
-                total[0] += 2.0 * out.numel() / out.shape[0] * (mod.in_channels // mod.groups) * k
+        def hook(mod, inp, out):   # registered on the convolution modules only; total is self._flop_count while they run
+            self._count_conv(mod, out)
 
         hs = [m.register_forward_hook(hook) for m in self.model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d))]
         self._flop_count = total   # the bias-free convolution calls of the rewritten neck / head count themselves (EXECUTED flops: the

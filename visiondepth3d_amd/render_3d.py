@@ -876,6 +876,7 @@ class Renderer:
         return out_s, out_n
 
     X3_MODES = {"bf16x3": 0, "fp16x2": 1}
+    TILE_CONVS = {("bf16x3", 1): "x3", ("bf16x3", 2): "s2_x3", ("fp16x2", 1): "s1_x2", ("fp16x2", 2): "s2_x2"}   # (mode, stride) -> vd3d_conv3x3_<family>
 
     def gemm_x3_pack(self, weight: torch.Tensor, mode: str = "bf16x3") -> torch.Tensor:
         """Split + pack a float32 Linear weight [N, K] once for ``linear_x3`` in ``mode`` (include/vd3d.h vd3d_gemm_x3_pack_weights); returns the opaque image (uint8)."""
@@ -934,117 +935,87 @@ class Renderer:
         _lib.check(self._L.vd3d_attention_f32_form(self._ctx, _ptr(qkv), B, T, n_heads, D, float(scale), _ptr(out), int(form)))
         return out
 
-    def conv3x3_x2_pack(self, weight: torch.Tensor):
-        """Split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_x2``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 128})."""
+    def _conv3x3_pack(self, fam: str, weight: torch.Tensor):
+        """The pack of every vd3d_conv3x3_<fam> (_lib.py: one signature): the opaque image, or ``None`` where the kernel is not 3 x 3 or the shape is not built."""
         w = weight.detach().to(self.device, torch.float32).contiguous()
         Cout, Cin, kh, kw = w.shape
-        nb = int(self._L.vd3d_conv3x3_x2_weight_bytes(Cin, Cout)) if (kh, kw) == (3, 3) else -1
+        nb = int(getattr(self._L, f"vd3d_conv3x3_{fam}_weight_bytes")(Cin, Cout)) if (kh, kw) == (3, 3) else -1
         if nb < 0:
             return None
         img = torch.empty(nb, dtype=torch.uint8, device=self.device)
         self._enter(w, img)
-        _lib.check(self._L.vd3d_conv3x3_x2_pack_weights(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
+        _lib.check(getattr(self._L, f"vd3d_conv3x3_{fam}_pack_weights")(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
         return img
+
+    def _conv3x3(self, fam: str, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
+        """The run of every vd3d_conv3x3_<fam>: padding 1, stride 2 for the ``s2_`` families (output (H+1)//2 x (W+1)//2), else stride 1."""
+        B, Cin, H, W = x.shape
+        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
+            raise AssertionError(f"conv3x3_{fam}: float32 channels_last input")
+        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if fam.startswith("s2_") else (H, W)
+        out = torch.empty((B, int(Cout), Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        self._enter(x, w_image, out)
+        _lib.check(getattr(self._L, f"vd3d_conv3x3_{fam}")(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
+        return out
+
+    def conv3x3_tile_pack(self, weight: torch.Tensor, mode: str = "bf16x3", stride: int = 1):
+        """Pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_tile`` in ``mode`` at ``stride`` (``TILE_CONVS``: the 8 x 32 tile kernel's four
+        members); ``None`` when the member does not build the shape.  Goes through the member's public method, looked up per call, like ``conv3x3_tile``."""
+        return getattr(self, f"conv3x3_{self.TILE_CONVS[mode, stride]}_pack")(weight)
+
+    def conv3x3_tile(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int, mode: str = "bf16x3", stride: int = 1) -> torch.Tensor:
+        """F.conv2d(x, W, None, stride, padding 1) for a float32 channels_last tensor with W given as ``conv3x3_tile_pack(W, mode, stride)``: the call of the
+        member's public method, looked up per call (a wrapper put on ``conv3x3_x3`` to count its calls sees DepthPipe's)."""
+        return getattr(self, f"conv3x3_{self.TILE_CONVS[mode, stride]}")(x, w_image, Cout)
+
+    def conv3x3_x2_pack(self, weight: torch.Tensor):
+        """Split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_x2``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 128})."""
+        return self._conv3x3_pack("x2", weight)
 
     def conv3x3_x2(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
         """F.conv2d(x, W, None, stride 1, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_x2_pack(W)``: fp16x2 MFMA arithmetic,
         float32 accumulation (include/vd3d.h vd3d_conv3x3_x2); returns a channels_last [B, Cout, H, W] tensor."""
-        B, Cin, H, W = x.shape
-        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
-            raise AssertionError("conv3x3_x2: float32 channels_last input")
-        out = torch.empty((B, int(Cout), H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        self._enter(x, w_image, out)
-        _lib.check(self._L.vd3d_conv3x3_x2(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
-        return out
+        return self._conv3x3("x2", x, w_image, Cout)
 
     def conv3x3_x3_pack(self, weight: torch.Tensor):
         """Split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_x3``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 128, 256})."""
-        w = weight.detach().to(self.device, torch.float32).contiguous()
-        Cout, Cin, kh, kw = w.shape
-        nb = int(self._L.vd3d_conv3x3_x3_weight_bytes(Cin, Cout)) if (kh, kw) == (3, 3) else -1
-        if nb < 0:
-            return None
-        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._enter(w, img)
-        _lib.check(self._L.vd3d_conv3x3_x3_pack_weights(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
-        return img
+        return self._conv3x3_pack("x3", weight)
 
     def conv3x3_x3(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
         """F.conv2d(x, W, None, stride 1, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_x3_pack(W)``: bf16x3 MFMA arithmetic
         (three bf16 terms per operand, six products per MAC), float32 accumulation (include/vd3d.h vd3d_conv3x3_x3); returns a channels_last [B, Cout, H, W] tensor."""
-        B, Cin, H, W = x.shape
-        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
-            raise AssertionError("conv3x3_x3: float32 channels_last input")
-        out = torch.empty((B, int(Cout), H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        self._enter(x, w_image, out)
-        _lib.check(self._L.vd3d_conv3x3_x3(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
-        return out
+        return self._conv3x3("x3", x, w_image, Cout)
 
     def conv3x3_s2_x3_pack(self, weight: torch.Tensor):
         """Split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_s2_x3``; ``None`` when the shape is not built (Cin % 16, Cout a multiple of
         128 up to 1024)."""
-        w = weight.detach().to(self.device, torch.float32).contiguous()
-        Cout, Cin, kh, kw = w.shape
-        nb = int(self._L.vd3d_conv3x3_s2_x3_weight_bytes(Cin, Cout)) if (kh, kw) == (3, 3) else -1
-        if nb < 0:
-            return None
-        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._enter(w, img)
-        _lib.check(self._L.vd3d_conv3x3_s2_x3_pack_weights(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
-        return img
+        return self._conv3x3_pack("s2_x3", weight)
 
     def conv3x3_s2_x3(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
         """F.conv2d(x, W, None, stride 2, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_s2_x3_pack(W)``: bf16x3 MFMA
         arithmetic, float32 accumulation (include/vd3d.h vd3d_conv3x3_s2_x3); returns a channels_last [B, Cout, (H+1)//2, (W+1)//2] tensor."""
-        B, Cin, H, W = x.shape
-        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
-            raise AssertionError("conv3x3_s2_x3: float32 channels_last input")
-        out = torch.empty((B, int(Cout), (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        self._enter(x, w_image, out)
-        _lib.check(self._L.vd3d_conv3x3_s2_x3(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
-        return out
-
-    def _conv3x3_x2t_pack(self, st: str, weight: torch.Tensor):
-        w = weight.detach().to(self.device, torch.float32).contiguous()
-        Cout, Cin, kh, kw = w.shape
-        nb = int(getattr(self._L, f"vd3d_conv3x3_{st}_x2_weight_bytes")(Cin, Cout)) if (kh, kw) == (3, 3) else -1
-        if nb < 0:
-            return None
-        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._enter(w, img)
-        _lib.check(getattr(self._L, f"vd3d_conv3x3_{st}_x2_pack_weights")(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
-        return img
-
-    def _conv3x3_x2t(self, st: str, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
-        B, Cin, H, W = x.shape
-        if x.dtype != torch.float32 or not x.is_contiguous(memory_format=torch.channels_last):
-            raise AssertionError(f"conv3x3_{st}_x2: float32 channels_last input")
-        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if st == "s2" else (H, W)
-        out = torch.empty((B, int(Cout), Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        self._enter(x, w_image, out)
-        _lib.check(getattr(self._L, f"vd3d_conv3x3_{st}_x2")(self._ctx, _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), _ptr(out)))
-        return out
+        return self._conv3x3("s2_x3", x, w_image, Cout)
 
     def conv3x3_s1_x2_pack(self, weight: torch.Tensor):
         """Scale, split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_s1_x2``; ``None`` when the shape is not built (Cin % 16, Cout in
         {32, 64, 128, 256})."""
-        return self._conv3x3_x2t_pack("s1", weight)
+        return self._conv3x3_pack("s1_x2", weight)
 
     def conv3x3_s1_x2(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
         """F.conv2d(x, W, None, stride 1, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_s1_x2_pack(W)``: fp16x2 MFMA arithmetic
         (two fp16 terms per operand, three products per MAC, |x| < 65 504), float32 accumulation, on the 8 x 32 tile kernel that takes every map size
         (include/vd3d.h vd3d_conv3x3_s1_x2); returns a channels_last [B, Cout, H, W] tensor."""
-        return self._conv3x3_x2t("s1", x, w_image, Cout)
+        return self._conv3x3("s1_x2", x, w_image, Cout)
 
     def conv3x3_s2_x2_pack(self, weight: torch.Tensor):
         """Scale, split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_s2_x2``; ``None`` when the shape is not built (Cin % 16, Cout a
         multiple of 128 up to 1024)."""
-        return self._conv3x3_x2t_pack("s2", weight)
+        return self._conv3x3_pack("s2_x2", weight)
 
     def conv3x3_s2_x2(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int) -> torch.Tensor:
         """F.conv2d(x, W, None, stride 2, padding 1) for a float32 channels_last [B, Cin, H, W] tensor with W given as ``conv3x3_s2_x2_pack(W)``: fp16x2 MFMA
         arithmetic, float32 accumulation (include/vd3d.h vd3d_conv3x3_s2_x2); returns a channels_last [B, Cout, (H+1)//2, (W+1)//2] tensor."""
-        return self._conv3x3_x2t("s2", x, w_image, Cout)
+        return self._conv3x3("s2_x2", x, w_image, Cout)
 
     def conv_ifn_pack(self, kind: int, weight: torch.Tensor):
         """Split + pack a float32 weight for ``conv_ifn``: ``[Cout, Cin, 3, 3]`` for ``_abi.IFN_K3S1`` / ``IFN_K3S2``, ``[Cin, Cout, 4, 4]`` (ConvTranspose2d's layout) for
