@@ -38,7 +38,8 @@ extern "C" {
  *    the letterbox entry points (vd3d_letterbox_*, vd3d_canny_*, vd3d_depth_letterbox_fill_u8) with their two new structs, vd3d_conv3x3_s2_x3_weight_bytes,
  *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)), vd3d_depth_handoff_form, vd3d_depth_preprocess_form,
  *    vd3d_conv3x3_s1_x2_* and vd3d_conv3x3_s2_x2_* (weight_bytes, pack_weights and the convolution each: DepthPipe(conv="fp16x2")),
- *    vd3d_resize_pil_bicubic_u8, vd3d_depth_preprocess_pil (DepthPipe(front_end="pil")). */
+ *    vd3d_resize_pil_bicubic_u8, vd3d_depth_preprocess_pil (DepthPipe(front_end="pil")), vd3d_dpt_head_tail_act_f32 (the sigmoid tail of the metric
+ *    Depth-Anything heads under DepthPipe(self_contained=True)). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -661,11 +662,22 @@ int vd3d_upsample_bilinear_nhwc(vd3d_ctx* ctx, int dtype, const void* in, void* 
  *   vd3d_nhwc_bias_act_f32:  v = y [+ bias[c]] [+ r1]; [v = r2 + v]; [v = max(v, 0)] -> out (may alias y); [relu_out = max(v, 0)]
  *   vd3d_upsample_bilinear_bias_nhwc_f32:  vd3d_upsample_bilinear_nhwc + bias[c] on the interpolated value (up(conv + b) == up(conv) + b)
  *   vd3d_dpt_head_tail_f32:  out[p] = max(b3 + sum_c w3[c] * max(y[p][c] + b2[c], 0), 0) * scale -- conv2's bias, ReLU, the 1x1 conv3, its
- *                            bias, the final ReLU and max_depth of the head in one pass; C in {16, 32, 64} */
+ *                            bias, the final ReLU and max_depth of the head in one pass; C in {16, 32, 64}
+ *   vd3d_dpt_head_tail_act_f32:  the same pass with the head's last activation as an argument:
+ *                                  v = b3 + sum_c w3[c] * max(y[p][c] + b2[c], 0)
+ *                                  act VD3D_HEAD_ACT_RELU    (0): out[p] = max(v, 0) * scale    -- vd3d_dpt_head_tail_f32's function, the same bits
+ *                                  act VD3D_HEAD_ACT_SIGMOID (1): out[p] = sigmoid(v) * scale   -- the metric Depth-Anything heads (Sigmoid() * max_depth)
+ *                                v is formed exactly as vd3d_dpt_head_tail_f32 forms it (same lanes, same FMA chain, same butterfly).  sigmoid is
+ *                                torch.sigmoid on a float32 CPU tensor, 1 / (1 + Sleef_expf_u10(0 - v)) -- what vd3d_torch_math(op 1) returns; the sigmoid and
+ *                                the multiplication by scale are two float32 roundings, as in the module graph.
+ * Both tails: y, b2 and w3 16-byte aligned, C in {16, 32, 64} (else VD3D_E_UNSUPPORTED); n_pix >= 1 and, for the second, act in {0, 1} (else
+ * VD3D_E_INVALID).  A refused call launches nothing and leaves out as it was. */
+enum { VD3D_HEAD_ACT_RELU = 0, VD3D_HEAD_ACT_SIGMOID = 1 };
 int vd3d_nhwc_bias_act_f32(vd3d_ctx* ctx, const float* y, const float* bias_or_null, const float* r1_or_null, const float* r2_or_null, int relu,
                            int64_t n_pix, int C, float* out, float* relu_out_or_null);
 int vd3d_upsample_bilinear_bias_nhwc_f32(vd3d_ctx* ctx, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C);
 int vd3d_dpt_head_tail_f32(vd3d_ctx* ctx, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, float* out);
+int vd3d_dpt_head_tail_act_f32(vd3d_ctx* ctx, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, int act, float* out);
 
 /* The DPT head's 3 x 3 convolution with its up-sampling in front and, optionally, the tail behind, in one exact-float32 kernel (float32 operands on
  * v_mfma_f32_32x32x2_f32, float32 accumulation, one fixed K order -- 16-channel chunk, tap, channel -- no split-K, no atomics: identical from run to run):

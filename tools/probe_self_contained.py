@@ -1,4 +1,5 @@
-"""DepthPipe(self_contained=True) beside the library mode it leaves (gemm="bf16x3", conv="bf16x3", miopen_find=True), DA-V2-Base, 16 frames at 3840 x 2160:
+"""DepthPipe(self_contained=True) beside the library mode it leaves (the same gemm / conv pair with miopen_find=True), 16 frames at 3840 x 2160.  ``--model`` takes
+any name of depth.MODEL_ZOO (default depth-anything-v2-base; dpt-large and the metric Depth-Anything names included), ``--pair`` bf16x3 (default) or fp16x2:
 
   python tools/probe_self_contained.py --forward [--out FILE.md]     both pipes in one process, alternating windows (three windows of three forwards after
                                                                      warm-up, device events, spread stated), and a per-kernel-family breakdown of the mode
@@ -17,11 +18,11 @@ import sys  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from visiondepth3d_amd.depth import DepthPipe  # noqa: E402
+from visiondepth3d_amd.depth import MODEL_ZOO, DepthPipe  # noqa: E402
 from visiondepth3d_amd.render_3d import Renderer  # noqa: E402
 
 F = torch.nn.functional
-NAME, B, H, W = "depth-anything-v2-base", 16, 2160, 3840
+NAME, PAIR, B, H, W = "depth-anything-v2-base", "bf16x3", 16, 2160, 3840   # --model / --pair replace the first two
 MODES = {"library": dict(miopen_find=True), "self": dict(self_contained=True)}
 
 
@@ -41,7 +42,7 @@ def frames():
 
 
 def pipe(R, mode):
-    return DepthPipe(NAME, device="cuda", dtype=torch.float32, renderer=R, gemm="bf16x3", conv="bf16x3", **MODES[mode])
+    return DepthPipe(NAME, device="cuda", dtype=torch.float32, renderer=R, gemm=PAIR, conv=PAIR, seed=5 if NAME == "dpt-large" else 0, **MODES[mode])
 
 
 def probe_forward(R, say, windows=3, steps=3):
@@ -54,7 +55,7 @@ def probe_forward(R, say, windows=3, steps=3):
         for m, p in pipes.items():
             ms[m].append(bench(lambda: p.infer_bgr_u8(f, raw=True), steps))
     for m, v in ms.items():
-        say(f"- {NAME}, {B} frames at {W} x {H}, gemm=bf16x3, conv=bf16x3, {m}: median {statistics.median(v):.2f} ms per forward, windows "
+        say(f"- {NAME}, {B} frames at {W} x {H}, gemm={PAIR}, conv={PAIR}, {m}: median {statistics.median(v):.2f} ms per forward, windows "
             f"{', '.join(f'{t:.2f}' for t in v)} (spread {max(v) - min(v):.2f})")
     a, b = statistics.median(ms["self"]), statistics.median(ms["library"])
     say(f"- self-contained / library = {a / b:.4f} ({a - b:+.2f} ms)")
@@ -75,7 +76,7 @@ def probe_cold(R, say, mode):
     f = frames()
     p = pipe(R, mode)
     p.infer_bgr_u8(f, raw=True); torch.cuda.synchronize()
-    say(f"- cold start, {mode}: {time.perf_counter() - T0:.1f} s from process start to the end of the first forward ({NAME}, {B} frames at {W} x {H})")
+    say(f"- cold start, {mode}: {time.perf_counter() - T0:.1f} s from process start to the end of the first forward ({NAME}, gemm={PAIR}, conv={PAIR}, {B} frames at {W} x {H})")
 
 
 def probe_shapes(R, say):
@@ -94,12 +95,16 @@ def probe_shapes(R, say):
 
 
 def main():
+    global NAME, PAIR
     ap = argparse.ArgumentParser()
     ap.add_argument("--forward", action="store_true")
     ap.add_argument("--shapes", action="store_true")
     ap.add_argument("--cold", choices=list(MODES))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--model", default=NAME, choices=sorted(MODEL_ZOO))
+    ap.add_argument("--pair", default=PAIR, choices=["bf16x3", "fp16x2"])
     a = ap.parse_args()
+    NAME, PAIR = a.model, a.pair
 
     def say(s):
         print(s, flush=True)

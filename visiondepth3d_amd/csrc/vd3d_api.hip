@@ -1958,13 +1958,22 @@ VD3D_EXPORT int vd3d_upsample_bilinear_bias_nhwc_f32(vd3d_ctx* c, const float* i
   HIPCHK(hipGetLastError());
   return 0;
 }
-VD3D_EXPORT int vd3d_dpt_head_tail_f32(vd3d_ctx* c, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, float* out) {
+// one body for both entry points: the checks, in this order, are the same whatever the activation
+static int dpt_head_tail(vd3d_ctx* c, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, int act, float* out) {
   if (!c || !y || !b2 || !w3 || !out || n_pix < 1) return set_err(VD3D_E_INVALID, "bad argument");
+  if (act != VD3D_HEAD_ACT_RELU && act != VD3D_HEAD_ACT_SIGMOID) return set_err(VD3D_E_INVALID, "dpt_head_tail: unknown activation %d", act);
   HIPCHK(hipSetDevice(c->device));
-  if (!vd_launch_head_tail_f32(c->stream, y, b2, w3, b3, scale, (long long)n_pix, C, out))
-    return set_err(VD3D_E_UNSUPPORTED, "dpt_head_tail: C %d not in {16, 32, 64}", C);
+  if (!vd_launch_head_tail_f32(c->stream, y, b2, w3, b3, scale, (long long)n_pix, C, act, out))
+    return set_err(VD3D_E_UNSUPPORTED, "dpt_head_tail: C %d not in {16, 32, 64}, or y / b2 / w3 not 16-byte aligned", C);
   HIPCHK(hipGetLastError());
   return 0;
+}
+VD3D_EXPORT int vd3d_dpt_head_tail_f32(vd3d_ctx* c, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, float* out) {
+  return dpt_head_tail(c, y, b2, w3, b3, scale, n_pix, C, VD3D_HEAD_ACT_RELU, out);
+}
+VD3D_EXPORT int vd3d_dpt_head_tail_act_f32(vd3d_ctx* c, const float* y, const float* b2, const float* w3, float b3, float scale, int64_t n_pix, int C, int act,
+                                           float* out) {
+  return dpt_head_tail(c, y, b2, w3, b3, scale, n_pix, C, act, out);
 }
 VD3D_EXPORT int64_t vd3d_dpt_head_conv_weight_bytes(int Cin, int Cout) { return (int64_t)vd_dpt_head_conv_weight_bytes(Cin, Cout); }
 VD3D_EXPORT int vd3d_dpt_head_conv_pack_weights(vd3d_ctx* c, const float* W, int Cin, int Cout, void* image) {

@@ -293,7 +293,7 @@ bool vd_launch_upsample_bilinear_nhwc(hipStream_t s, int dtype, const void* in, 
 bool vd_launch_bias_act_f32(hipStream_t s, const float* y, const float* bias, const float* r1, const float* r2, int relu, long long n_pix, int C,
                             float* out, float* relu_out);
 bool vd_launch_upsample_bilinear_bias_nhwc_f32(hipStream_t s, const float* in, const float* bias, float* out, int B, int ih, int iw, int oh, int ow, int C);
-bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, const float* w3, float b3, float scale, long long n_pix, int C, float* out);
+bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, const float* w3, float b3, float scale, long long n_pix, int C, int act, float* out);   // act: VD3D_HEAD_ACT_*
 bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const float* bias, int B, int H, int W, int f, int C, float* out);
 bool vd_launch_patchify_f32(hipStream_t s, const float* x, int B, int th, int tw, int p, float* out);   // NHWC [B][th][tw][3] -> rows [B gh gw][3 p^2 up to 16]
 // ---- vd3d_handoff.hip

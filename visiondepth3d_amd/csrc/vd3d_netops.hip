@@ -279,9 +279,19 @@ bool vd_launch_upsample_bilinear_bias_nhwc_f32(hipStream_t s, const float* in, c
 }
 
 // k_head_tail: everything behind the head's second convolution -- its bias, ReLU, the 1x1 convolution to ONE channel (a C-term dot product per
-// pixel), its bias, ReLU and max_depth -- in one pass: reads the C-channel map once, writes one float per pixel (PyTorch: bias r+w, ReLU r+w,
-// MIOpen 1x1 r, bias, ReLU, scale).  LPP = C / 4 adjacent lanes share a pixel (coalesced 16-byte loads), partial dot products meet in a butterfly.
-template <int LPP>
+// pixel), its bias, the final activation and max_depth -- in one pass: reads the C-channel map once, writes one float per pixel (PyTorch: bias r+w, ReLU r+w,
+// MIOpen 1x1 r, bias, activation, scale).  LPP = C / 4 adjacent lanes share a pixel (coalesced 16-byte loads), partial dot products meet in a butterfly.
+// ACT (VD3D_HEAD_ACT_*) is the head's last activation: 0 = ReLU (the relative Depth-Anything heads, DPT), 1 = torch.sigmoid (the metric Depth-Anything heads:
+// vd_sigmoid_torch, the values torch's CPU kernel gives); the activation and the multiplication by scale are two float32 roundings, as in the module graph.
+// A template parameter: the ReLU instantiations hold no trace of the other branch.  NaN: fmaxf(NaN, 0) is 0, so the ReLU tail has always turned a NaN in y into
+// a finite value (both of its ReLUs do); the sigmoid tail keeps a NaN alive through the inner ReLU -- its pixel, and no other, comes out NaN, as torch's graph
+// gives it -- and is the same arithmetic, bit for bit, on every other input.
+template <int ACT>
+VD_DEV float head_tail_relu(float x) {
+  if constexpr (ACT == 1) return x != x ? x : fmaxf(x, 0.f);
+  else return fmaxf(x, 0.f);
+}
+template <int LPP, int ACT>
 __global__ __launch_bounds__(256) void k_head_tail(const float4* __restrict__ y, const float4* __restrict__ b2, const float4* __restrict__ w3, float b3,
                                                    float scale, long long n_pix, float* __restrict__ out) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -290,26 +300,36 @@ __global__ __launch_bounds__(256) void k_head_tail(const float4* __restrict__ y,
   float acc = 0.f;
   if (pix < n_pix) {
     const float4 v = y[idx], b = b2[l], w = w3[l];
-    acc = fmaxf(v.x + b.x, 0.f) * w.x;
-    acc = vd_fma(fmaxf(v.y + b.y, 0.f), w.y, acc);
-    acc = vd_fma(fmaxf(v.z + b.z, 0.f), w.z, acc);
-    acc = vd_fma(fmaxf(v.w + b.w, 0.f), w.w, acc);
+    acc = head_tail_relu<ACT>(v.x + b.x) * w.x;
+    acc = vd_fma(head_tail_relu<ACT>(v.y + b.y), w.y, acc);
+    acc = vd_fma(head_tail_relu<ACT>(v.z + b.z), w.z, acc);
+    acc = vd_fma(head_tail_relu<ACT>(v.w + b.w), w.w, acc);
   }
 #pragma unroll
   for (int off = LPP / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-  if (l == 0 && pix < n_pix) out[pix] = fmaxf(acc + b3, 0.f) * scale;
+  if (l == 0 && pix < n_pix) {
+    if constexpr (ACT == 1) out[pix] = vd_sigmoid_torch(acc + b3) * scale;
+    else out[pix] = fmaxf(acc + b3, 0.f) * scale;
+  }
 }
-bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, const float* w3, float b3, float scale, long long n_pix, int C, float* out) {
-  if (n_pix < 1) return false;
+template <int ACT>
+static bool launch_head_tail(hipStream_t s, const float4* yy, const float4* bb, const float4* ww, float b3, float scale, long long n_pix, int C, float* out) {
   const long long total = n_pix * (C / 4);
   const dim3 g((unsigned)((total + 255) / 256)), b(256);
-  const float4 *yy = (const float4*)y, *bb = (const float4*)b2, *ww = (const float4*)w3;
   switch (C) {
-    case 16: hipLaunchKernelGGL(k_head_tail<4>, g, b, 0, s, yy, bb, ww, b3, scale, n_pix, out); return true;
-    case 32: hipLaunchKernelGGL(k_head_tail<8>, g, b, 0, s, yy, bb, ww, b3, scale, n_pix, out); return true;
-    case 64: hipLaunchKernelGGL(k_head_tail<16>, g, b, 0, s, yy, bb, ww, b3, scale, n_pix, out); return true;
+    case 16: hipLaunchKernelGGL((k_head_tail<4, ACT>), g, b, 0, s, yy, bb, ww, b3, scale, n_pix, out); return true;
+    case 32: hipLaunchKernelGGL((k_head_tail<8, ACT>), g, b, 0, s, yy, bb, ww, b3, scale, n_pix, out); return true;
+    case 64: hipLaunchKernelGGL((k_head_tail<16, ACT>), g, b, 0, s, yy, bb, ww, b3, scale, n_pix, out); return true;
     default: return false;
   }
+}
+// act: 0 = ReLU, 1 = sigmoid (the caller has checked it).  false = nothing launched: C not in {16, 32, 64}, n_pix < 1, a grid past 2^31 - 1 workgroups, or
+// y / b2 / w3 not 16-byte aligned (the kernel reads them as float4) or out not 4-byte aligned.
+bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, const float* w3, float b3, float scale, long long n_pix, int C, int act, float* out) {
+  if (n_pix < 1 || (C != 16 && C != 32 && C != 64) || (n_pix * (C / 4) + 255) / 256 > 0x7fffffffLL) return false;
+  if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(b2) | reinterpret_cast<uintptr_t>(w3)) & 15) || (reinterpret_cast<uintptr_t>(out) & 3)) return false;
+  const float4 *yy = (const float4*)y, *bb = (const float4*)b2, *ww = (const float4*)w3;
+  return act == 1 ? launch_head_tail<1>(s, yy, bb, ww, b3, scale, n_pix, C, out) : launch_head_tail<0>(s, yy, bb, ww, b3, scale, n_pix, C, out);
 }
 
 // k_depth_to_space_bias: the scatter half of DPT's reassemble-stage ConvTranspose2d(C, C, kernel_size=s, stride=s) -- kernel == stride, so the layer is a GEMM

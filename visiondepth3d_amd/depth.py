@@ -42,6 +42,10 @@ MODEL_ZOO = {
     "depth-anything-v2-small": _DA_S, "depth-anything-v2-base": _DA_B, "depth-anything-v2-large": _DA_L,
     "depth-anything-v1-small": _DA_S, "depth-anything-v1-base": _DA_B, "depth-anything-v1-large": _DA_L,
     "distill-any-depth-small": _DA_S, "distill-any-depth-large": _DA_L,
+    # depth-anything/Depth-Anything-V2-Metric-{Indoor,Outdoor}-Large-hf: the same DINOv2-L network with depth_estimation_type="metric" -- the head ends in
+    # Sigmoid() * max_depth (metres: 20 indoor / Hypersim, 80 outdoor / Virtual KITTI 2) instead of ReLU() * max_depth
+    "depth-anything-v2-metric-indoor-large": dict(_DA_L, metric=True, max_depth=20),
+    "depth-anything-v2-metric-outdoor-large": dict(_DA_L, metric=True, max_depth=80),
     "dpt-large": dict(arch="dpt", hidden=1024, layers=24, heads=16, out_indices=[5, 11, 17, 23], neck=[256, 512, 1024, 1024], fusion=256),
 }
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
@@ -64,9 +68,10 @@ def build_config(name: str):
                          neck_hidden_sizes=z["neck"], fusion_hidden_size=z["fusion"], readout_type="project")
     bc = Dinov2Config(hidden_size=z["hidden"], num_hidden_layers=z["layers"], num_attention_heads=z["heads"], patch_size=14,
                       image_size=518, out_indices=z["out_indices"], reshape_hidden_states=False, apply_layernorm=True)
+    metric = dict(depth_estimation_type="metric", max_depth=int(z["max_depth"])) if z.get("metric") else {}   # (the config class takes an int there)
     return DepthAnythingConfig(backbone_config=bc, reassemble_hidden_size=z["hidden"], neck_hidden_sizes=z["neck"],
                                fusion_hidden_size=z["fusion"],
-                               head_hidden_size=z["head"], reassemble_factors=[4, 2, 1, 0.5], patch_size=14)
+                               head_hidden_size=z["head"], reassemble_factors=[4, 2, 1, 0.5], patch_size=14, **metric)
 
 
 @torch.no_grad()
@@ -265,8 +270,9 @@ class DepthPipe:
         first forward of a process, 4.5 % on the 4K float32 forward (profiles/r04_net_library_selection.md); opt-in, bench.py uses it.
         The flag is PyTorch's process-wide one: True / False set it, None (default) leaves it as the caller has it.
         ``self_contained``: ``False`` (default) -- everything above.  ``True`` -- OPT-IN, only with ``gemm="bf16x3"``, ``conv="bf16x3"`` or ``gemm="fp16x2"``, ``conv="fp16x2"``, float32, a renderer on a
-        GPU and ``fuse_backbone=True`` (else ValueError naming what is missing), and only for ``DepthAnythingForDepthEstimation`` on ``Dinov2Backbone`` (else
-        NotImplementedError naming the model): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
+        GPU and ``fuse_backbone=True`` (else ValueError naming what is missing), and only for the models of the split modes -- ``DepthAnythingForDepthEstimation`` on
+        ``Dinov2Backbone`` whose head ends in ReLU (relative) or Sigmoid (metric: Depth-Anything-V2-Metric-*), and DPT-Large as ``_split_scope`` accepts it
+        (else NotImplementedError naming the model, raised before the renderer or a device is touched): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
         as ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, the reassemble stage's 1 x 1 projections as ``vd3d_gemm_x3`` over the token rows, its transposed
         convolutions as ``vd3d_gemm_x3`` + ``vd3d_depth_to_space_bias_nhwc_f32``, its 3 x 3 stride-2 convolution on ``vd3d_conv3x3_s2_x3``, the fusion layers'
         1 x 1 projections as ``vd3d_gemm_x3`` over the pixel rows, and EVERY 3 x 3 stride-1 convolution on ``vd3d_conv3x3_x3`` (no size rule).  A module the
@@ -275,7 +281,11 @@ class DepthPipe:
         False.  Per output element every kernel sums in one fixed order and nothing is split along K, so a frame's prediction does not depend on the batch it
         is in or on the ROCm release's solution tables.  With the fp16x2 pair every route above takes that mode's kernels (``vd3d_gemm_x3`` and
         ``vd3d_attention_x3`` in mode fp16x2, ``vd3d_conv3x3_s2_x2``, ``vd3d_conv3x3_s1_x2``), the route labels read ``("fp16x2", "self-contained...")`` and
-        the mode's range contract holds in front of every one of them.  DPT-Large stays refused by name under the keyword."""
+        the mode's range contract holds in front of every one of them.  A metric head's ``Sigmoid() * max_depth`` runs inside the tail launch
+        (``vd3d_dpt_head_tail_act_f32``: torch.sigmoid's CPU values); without the keyword a metric model routes as it always did, its head the module graph.
+        DPT-Large under the keyword: its patch embedding (16 x 16, K = 768) takes the same patchify + GEMM route, the reassemble stage keeps the split modes'
+        readout / projection / transposed-convolution GEMMs and runs hook 3's 3 x 3 stride-2 convolution on the stride-2 tile convolution, and ``neck.convs``,
+        the fusion stage and the head's two 3 x 3 convolutions take the tile convolution at every map size (4 x 4 to 48 x 48 at 384 x 384)."""
         self.name, self.device, self.dtype = name, torch.device(device), dtype
         if gemm not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
@@ -316,15 +326,17 @@ class DepthPipe:
             synthetic_weights_(model, seed)
             processor = processor or PROCESSORS[MODEL_ZOO[name]["arch"]]
         self.arch = "da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "generic"
-        if self.self_contained and not (self.arch == "da" and type(model.backbone).__name__ == "Dinov2Backbone"):
-            bname = type(getattr(model, "backbone", None)).__name__ if getattr(model, "backbone", None) is not None else "its own encoder"
-            raise NotImplementedError(f"self_contained=True: {name!r} ({type(model).__name__} on {bname}) -- the mode is built for DepthAnythingForDepthEstimation "
-                                      "on Dinov2Backbone (Depth-Anything V1 / V2, Distill-Any-Depth) only; DPT-Large keeps the split modes without it")
-        if self.self_contained:
-            bc = model.config.backbone_config
-            if int(bc.hidden_size) not in (384, 768, 1024) or int(bc.hidden_size) != 64 * int(bc.num_attention_heads):
-                raise NotImplementedError(f"self_contained=True: {name!r}: hidden size {bc.hidden_size} with {bc.num_attention_heads} heads -- vd3d_attention_x3 and "
-                                          "vd3d_add_layernorm are built for 384 / 768 / 1024 with 64-wide heads; anything else would run library attention")
+        if self.self_contained:   # refused here, by name, on the module graph as it was handed in: no renderer call, nothing moved to a device yet
+            self.model = model
+            if self._split_scope(fuse_backbone) == "dinov2":
+                bc = model.config.backbone_config
+                if int(bc.hidden_size) not in (384, 768, 1024) or int(bc.hidden_size) != 64 * int(bc.num_attention_heads):
+                    raise NotImplementedError(f"self_contained=True: {name!r}: hidden size {bc.hidden_size} with {bc.num_attention_heads} heads -- vd3d_attention_x3 and "
+                                              "vd3d_add_layernorm are built for 384 / 768 / 1024 with 64-wide heads; anything else would run library attention")
+                act2 = getattr(model.head, "activation2", None)
+                if not isinstance(act2, (torch.nn.ReLU, torch.nn.Sigmoid)):
+                    raise NotImplementedError(f"self_contained=True: {name!r} ({type(model).__name__}): the depth head ends in {type(act2).__name__} -- the head tail "
+                                              "(vd3d_dpt_head_tail_f32 / vd3d_dpt_head_tail_act_f32) is built for ReLU (relative) and Sigmoid (metric) only")
         self.proc = dict(PROCESSORS["da"] if processor is None else processor)
         self.model = model.eval().to(self.device, dtype)
         if channels_last and self.device.type == "cuda":
@@ -338,6 +350,8 @@ class DepthPipe:
         self.dpt_vit = False
         if self.gemm != "f32" and self._split_scope(fuse_backbone) == "dpt-vit":
             self._rewrite_dpt_vit()
+            if self.self_contained:
+                self._patch_patch_embedding(self.model.dpt.embeddings.patch_embeddings)
         if dino:
             self._cache_position_embeddings()
             if fuse_backbone:
@@ -345,7 +359,7 @@ class DepthPipe:
             if self.renderer is not None:
                 self._patch_dpt_upsampling()
             if self.self_contained:
-                self._patch_patch_embedding()
+                self._patch_patch_embedding(self.model.backbone.embeddings.patch_embeddings)
 
     def _library_selection(self, tuned_gemm: bool, miopen_find):
         if miopen_find is not None:
@@ -567,11 +581,14 @@ class DepthPipe:
             return
         head = self.model.head
         tail_operands = None
-        if (f32 and isinstance(head.activation2, torch.nn.ReLU) and head.conv2.out_channels in (16, 32, 64) and head.conv3.kernel_size == (1, 1)
+        # the metric heads (Sigmoid() * max_depth) take the tail kernel under self_contained=True only: without the keyword they route as they always did
+        tail_act = "relu" if isinstance(head.activation2, torch.nn.ReLU) else "sigmoid" if sc and isinstance(head.activation2, torch.nn.Sigmoid) else None
+        if (f32 and tail_act is not None and head.conv2.out_channels in (16, 32, 64) and head.conv3.kernel_size == (1, 1)
                 and head.conv2.bias is not None and head.conv3.bias is not None and head.conv1.bias is not None):
             tail_operands = _head_tail_operands(head.conv3)
         if sc and tail_operands is None:
-            raise NotImplementedError("self_contained=True: a depth head other than [conv 3 x 3, up-sampling, conv 3 x 3 -> 16 / 32 / 64, ReLU, conv 1 x 1, ReLU] with biases -- not built")
+            raise NotImplementedError(f"self_contained=True: {self.name!r}: a depth head other than [conv 3 x 3, up-sampling, conv 3 x 3 -> 16 / 32 / 64, ReLU, conv 1 x 1, "
+                                      f"ReLU | Sigmoid] with biases (its last activation is {type(head.activation2).__name__}) -- not built")
 
         # float32 mode: up-sampling + conv2 + tail as ONE exact-float32 MFMA launch (vd3d_dpt_head_conv_f32); VD3D_HEAD_FUSED=0: A/B switch back to the three launches
         head_fused = self.gemm == "f32" and self.conv != "bf16x3" and self.device.type == "cuda"   # (the kernel reads device memory: a pipe on the CPU keeps its graph)
@@ -617,6 +634,8 @@ class DepthPipe:
                 if self._flop_count is not None:
                     self._flop_count[0] += 2.0 * y.numel() / y.shape[0]   # the 1x1 convolution to one channel inside the tail kernel
                 w3, b3 = tail_operands()
+                if tail_act == "sigmoid":   # vd3d_dpt_head_tail_act_f32
+                    return R.dpt_head_tail(y, head.conv2.bias, w3, b3, float(head.max_depth), act="sigmoid")
                 return R.dpt_head_tail(y, head.conv2.bias, w3, b3, float(head.max_depth))
             h = up(head.conv1(x), size)
             h = head.conv3(head.activation1(head.conv2(h)))
@@ -633,6 +652,42 @@ class DepthPipe:
             return out
         stage.forward = self._self_contained_reassemble(names) if sc else reassemble_fwd
 
+    def _self_contained_resize(self, rz, name):
+        """The resize module ``rz`` (``name``) of a reassemble layer under self_contained=True -> (kind, operand): ("ct", _ConvTransposeGemm) for a ConvTranspose2d with a
+        square kernel == stride, no padding and C_in % 16; ("s2", weight image) for a Conv2d 3 x 3 / stride 2 / padding 1 the stride-2 tile convolution of the mode
+        builds (C_in % 16, C_out % 128 up to 1024); ("identity", None).  Anything else is refused by name.  One rule for the DINOv2 stage and DPT's."""
+        R, gm = self.renderer, self.gemm
+        if isinstance(rz, torch.nn.ConvTranspose2d):
+            if not (rz.kernel_size == rz.stride and rz.kernel_size[0] == rz.kernel_size[1] and rz.padding == (0, 0) and rz.output_padding == (0, 0)
+                    and rz.dilation == (1, 1) and rz.groups == 1 and rz.in_channels % 16 == 0 and rz.out_channels % 4 == 0):
+                raise NotImplementedError(f"self_contained=True: {name}: a ConvTranspose2d with kernel {rz.kernel_size} / stride {rz.stride} / padding "
+                                          f"{rz.padding}, {rz.in_channels} -> {rz.out_channels} channels (built: square kernel == stride, no padding, C_in % 16) -- not built")
+            return "ct", _ConvTransposeGemm(R, rz, gm)
+        if isinstance(rz, torch.nn.Conv2d):
+            img = R.conv3x3_tile_pack(rz.weight, gm, 2) if _is_conv(rz, 3, 2, 1) else None
+            if img is None:
+                raise NotImplementedError(f"self_contained=True: {name}: a Conv2d with kernel {rz.kernel_size} / stride {rz.stride} / padding {rz.padding}, "
+                                          f"{rz.in_channels} -> {rz.out_channels} channels (built: 3 x 3 / stride 2 / padding 1, C_in % 16, C_out % 128 up to 1024) -- not built")
+            return "s2", img
+        if not isinstance(rz, torch.nn.Identity):
+            raise NotImplementedError(f"self_contained=True: {name} ({type(rz).__name__}) is no resize module the mode routes -- not built")
+        return "identity", None
+
+    def _self_contained_resize_run(self, kind, operand, rz, name, rows, B, gh, gw):
+        """Run what ``_self_contained_resize`` prepared on the projected token rows [B, gh gw, C] (NHWC storage of the B x gh x gw map) -> the channels_last
+        [B, C', h', w'] map, and record the route.  The caller counts the flops."""
+        R, gm = self.renderer, self.gemm
+        if kind == "ct":
+            self.conv_routes[name] = (gm, "self-contained: vd3d_gemm_x3 + vd3d_depth_to_space_bias_nhwc_f32")
+            return operand(rows, B, gh, gw)
+        x = rows.view(B, gh, gw, rows.shape[-1]).permute(0, 3, 1, 2)
+        if kind == "s2":
+            x = R.conv3x3_tile(x, operand, rz.out_channels, gm, 2)
+            if rz.bias is not None:
+                x = R.bias_act(x, rz.bias)
+            self.conv_routes[name] = (gm, "self-contained: vd3d_conv3x3_" + R.TILE_CONVS[gm, 2])
+        return x
+
     def _self_contained_reassemble(self, names):
         """The DINOv2 reassemble stage without a library call (self_contained=True): per hook, the tokens minus CLS are the rows of the 1 x 1 projection (linear_x3
         with its bias; [B, T-1, C_i] is NHWC storage); ConvTranspose2d (kernel == stride, no padding) is a _ConvTransposeGemm, as on DPT-Large's route
@@ -645,22 +700,8 @@ class DepthPipe:
             pm, rz = lay.projection, lay.resize
             if not _is_conv(pm, 1, 1, 0) or pm.in_channels % 16:
                 raise NotImplementedError(f"self_contained=True: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
-            hk = dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm), kind="identity", img=None)
-            if isinstance(rz, torch.nn.ConvTranspose2d):
-                if not (rz.kernel_size == rz.stride and rz.kernel_size[0] == rz.kernel_size[1] and rz.padding == (0, 0) and rz.output_padding == (0, 0)
-                        and rz.dilation == (1, 1) and rz.groups == 1 and rz.in_channels % 16 == 0 and rz.out_channels % 4 == 0):
-                    raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a ConvTranspose2d with kernel {rz.kernel_size} / stride {rz.stride} / padding "
-                                              f"{rz.padding}, {rz.in_channels} -> {rz.out_channels} channels (built: square kernel == stride, no padding, C_in % 16) -- not built")
-                hk["kind"], hk["img"] = "ct", _ConvTransposeGemm(R, rz, gm)
-            elif isinstance(rz, torch.nn.Conv2d):
-                img = R.conv3x3_tile_pack(rz.weight, gm, 2) if _is_conv(rz, 3, 2, 1) else None
-                if img is None:
-                    raise NotImplementedError(f"self_contained=True: {names[id(rz)]}: a Conv2d with kernel {rz.kernel_size} / stride {rz.stride} / padding {rz.padding}, "
-                                              f"{rz.in_channels} -> {rz.out_channels} channels (built: 3 x 3 / stride 2 / padding 1, C_in % 16, C_out % 128 up to 1024) -- not built")
-                hk["kind"], hk["img"] = "s2", img
-            elif not isinstance(rz, torch.nn.Identity):
-                raise NotImplementedError(f"self_contained=True: {names[id(rz)]} ({type(rz).__name__}) is no resize module the mode routes -- not built")
-            hooks.append(hk)
+            kind, img = self._self_contained_resize(rz, names[id(rz)])
+            hooks.append(dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm), kind=kind, img=img))
 
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
@@ -675,28 +716,20 @@ class DepthPipe:
                 n = pm.out_channels
                 x = R.linear_x3(hs[:, 1:].contiguous(), hk["proj"], n, pm.bias, mode=gm)         # [B, T-1, C_i]: NHWC storage
                 self.conv_routes[names[id(pm)]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
-                x = x.view(B, gh, gw, n).permute(0, 3, 1, 2)
-                self._count_conv(pm, x)   # the routed modules bypass the counting hooks: the figure equals the library mode's
-                if hk["kind"] == "ct":
-                    x = hk["img"](x.permute(0, 2, 3, 1), B, gh, gw)
-                    self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_gemm_x3 + vd3d_depth_to_space_bias_nhwc_f32")
-                    self._count_conv(rz, x)
-                elif hk["kind"] == "s2":
-                    x = R.conv3x3_tile(x, hk["img"], rz.out_channels, gm, 2)
-                    if rz.bias is not None:
-                        x = R.bias_act(x, rz.bias)
-                    self.conv_routes[names[id(rz)]] = (gm, "self-contained: vd3d_conv3x3_" + R.TILE_CONVS[gm, 2])
-                    self._count_conv(rz, x)
+                self._count_conv(pm, x.view(B, gh, gw, n).permute(0, 3, 1, 2))   # the routed modules bypass the counting hooks: the figure equals the library mode's
+                x = self._self_contained_resize_run(hk["kind"], hk["img"], rz, names[id(rz)], x, B, gh, gw)
+                if hk["kind"] != "identity":
+                    self._count_conv(rz, x)   # the hook's formula, as the library mode counts these modules
                 out.append(x)
             return out
         return reassemble_fwd
 
-    def _patch_patch_embedding(self):
-        """Self-contained: Dinov2PatchEmbeddings (Conv2d(3, C, kernel_size=p, stride=p)) as vd3d_patchify_f32 + vd3d_gemm_x3 on the weight reshaped to [C, 3 p^2] and
-        zero-padded to the GEMM's K unit (p = 14: 588 -> 592), with its bias: [B, T-1, C] directly.  CLS, the cached position embedding and the final LayerNorm
-        stay ATen element-wise / native kernels."""
+    def _patch_patch_embedding(self, pe):
+        """Self-contained: the patch-embedding module ``pe`` (Dinov2PatchEmbeddings, DPTViTPatchEmbeddings: ``projection`` = Conv2d(3, C, kernel_size=p, stride=p), whose
+        map the module flattens and transposes) as vd3d_patchify_f32 + vd3d_gemm_x3 on the weight reshaped to [C, 3 p^2] and zero-padded to the GEMM's K unit
+        (p = 14: 588 -> 592; p = 16: 768, no padding), with its bias: [B, T-1, C] directly.  CLS, the cached position embedding and the final LayerNorm stay ATen
+        element-wise / native kernels."""
         R = self.renderer
-        pe = self.model.backbone.embeddings.patch_embeddings
         m = pe.projection
         name = next(n for n, mod in self.model.named_modules() if mod is m)
         p = m.kernel_size[0]
@@ -720,14 +753,16 @@ class DepthPipe:
           * per hook, GELU(Linear_2C->C(cat(tokens, CLS))) as one linear_x3 with the GELU epilogue over the [B, T-1, 2C] rows, then the 1x1 projection
             (C -> C_i) as a linear_x3 with its bias on the same rows -- [B, T-1, C_i] is NHWC storage, handed on as a channels_last view;
           * resize: hooks 0 / 1 (ConvTranspose2d, kernel == stride s) as a linear_x3 with the weight permuted to [(i, j, co)][ci] + the scatter / bias
-            launch vd3d_depth_to_space_bias_nhwc_f32; hook 2 identity; hook 3 (3 x 3 stride 2) the library convolution;
+            launch vd3d_depth_to_space_bias_nhwc_f32; hook 2 identity; hook 3 (3 x 3 stride 2) the library convolution -- under self_contained=True the
+            stride-2 tile convolution of the mode + bias_act, by the rule of _self_contained_resize, and every module's route goes into conv_routes;
           * head: conv1 bias-free with its bias inside the align_corners up-sampling, conv2 bias-free (vd3d_conv3x3_x2 in fp16x2 where its size rule allows),
             vd3d_dpt_head_tail_f32 (scale 1) for the rest.
         neck.convs (3 x 3, no bias, C_i -> 256) and the fusion stage's 256 -> 256 convolutions have 256 output channels, which vd3d_conv3x3_x2 does not
         build: they stay library float32 convolutions, as for DA-V2-Large -- unless the pipe was built with conv="bf16x3", whose vd3d_conv3x3_x3 builds
         256 output channels and takes them and the head's two 3 x 3 convolutions (conv_nb / the neck.convs routing of _patch_dpt_upsampling)."""
-        R, gm, CL = self.renderer, self.gemm, torch.channels_last
+        R, gm, CL, sc = self.renderer, self.gemm, torch.channels_last, self.self_contained
         stage, head = self.model.neck.reassemble_stage, self.model.head
+        names = {id(m): n for n, m in self.model.named_modules()}
         hooks = []
         for i, lay in enumerate(stage.layers):
             rl, ract = stage.readout_projects[i][0], stage.readout_projects[i][1]
@@ -735,7 +770,9 @@ class DepthPipe:
             pw = lay.projection.weight
             hk = dict(readout=(R.gemm_x3_pack(rl.weight, gm), rl.out_features, rl.bias, gelu, ract),
                       proj=(R.gemm_x3_pack(pw.reshape(pw.shape[0], -1), gm), pw.shape[0], lay.projection.bias), resize=lay.resize,
-                      ct=_ConvTransposeGemm(R, lay.resize, gm) if isinstance(lay.resize, torch.nn.ConvTranspose2d) else None)
+                      ct=_ConvTransposeGemm(R, lay.resize, gm) if isinstance(lay.resize, torch.nn.ConvTranspose2d) and not sc else None)
+            if sc:   # no library call: the resize module by the rule of the DINOv2 stage (refused by name here, at construction, if it is not built)
+                hk["sc"], hk["pname"] = self._self_contained_resize(lay.resize, names[id(lay.resize)]), names[id(lay.projection)]
             hooks.append(hk)
 
         def count_rows(t, n):   # flops_per_frame: the 1x1 projections and transposed convolutions (EXECUTED: P x C_out x C_in) bypass the module hooks;
@@ -757,7 +794,16 @@ class DepthPipe:
                 img, n, bias = hk["proj"]
                 count_rows(x, n)
                 x = R.linear_x3(x, img, n, bias, mode=gm)                                                       # [B, T-1, C_i]
-                if hk["ct"] is not None:
+                if sc:
+                    kind, operand = hk["sc"]
+                    rz = hk["resize"]
+                    self.conv_routes[hk["pname"]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
+                    if kind == "ct":
+                        count_rows(x, operand.n)
+                    x = self._self_contained_resize_run(kind, operand, rz, names[id(rz)], x, B, gh, gw)
+                    if kind == "s2":
+                        self._count_conv(rz, x)   # what the module's hook adds without the keyword
+                elif hk["ct"] is not None:
                     count_rows(x, hk["ct"].n)
                     x = hk["ct"](x, B, gh, gw)
                 else:
@@ -903,17 +949,22 @@ class DepthPipe:
 
     def _split_scope(self, fuse_backbone: bool = True) -> str:
         """Which rewrite ``gemm="bf16x3" / "fp16x2"`` applies to this model: "dinov2" (DepthAnythingForDepthEstimation on Dinov2Backbone) or "dpt-vit"
-        (DPTForDepthEstimation on its plain ViT encoder with readout_type="project": DPT-Large).  Everything else raises NotImplementedError naming the model."""
-        m, what = self.model, f"{self.name!r} ({type(self.model).__name__})"
+        (DPTForDepthEstimation on its plain ViT encoder with readout_type="project": DPT-Large).  Everything else raises NotImplementedError naming the model.
+        ``self_contained=True`` covers exactly the models of the split modes, so the constructor asks here too; the refusal then names the keyword.  Reads the
+        module graph and its configuration only."""
+        m, what = self.model, f"{self.name!r} ({type(self.model).__name__}"
+        bb = getattr(m, "backbone", None)
+        what += f" on {type(bb).__name__})" if self.arch == "da" and bb is not None else ")"
+        tag = "self_contained=True" if self.self_contained else f"gemm={self.gemm!r}"
         if self.arch == "da" and type(m.backbone).__name__ == "Dinov2Backbone" and fuse_backbone:
             return "dinov2"
         if type(m).__name__ != "DPTForDepthEstimation" or not fuse_backbone:
-            raise NotImplementedError(f"gemm={self.gemm!r}: {what} -- the split modes rewrite the fused DINOv2 backbone (Depth-Anything V1 / V2, Distill-Any-Depth) and the "
+            raise NotImplementedError(f"{tag}: {what} -- the split modes rewrite the fused DINOv2 backbone (Depth-Anything V1 / V2, Distill-Any-Depth) and the "
                                       "plain-ViT DPT (DPT-Large), with fuse_backbone=True; this model runs its stock float32 graph -- nothing is substituted silently")
         cfg = m.config
 
         def refuse(why):
-            raise NotImplementedError(f"gemm={self.gemm!r}: {what}: {why} -- not built in the split modes; gemm='f32' runs the stock float32 graph")
+            raise NotImplementedError(f"{tag}: {what}: {why} -- not built in the split modes; gemm='f32' runs the stock float32 graph")
         if cfg.is_hybrid:
             refuse("DPT-Hybrid (MiDaS 3.0 hybrid, Intel/dpt-hybrid-midas: BiT stem, identity readout on hooks 0 / 1)")
         if getattr(m, "backbone", None) is not None or cfg.backbone_config is not None:

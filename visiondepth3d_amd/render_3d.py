@@ -1131,13 +1131,20 @@ class Renderer:
         _lib.check(self._L.vd3d_upsample_bilinear_bias_nhwc_f32(self._ctx, _ptr(x), _ptr(bias), _ptr(out), B, ih, iw, oh, ow, Cc))
         return out
 
-    def dpt_head_tail(self, y, b2, w3, b3: float, scale: float):
-        """[B,C,h,w] (conv2 WITHOUT its bias) -> [B,h,w]: relu(b3 + sum_c w3[c] relu(y + b2[c])) * scale."""
+    def dpt_head_tail(self, y, b2, w3, b3: float, scale: float, act: str = "relu"):
+        """[B,C,h,w] (conv2 WITHOUT its bias) -> [B,h,w]: act(b3 + sum_c w3[c] relu(y + b2[c])) * scale.  ``act``: ``"relu"`` (default;
+        vd3d_dpt_head_tail_f32) or ``"sigmoid"`` (the metric Depth-Anything heads; vd3d_dpt_head_tail_act_f32, torch.sigmoid's CPU values)."""
+        if act not in ("relu", "sigmoid"):
+            raise ValueError("dpt_head_tail: act must be 'relu' or 'sigmoid'")
         self._nhwc_f32(y)
         B, Cc, h, w = y.shape
         out = torch.empty((B, h, w), dtype=torch.float32, device=y.device)
         self._enter(y, b2, w3, out)
-        _lib.check(self._L.vd3d_dpt_head_tail_f32(self._ctx, _ptr(y), _ptr(b2), _ptr(w3), float(b3), float(scale), B * h * w, Cc, _ptr(out)))
+        if act == "relu":
+            _lib.check(self._L.vd3d_dpt_head_tail_f32(self._ctx, _ptr(y), _ptr(b2), _ptr(w3), float(b3), float(scale), B * h * w, Cc, _ptr(out)))
+        else:
+            _lib.check(self._L.vd3d_dpt_head_tail_act_f32(self._ctx, _ptr(y), _ptr(b2), _ptr(w3), float(b3), float(scale), B * h * w, Cc,
+                                                          _abi.HEAD_ACT_SIGMOID, _ptr(out)))
         return out
 
     def dpt_head_conv_pack(self, weight: torch.Tensor):
