@@ -252,7 +252,7 @@ def test_conv3x3_head_vs_float32_reference(R, H, W, act):
 
 
 @pytest.mark.parametrize("r", [4, 2])
-@pytest.mark.parametrize("H,W", [(3, 5), (64, 64), (70, 100), (135, 241)])
+@pytest.mark.parametrize("H,W", [(3, 5), (64, 64), (70, 100), (135, 241), (1, 1), (2, 63), (1, 64), (1, 65)])
 def test_esr_tail_equals_pixel_shuffle_plus_nearest_add(R, H, W, r):
     """vd3d_esr_tail_f32 == float(pixel_shuffle(t[:, :3 r^2], r) + interpolate(x, nearest)) bit for bit (fp16 addition like the network's)."""
     import torch.nn.functional as F
