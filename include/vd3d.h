@@ -39,7 +39,8 @@ extern "C" {
  *    vd3d_conv3x3_s2_x3_pack_weights, vd3d_conv3x3_s2_x3, vd3d_patchify_f32 (DepthPipe(self_contained=True)), vd3d_depth_handoff_form, vd3d_depth_preprocess_form,
  *    vd3d_conv3x3_s1_x2_* and vd3d_conv3x3_s2_x2_* (weight_bytes, pack_weights and the convolution each: DepthPipe(conv="fp16x2")),
  *    vd3d_resize_pil_bicubic_u8, vd3d_depth_preprocess_pil (DepthPipe(front_end="pil")), vd3d_dpt_head_tail_act_f32 (the sigmoid tail of the metric
- *    Depth-Anything heads under DepthPipe(self_contained=True)). */
+ *    Depth-Anything heads under DepthPipe(self_contained=True)), vd3d_im2col_nhwc_f32, vd3d_maxpool3x3_s2_nhwc_f32, vd3d_groupnorm_nhwc_f32_workspace_bytes and
+ *    vd3d_groupnorm_nhwc_f32: the BiT prefix of DPT-Hybrid under DepthPipe(self_contained=True). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -708,6 +709,37 @@ int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* ctx, const float* y, const float
  * the columns from 3 p^2 on are written as zeros.  vd3d_gemm_x3 on the weight [C][3 p^2] zero-padded to Kp, with the bias, then gives the patch tokens
  * [B][gh * gw][C].  1 <= p <= 64, th, tw >= p, B >= 1, rows 16-byte aligned (x 4-byte), else VD3D_E_UNSUPPORTED and nothing is launched. */
 int vd3d_patchify_f32(vd3d_ctx* ctx, const float* x, int B, int th, int tw, int p, float* rows);
+
+/* ---- The BiT ResNet prefix of DPT-Hybrid (MiDaS 3.0; BitEmbeddings + three BitStages of BitBottleneckLayer) under DepthPipe(self_contained=True): its matrix
+ * work runs on vd3d_gemm_x3 and the stride-1 tile convolutions; these entry points are everything else.  Activations are float32 NHWC rows [B * H * W][C].
+ *
+ * The gather half of a k x k convolution run as a GEMM: x [B][H][W][C] -> rows [B * Ho * Wo][Kp], Ho = (H + pad_top + pad_bottom - k) / stride + 1 (Wo alike),
+ * Kp = k k C rounded up to a multiple of 16,
+ *   rows[(b * Ho + oy) * Wo + ox][(ky * k + kx) * C + c] = x[b][oy * stride - pad_top + ky][ox * stride - pad_left + kx][c], zero outside the map
+ * (exact copies: the weight [Cout][C][k][k] permuted to [Cout][k][k][C]); the columns from k k C on are written as zeros.  The four paddings are given apart
+ * because TensorFlow's "same" padding is asymmetric (2 / 3 for 7 x 7 stride 2 on an even side, 0 / 1 for 3 x 3 stride 2).  k in {1, 3, 7}, stride 1 | 2, every
+ * padding 0 .. k - 1, at least one output pixel, rows 16-byte aligned, x 4-byte (16-byte where C % 4 == 0: 16-byte loads), else VD3D_E_UNSUPPORTED. */
+int vd3d_im2col_nhwc_f32(vd3d_ctx* ctx, const float* x, int B, int H, int W, int C, int k, int stride, int pad_top, int pad_bottom, int pad_left, int pad_right,
+                         float* rows);
+
+/* 3 x 3 / stride 2 max-pool of x [B][H][W][C] padded by pad_value on the four sides (0 .. 2 each): out [B][Ho][Wo][C], Ho = (H + pad_top + pad_bottom - 3) / 2 + 1.
+ * torch.nn.functional.max_pool2d(F.pad(x, ..., value=pad_value), 3, 2): a NaN in a window is that window's result.  C a multiple of 4, x / out 16-byte aligned,
+ * at least one output pixel, else VD3D_E_UNSUPPORTED. */
+int vd3d_maxpool3x3_s2_nhwc_f32(vd3d_ctx* ctx, const float* x, int B, int H, int W, int C, int pad_top, int pad_bottom, int pad_left, int pad_right,
+                                float pad_value, float* out);
+
+/* GroupNorm over x [B][P][C] (P = H W pixels) in G groups of C / G neighbouring channels, with an optional residual and ReLU behind it:
+ *   out = [max(., 0)]( (x - mean) * (rstd * gamma[c]) + beta[c] [+ residual] ),  mean and the BIASED variance per (frame, group), rstd = 1 / sqrt(var + eps).
+ * Two passes over the data for the statistics -- the mean first, then the sum of (x - mean)^2, never E[x^2] - mean^2 -- and one to apply: three launches, no
+ * atomics, every sum in ONE fixed order that depends on (P, C, C / G) alone (csrc/vd3d_bit.hip states it; tests/test_hip_bit_stem.py restates it in NumPy):
+ * a frame's result does not depend on its batch and repeats bit for bit.  flags: VD3D_GN_RELU.  out may be x or residual.  workspace: at least
+ * vd3d_groupnorm_nhwc_f32_workspace_bytes(B, P, C, G) bytes of device memory (host-only; < 0: shape not built), contents irrelevant.
+ * Built: C in {64, 128, 256, 512, 1024} with C / G in {2, 4, 8, 16, 32}; 1 <= B <= 65 535; P <= 2^24; every pointer 16-byte aligned.  Anything else is
+ * VD3D_E_UNSUPPORTED and nothing is launched. */
+enum { VD3D_GN_RELU = 1 };
+int64_t vd3d_groupnorm_nhwc_f32_workspace_bytes(int B, int64_t P, int C, int G);
+int vd3d_groupnorm_nhwc_f32(vd3d_ctx* ctx, const float* x, const float* residual_or_null, const float* gamma, const float* beta, float eps, int flags, int B,
+                            int64_t P, int C, int G, void* workspace, int64_t workspace_bytes, float* out);
 
 /* ---- preview visualisers: generate_preview_image, core/preview_utils.py:23-84, the exactly defined types.
  * left / right: uint8 BGR [h][w][3] eyes (outputs of vd3d_pixel_shift).  out: [h][w][3], except HSBS: [h][2*(w/2)][3].

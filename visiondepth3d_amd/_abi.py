@@ -19,6 +19,7 @@ DT_BF16, DT_F32, DT_F16 = range(3)   # vd3d_dtype (DT_F16: vd3d_esr_preprocess o
 E_INVALID, E_HIP, E_NOMEM, E_UNSUPPORTED = -1, -2, -3, -4
 IFN_K3S1, IFN_K3S2, IFN_T4S2 = range(3)   # the `kind` of vd3d_conv_ifn: 3 x 3 stride 1, 3 x 3 stride 2, transposed 4 x 4 stride 2
 HEAD_ACT_RELU, HEAD_ACT_SIGMOID = range(2)   # the `act` of vd3d_dpt_head_tail_act_f32 (VD3D_HEAD_ACT_*): the depth head's last activation
+GN_RELU = 1   # the `flags` of vd3d_groupnorm_nhwc_f32 (VD3D_GN_RELU): ReLU behind the normalisation (and the residual)
 
 
 class ShiftParams(C.Structure):

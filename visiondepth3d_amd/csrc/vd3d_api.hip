@@ -2021,6 +2021,40 @@ VD3D_EXPORT int vd3d_patchify_f32(vd3d_ctx* c, const float* x, int B, int th, in
   HIPCHK(hipGetLastError());
   return 0;
 }
+VD3D_EXPORT int vd3d_im2col_nhwc_f32(vd3d_ctx* c, const float* x, int B, int H, int W, int C, int k, int stride, int pt, int pb, int pl, int pr, float* rows) {
+  if (!c || !x || !rows) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_im2col_nhwc_f32(c->stream, x, B, H, W, C, k, stride, pt, pb, pl, pr, rows))
+    return set_err(VD3D_E_UNSUPPORTED, "im2col: not built: batch %d, map %d x %d x %d, kernel %d (1 | 3 | 7), stride %d (1 | 2), padding %d / %d / %d / %d (0 .. k - 1 each, "
+                   "at least one output pixel), or the rows not 16-byte aligned (x 16-byte where C %% 4 == 0, else 4-byte), or too many rows for one grid",
+                   B, H, W, C, k, stride, pt, pb, pl, pr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_maxpool3x3_s2_nhwc_f32(vd3d_ctx* c, const float* x, int B, int H, int W, int C, int pt, int pb, int pl, int pr, float pad, float* out) {
+  if (!c || !x || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_maxpool3x3_s2_nhwc_f32(c->stream, x, B, H, W, C, pt, pb, pl, pr, pad, out))
+    return set_err(VD3D_E_UNSUPPORTED, "maxpool3x3_s2: not built: batch %d, map %d x %d x %d (C a multiple of 4), padding %d / %d / %d / %d (0 .. 2 each, at least one "
+                   "output pixel), or x / out not 16-byte aligned, or a map too large for one grid", B, H, W, C, pt, pb, pl, pr);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int64_t vd3d_groupnorm_nhwc_f32_workspace_bytes(int B, int64_t P, int C, int G) { return (int64_t)vd_groupnorm_workspace_bytes(B, (long long)P, C, G); }
+VD3D_EXPORT int vd3d_groupnorm_nhwc_f32(vd3d_ctx* c, const float* x, const float* res, const float* gamma, const float* beta, float eps, int flags, int B, int64_t P,
+                                        int C, int G, void* ws, int64_t ws_bytes, float* out) {
+  if (!c || !x || !gamma || !beta || !ws || !out || (flags & ~VD3D_GN_RELU)) return set_err(VD3D_E_INVALID, "bad argument");
+  const long long need = vd_groupnorm_workspace_bytes(B, (long long)P, C, G);
+  if (need < 0)
+    return set_err(VD3D_E_UNSUPPORTED, "groupnorm: shape not built: %d channels in %d groups, batch %d, %lld pixels (built: C in {64, 128, 256, 512, 1024} with C / G in "
+                   "{2, 4, 8, 16, 32}, batch 1 .. 65535, up to 2^24 pixels)", C, G, B, (long long)P);
+  if (ws_bytes < need) return set_err(VD3D_E_INVALID, "groupnorm: the workspace holds %lld bytes, %lld needed", (long long)ws_bytes, need);
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_groupnorm_nhwc_f32(c->stream, x, res, gamma, beta, eps, flags & VD3D_GN_RELU, B, (long long)P, C, G, ws, out))
+    return set_err(VD3D_E_UNSUPPORTED, "groupnorm: x, the residual, gamma, beta, the workspace and out must be 16-byte aligned");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 VD3D_EXPORT int vd3d_preview_image(vd3d_ctx* c, int type, const uint8_t* left_bgr, const uint8_t* right_bgr, int h, int w, uint8_t* out_bgr) {
   if (!c || !left_bgr || !right_bgr || !out_bgr || h < 1 || w < 1) return set_err(VD3D_E_INVALID, "bad argument");

@@ -296,6 +296,12 @@ bool vd_launch_upsample_bilinear_bias_nhwc_f32(hipStream_t s, const float* in, c
 bool vd_launch_head_tail_f32(hipStream_t s, const float* y, const float* b2, const float* w3, float b3, float scale, long long n_pix, int C, int act, float* out);   // act: VD3D_HEAD_ACT_*
 bool vd_launch_depth_to_space_bias_f32(hipStream_t s, const float* y, const float* bias, int B, int H, int W, int f, int C, float* out);
 bool vd_launch_patchify_f32(hipStream_t s, const float* x, int B, int th, int tw, int p, float* out);   // NHWC [B][th][tw][3] -> rows [B gh gw][3 p^2 up to 16]
+// ---- vd3d_bit.hip: the BiT ResNet prefix of DPT-Hybrid between its GEMMs / tile convolutions (float32 NHWC rows)
+bool vd_launch_im2col_nhwc_f32(hipStream_t s, const float* x, int B, int H, int W, int C, int k, int stride, int pt, int pb, int pl, int pr, float* rows);
+bool vd_launch_maxpool3x3_s2_nhwc_f32(hipStream_t s, const float* x, int B, int H, int W, int C, int pt, int pb, int pl, int pr, float pad, float* out);
+long long vd_groupnorm_workspace_bytes(int B, long long P, int C, int G);   // < 0: shape not built
+bool vd_launch_groupnorm_nhwc_f32(hipStream_t s, const float* x, const float* res, const float* gamma, const float* beta, float eps, int relu, int B, long long P, int C,
+                                  int G, void* ws, float* out);
 // ---- vd3d_handoff.hip
 // form: 0 = the library's choice (the separable kernel for up-scaling), 1 = the general kernel, 2 = the separable kernel (false where it does not apply)
 bool vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,

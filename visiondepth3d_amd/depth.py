@@ -47,6 +47,9 @@ MODEL_ZOO = {
     "depth-anything-v2-metric-indoor-large": dict(_DA_L, metric=True, max_depth=20),
     "depth-anything-v2-metric-outdoor-large": dict(_DA_L, metric=True, max_depth=80),
     "dpt-large": dict(arch="dpt", hidden=1024, layers=24, heads=16, out_indices=[5, 11, 17, 23], neck=[256, 512, 1024, 1024], fusion=256),
+    # Intel/dpt-hybrid-midas ("MiDaS 3.0"): ViT-B/16 behind a BiT ResNet-50 prefix (stages 1 - 3, weight-standardised convolutions, GroupNorm(32)); hooks 0 / 1 are the
+    # prefix's stage-1 / stage-2 maps and go to the neck as they are (neck_ignore_stages), hooks 2 / 3 are ViT layers 8 / 11 through the "project" readout
+    "dpt-hybrid-midas": dict(arch="dpt", hybrid=True, hidden=768, layers=12, heads=12, out_indices=[2, 5, 8, 11], neck=[256, 512, 768, 768], fusion=256),
 }
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -63,6 +66,12 @@ def build_config(name: str):
     z = MODEL_ZOO[name]
     if z["arch"] == "dpt":
         from transformers import DPTConfig
+        if z.get("hybrid"):   # the published config.json of Intel/dpt-hybrid-midas
+            return DPTConfig(is_hybrid=True, hidden_size=z["hidden"], num_hidden_layers=z["layers"], num_attention_heads=z["heads"], intermediate_size=4 * z["hidden"],
+                             image_size=384, patch_size=16, backbone_out_indices=z["out_indices"], neck_hidden_sizes=z["neck"], neck_ignore_stages=[0, 1],
+                             reassemble_factors=[1, 1, 1, 0.5], fusion_hidden_size=z["fusion"], readout_type="project", backbone_featmap_shape=[1, 1024, 24, 24],
+                             backbone_config=dict(model_type="bit", layer_type="bottleneck", depths=[3, 4, 9], out_features=["stage1", "stage2", "stage3"],
+                                                  global_padding="same", embedding_dynamic_padding=True, num_groups=32))
         return DPTConfig(hidden_size=z["hidden"], num_hidden_layers=z["layers"], num_attention_heads=z["heads"],
                          intermediate_size=4 * z["hidden"], image_size=384, patch_size=16, backbone_out_indices=z["out_indices"],
                          neck_hidden_sizes=z["neck"], fusion_hidden_size=z["fusion"], readout_type="project")
@@ -155,6 +164,164 @@ def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     return F.pad(w.detach().reshape(C, k), (0, (k + 15) // 16 * 16 - k)).contiguous()
 
 
+def im2col_gemm_weight(w: torch.Tensor) -> torch.Tensor:
+    """Convolution weight [C_out, C_in, k, k] -> the GEMM weight [C_out, Kp] whose columns are in vd3d_im2col_nhwc_f32's order, (ky, kx, c_in): a permute to
+    [C_out, k, k, C_in], flattened, zero-padded from k k C_in to the next multiple of 16 (the 7 x 7 stem on 3 channels: 147 -> 160)."""
+    Cout, kk = w.shape[0], w[0].numel()
+    return F.pad(w.detach().permute(0, 2, 3, 1).reshape(Cout, kk), (0, (kk + 15) // 16 * 16 - kk)).contiguous()
+
+
+def same_padding(size: int, k: int, stride: int):
+    """TensorFlow "same" padding of one axis as transformers' DynamicPad2d computes it (dilation 1) -> (low, high): 384 / 7 / 2 -> (2, 3); 96 / 3 / 2 -> (0, 1)."""
+    total = max((-(-size // stride) - 1) * stride + k - size, 0)
+    return total // 2, total - total // 2
+
+
+def bit_standardized_weight(m) -> torch.Tensor:
+    """The weight a WeightStandardizedConv2d convolves with, by the module's own expression (it recomputes this on every forward), in float32 on the CPU --
+    the values the CPU module computes, whatever device the module is on.  Folded once, before packing, by DepthPipe(self_contained=True)."""
+    w = m.weight.detach().to("cpu", torch.float32)
+    return F.batch_norm(w.reshape(1, m.out_channels, -1), None, None, training=True, momentum=0.0, eps=m.eps).reshape_as(w)
+
+
+def _bit_conv_kind(m, name: str, stem: bool = False) -> str:
+    """How self_contained=True routes the convolution ``m`` of a BiT prefix: "gemm" (1 x 1 / stride 1: vd3d_gemm_x3 over the pixel rows), "tile" (3 x 3 / stride 1 /
+    padding 1: the tile convolution of the mode) or "im2col" (stride 2 with dynamic "same" padding -- the 7 x 7 stem, 3 x 3, 1 x 1: vd3d_im2col_nhwc_f32 +
+    vd3d_gemm_x3).  Anything else is refused by name.  Reads the module only."""
+    tag = f"self_contained=True: {name}"
+    if type(m).__name__ != "WeightStandardizedConv2d":
+        raise NotImplementedError(f"{tag} ({type(m).__name__}) is no weight-standardised convolution -- not built")
+    if m.bias is not None:
+        raise NotImplementedError(f"{tag} has a bias (BiT's convolutions have none) -- not built")
+    k, s, dyn = m.kernel_size, m.stride, m.pad is not None
+    if m.groups == 1 and m.dilation == (1, 1):
+        cin16 = m.in_channels % 16 == 0
+        if k == (1, 1) and s == (1, 1) and m.padding == (0, 0) and not dyn and cin16:
+            return "gemm"
+        if k == (3, 3) and s == (1, 1) and m.padding == (1, 1) and not dyn and cin16 and m.out_channels in (32, 64, 128, 256):
+            return "tile"
+        if s == (2, 2) and m.padding == (0, 0) and dyn and ((k in ((1, 1), (3, 3)) and cin16) or (stem and k == (7, 7) and m.in_channels == 3)):
+            return "im2col"
+    raise NotImplementedError(f"{tag}: kernel {k} / stride {s} / padding {m.padding}{' + dynamic same-padding' if dyn else ''} / dilation {m.dilation} / groups "
+                              f"{m.groups}, {m.in_channels} -> {m.out_channels} channels (built: 1 x 1 and 3 x 3 -> 32 / 64 / 128 / 256 at stride 1, 1 x 1 and 3 x 3 at "
+                              "stride 2 with 'same' padding, C_in % 16; the 7 x 7 stride-2 stem on 3 channels) -- not built")
+
+
+def _bit_norm_relu(n, name: str) -> bool:
+    """The BitGroupNormActivation ``n`` as vd3d_groupnorm_nhwc_f32 runs it -> whether a ReLU follows; anything the kernel does not build is refused by name."""
+    if (type(n).__name__ != "BitGroupNormActivation" or n.num_groups != 32 or not n.affine or n.num_channels not in (64, 128, 256, 512, 1024)
+            or not isinstance(n.activation, (torch.nn.ReLU, torch.nn.Identity))):
+        raise NotImplementedError(f"self_contained=True: {name} ({type(n).__name__}, {getattr(n, 'num_channels', '?')} channels in {getattr(n, 'num_groups', '?')} groups, "
+                                  f"activation {type(getattr(n, 'activation', None)).__name__}) -- built: GroupNorm(32) with an affine on 64 / 128 / 256 / 512 / 1024 "
+                                  "channels, followed by ReLU or nothing")
+    return isinstance(n.activation, torch.nn.ReLU)
+
+
+def bit_prefix_plan(backbone, names: dict) -> dict:
+    """What self_contained=True runs for the BitBackbone ``backbone`` of a DPT-Hybrid (``names``: id(module) -> name): per convolution its route, per
+    normalisation whether a ReLU follows -- or NotImplementedError naming the first module the mode does not build (a bias, a pre-activation layer, groups != 32,
+    global_padding other than "same", ...).  Reads the module graph and its configuration only: no device, no renderer."""
+    cfg, top = backbone.config, names[id(backbone)]
+    for what, ok in ((f"global_padding={cfg.global_padding!r} (built: 'same')", str(cfg.global_padding or "").lower() == "same"),
+                     (f"layer_type={cfg.layer_type!r} (built: 'bottleneck')", cfg.layer_type == "bottleneck"),
+                     (f"num_groups={cfg.num_groups} (built: 32)", int(cfg.num_groups) == 32)):
+        if not ok:
+            raise NotImplementedError(f"self_contained=True: {top}: a BiT backbone with {what} -- not built")
+    emb, pool = backbone.bit.embedder, backbone.bit.embedder.pooler
+    if not (type(pool).__name__ == "BitMaxPool2d" and tuple(pool.kernel_size) == (3, 3) and tuple(pool.stride) == (2, 2) and tuple(pool.padding) == (0, 0)
+            and tuple(pool.dilation) == (1, 1) and not pool.ceil_mode and type(pool.pad).__name__ == "DynamicPad2d" and isinstance(emb.pad, torch.nn.Identity)):
+        raise NotImplementedError(f"self_contained=True: {names[id(pool)]}: a stem pool other than 3 x 3 / stride 2 with dynamic 'same' padding and no ConstantPad2d "
+                                  "in front of the norm (embedding_dynamic_padding=True, global_padding='same') -- not built")
+    plan = {"conv": {}, "relu": {}, "layers": []}
+
+    def conv(m, stem=False):
+        plan["conv"][id(m)] = _bit_conv_kind(m, names[id(m)], stem)
+
+    def norm(n, want_relu):
+        plan["relu"][id(n)] = _bit_norm_relu(n, names[id(n)])
+        if plan["relu"][id(n)] != want_relu:
+            raise NotImplementedError(f"self_contained=True: {names[id(n)]}: {'a' if want_relu else 'no'} ReLU expected behind this normalisation -- not built")
+    conv(emb.convolution, stem=True)
+    norm(emb.norm, True)
+    for stage in backbone.bit.encoder.stages:
+        for lay in stage.layers:
+            if type(lay).__name__ != "BitBottleneckLayer" or not isinstance(lay.activation, torch.nn.ReLU):
+                raise NotImplementedError(f"self_contained=True: {names[id(lay)]} ({type(lay).__name__}) is no post-activation bottleneck ending in ReLU -- not built")
+            if lay.downsample is not None:
+                conv(lay.downsample.conv)
+                norm(lay.downsample.norm, False)
+            for c, n, r in ((lay.conv1, lay.norm1, True), (lay.conv2, lay.norm2, True), (lay.conv3, lay.norm3, False)):
+                conv(c)
+                norm(n, r)
+            plan["layers"].append(lay)
+    return plan
+
+
+class _BitPrefix:
+    """The BiT ResNet prefix of DPT-Hybrid on renderer R without a library call (self_contained=True): ``plan`` = bit_prefix_plan(backbone).  The standardised
+    weights (bit_standardized_weight) are folded and packed once, here; activations are contiguous float32 NHWC [B, H, W, C] from the first launch to the last.
+    Per bottleneck: three GEMM / convolution launches (four in a stage's first layer, whose shortcut is a convolution too; an im2col launch in front of a strided
+    one) and one vd3d_groupnorm_nhwc_f32 behind each -- the last one with the shortcut and the ReLU in its apply pass.  A call returns the stage-1, -2 and -3 maps."""
+
+    def __init__(self, pipe, backbone, plan, names):
+        self.pipe, self.bb, self.plan, self.names = pipe, backbone, plan, names
+        R, gm = pipe.renderer, pipe.gemm
+        self.ops = {}
+        mods = {id(m): m for m in backbone.modules()}
+        for mid, kind in plan["conv"].items():
+            m = mods[mid]
+            w = bit_standardized_weight(m)
+            if kind == "tile":
+                op = R.conv3x3_tile_pack(w, gm, 1)
+                if op is None:
+                    raise NotImplementedError(f"self_contained=True: {names[mid]}: vd3d_conv3x3_{R.TILE_CONVS[gm, 1]} does not build {m.in_channels} -> {m.out_channels} channels")
+            else:
+                op = R.gemm_x3_pack(w.reshape(m.out_channels, -1) if kind == "gemm" else im2col_gemm_weight(w), gm)
+            self.ops[mid] = (kind, op)
+
+    def conv(self, m, x):
+        pipe, R, gm = self.pipe, self.pipe.renderer, self.pipe.gemm
+        kind, op = self.ops[id(m)]
+        if kind == "gemm":
+            y, how = R.linear_x3(x, op, m.out_channels, None, mode=gm), "vd3d_gemm_x3 over the pixel rows"
+        elif kind == "tile":
+            y = R.conv3x3_tile(x.permute(0, 3, 1, 2), op, m.out_channels, gm, 1).permute(0, 2, 3, 1)
+            how = "vd3d_conv3x3_" + R.TILE_CONVS[gm, 1]
+        else:
+            k, s = m.kernel_size[0], m.stride[0]
+            rows = R.im2col(x, k, s, same_padding(x.shape[1], k, s) + same_padding(x.shape[2], k, s))
+            y, how = R.linear_x3(rows, op, m.out_channels, None, mode=gm), "vd3d_im2col_nhwc_f32 + vd3d_gemm_x3"
+        pipe.conv_routes[self.names[id(m)]] = (gm, "self-contained: " + how)
+        pipe._count_conv(m, y)   # the bypassed module's hook: NHWC or NCHW, the element count per frame is the same
+        return y
+
+    def norm(self, n, y, residual=None, relu=None):
+        relu = self.plan["relu"][id(n)] if relu is None else relu
+        self.pipe.conv_routes[self.names[id(n)]] = (self.pipe.gemm, "self-contained: vd3d_groupnorm_nhwc_f32" + (" + shortcut + ReLU" if residual is not None else ""))
+        return self.pipe.renderer.groupnorm(y, n.num_groups, n.weight, n.bias, n.eps, residual=residual, relu=relu, out=y)
+
+    def __call__(self, pixel_values):
+        R = self.pipe.renderer
+        emb = self.bb.bit.embedder
+        if pixel_values.dtype != torch.float32 or pixel_values.shape[1] != emb.num_channels:
+            raise NotImplementedError(f"self_contained=True: the BiT stem takes a float32 [B, {emb.num_channels}, th, tw] image")
+        x = pixel_values.permute(0, 2, 3, 1).contiguous()   # what depth_preprocess hands over is NHWC storage already
+        x = self.norm(emb.norm, self.conv(emb.convolution, x))
+        x = R.maxpool3x3_s2(x, same_padding(x.shape[1], 3, 2) + same_padding(x.shape[2], 3, 2), float(emb.pooler.pad.value))
+        self.pipe.conv_routes[self.names[id(emb.pooler)]] = (self.pipe.gemm, "self-contained: vd3d_maxpool3x3_s2_nhwc_f32")
+        maps, at = [], 0
+        for stage in self.bb.bit.encoder.stages:
+            for _ in stage.layers:
+                lay = self.plan["layers"][at]
+                at += 1
+                short = x if lay.downsample is None else self.norm(lay.downsample.norm, self.conv(lay.downsample.conv, x))
+                h = self.norm(lay.norm1, self.conv(lay.conv1, x))
+                h = self.norm(lay.norm2, self.conv(lay.conv2, h))
+                x = self.norm(lay.norm3, self.conv(lay.conv3, h), residual=short, relu=True)   # the layer's own ReLU behind the shortcut add
+            maps.append(x)
+        return maps
+
+
 def _head_tail_operands(conv3: torch.nn.Conv2d):
     """() -> (w3, b3) of the head's 1x1 convolution to one channel, for vd3d_dpt_head_tail_f32.  The scalar bias is read on the host ONCE per parameter
     version (no per-call sync); an in-place update of the parameters (load_state_dict, .copy_) bumps their version counters and is picked up at the
@@ -243,8 +410,11 @@ class DepthPipe:
         attention, which scales them by 2^4 before its split (larger values give Inf / NaN, never a finite wrong number: include/vd3d.h).  gfx950 has no TF32 and its float32-input MFMA runs at 1/16 of the bf16 rate, which caps the default mode.
         The split modes cover the DINOv2 family (Depth-Anything V1 / V2, Distill-Any-Depth) and DPT-Large (a plain-ViT ``DPTForDepthEstimation`` with
         readout_type="project"; its readout / 1x1 projections and the transposed convolutions of the reassemble stage go on ``vd3d_gemm_x3`` too, see
-        ``_patch_dpt_vit_reassemble_head``).  Anything else -- DPT-Hybrid, BEiT / Swin backbones, ZoeDepth, DepthPro -- raises NotImplementedError; with
-        ``gemm="f32"`` a DPT model runs its stock module graph unchanged.
+        ``_patch_dpt_vit_reassemble_head``) and DPT-Hybrid in its published geometry (``"dpt-hybrid-midas"``, MiDaS 3.0: ViT-B/16 behind a BiT ResNet-50 prefix;
+        ``_split_scope`` states the geometry): the ViT layers, the 1 x 1 embedding projection of the prefix's stage-3 map and hooks 2 / 3 of the reassemble stage
+        run as for DPT-Large, hooks 0 / 1 are the prefix's stage-1 / stage-2 maps and go to the neck as they are, and the prefix itself stays the module graph on the
+        float32 library (``conv_routes`` says so per module) unless ``self_contained`` is given.  Anything else -- any other hybrid, BEiT / Swin backbones, ZoeDepth,
+        DepthPro -- raises NotImplementedError; with ``gemm="f32"`` a DPT model runs its stock module graph unchanged.
         ``conv``: ``None`` (default) -- the 3 x 3 convolutions of the DPT neck / fusion stage / head run as they always did per mode: library float32
         convolutions in ``"f32"`` and ``"bf16x3"``, ``vd3d_conv3x3_x2`` where its rules allow in ``"fp16x2"``.  ``"bf16x3"`` -- OPT-IN, only with
         ``gemm="bf16x3"`` (else ValueError): the 3 x 3 / stride 1 / padding 1 convolutions -- ``neck.convs``, the fusion stage's residual units, the head's
@@ -272,7 +442,7 @@ class DepthPipe:
         ``self_contained``: ``False`` (default) -- everything above.  ``True`` -- OPT-IN, only with ``gemm="bf16x3"``, ``conv="bf16x3"`` or ``gemm="fp16x2"``, ``conv="fp16x2"``, float32, a renderer on a
         GPU and ``fuse_backbone=True`` (else ValueError naming what is missing), and only for the models of the split modes -- ``DepthAnythingForDepthEstimation`` on
         ``Dinov2Backbone`` whose head ends in ReLU (relative) or Sigmoid (metric: Depth-Anything-V2-Metric-*), and DPT-Large as ``_split_scope`` accepts it
-        (else NotImplementedError naming the model, raised before the renderer or a device is touched): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
+        and DPT-Hybrid likewise (else NotImplementedError naming the model, raised before the renderer or a device is touched): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
         as ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, the reassemble stage's 1 x 1 projections as ``vd3d_gemm_x3`` over the token rows, its transposed
         convolutions as ``vd3d_gemm_x3`` + ``vd3d_depth_to_space_bias_nhwc_f32``, its 3 x 3 stride-2 convolution on ``vd3d_conv3x3_s2_x3``, the fusion layers'
         1 x 1 projections as ``vd3d_gemm_x3`` over the pixel rows, and EVERY 3 x 3 stride-1 convolution on ``vd3d_conv3x3_x3`` (no size rule).  A module the
@@ -285,7 +455,13 @@ class DepthPipe:
         (``vd3d_dpt_head_tail_act_f32``: torch.sigmoid's CPU values); without the keyword a metric model routes as it always did, its head the module graph.
         DPT-Large under the keyword: its patch embedding (16 x 16, K = 768) takes the same patchify + GEMM route, the reassemble stage keeps the split modes'
         readout / projection / transposed-convolution GEMMs and runs hook 3's 3 x 3 stride-2 convolution on the stride-2 tile convolution, and ``neck.convs``,
-        the fusion stage and the head's two 3 x 3 convolutions take the tile convolution at every map size (4 x 4 to 48 x 48 at 384 x 384)."""
+        the fusion stage and the head's two 3 x 3 convolutions take the tile convolution at every map size (4 x 4 to 48 x 48 at 384 x 384).
+        DPT-Hybrid under the keyword: the BiT prefix runs on own kernels too (``_BitPrefix``), on float32 NHWC rows from the first launch to the last -- the weight
+        standardisation folded once at construction (``bit_standardized_weight``: the module's own expression, on the CPU), 1 x 1 convolutions as ``vd3d_gemm_x3``
+        over the pixel rows, 3 x 3 stride-1 convolutions on the tile convolution of the mode, everything strided (the 7 x 7 stem, two 3 x 3, two 1 x 1 shortcuts; TensorFlow
+        "same" padding) as ``vd3d_im2col_nhwc_f32`` + ``vd3d_gemm_x3``, every GroupNorm(32) with its ReLU / shortcut add as ``vd3d_groupnorm_nhwc_f32`` (one fixed
+        summation order: batch-independent, bit-repeatable) and the stem's pool as ``vd3d_maxpool3x3_s2_nhwc_f32``.  A prefix module the mode does not build (a bias, a
+        pre-activation layer, groups other than 32, ``global_padding`` other than "same") is refused by name before the renderer or a device is touched."""
         self.name, self.device, self.dtype = name, torch.device(device), dtype
         if gemm not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
@@ -328,7 +504,10 @@ class DepthPipe:
         self.arch = "da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "generic"
         if self.self_contained:   # refused here, by name, on the module graph as it was handed in: no renderer call, nothing moved to a device yet
             self.model = model
-            if self._split_scope(fuse_backbone) == "dinov2":
+            scope = self._split_scope(fuse_backbone)
+            if scope == "dpt-hybrid":   # the BiT prefix: every module the mode cannot route is refused by name here
+                bit_prefix_plan(model.dpt.embeddings.backbone, {id(m): n for n, m in model.named_modules()})
+            if scope == "dinov2":
                 bc = model.config.backbone_config
                 if int(bc.hidden_size) not in (384, 768, 1024) or int(bc.hidden_size) != 64 * int(bc.num_attention_heads):
                     raise NotImplementedError(f"self_contained=True: {name!r}: hidden size {bc.hidden_size} with {bc.num_attention_heads} heads -- vd3d_attention_x3 and "
@@ -347,11 +526,17 @@ class DepthPipe:
         self.renderer = renderer if (renderer is not None and self.device.type == "cuda") else None
         dino = self.arch == "da" and type(self.model.backbone).__name__ == "Dinov2Backbone"
         # dpt_vit: DPT-Large's rewrite runs (split modes only; arch stays "generic": gemm="f32" keeps the stock DPT module graph)
-        self.dpt_vit = False
-        if self.gemm != "f32" and self._split_scope(fuse_backbone) == "dpt-vit":
+        # dpt_hybrid: DPT-Hybrid's rewrite runs (dpt_vit is set too: the ViT half, the reassemble stage, the neck and the head are DPT-Large's rewrite)
+        self.dpt_vit = self.dpt_hybrid = False
+        scope = self._split_scope(fuse_backbone) if self.gemm != "f32" else None
+        if scope == "dpt-vit":
             self._rewrite_dpt_vit()
             if self.self_contained:
                 self._patch_patch_embedding(self.model.dpt.embeddings.patch_embeddings)
+        elif scope == "dpt-hybrid":
+            self.dpt_hybrid = True
+            self._rewrite_dpt_vit()
+            self._patch_hybrid_embeddings()
         if dino:
             self._cache_position_embeddings()
             if fuse_backbone:
@@ -765,6 +950,9 @@ class DepthPipe:
         names = {id(m): n for n, m in self.model.named_modules()}
         hooks = []
         for i, lay in enumerate(stage.layers):
+            if i in stage.neck_ignore_stages:   # DPT-Hybrid's hooks 0 / 1: maps of the BiT prefix, handed to neck.convs as they are
+                hooks.append(None)
+                continue
             rl, ract = stage.readout_projects[i][0], stage.readout_projects[i][1]
             gelu = isinstance(ract, torch.nn.GELU) and getattr(ract, "approximate", "none") == "none" or type(ract).__name__ == "GELUActivation"
             pw = lay.projection.weight
@@ -782,6 +970,9 @@ class DepthPipe:
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
             for hk, hs in zip(hooks, hidden_states):
+                if hk is None:
+                    out.append(hs)
+                    continue
                 B, T, d = hs.shape
                 if patch_height is None or patch_width is None:   # the stock stage's square grid
                     patch_height = patch_width = int((T - 1) ** 0.5)
@@ -948,8 +1139,10 @@ class DepthPipe:
         return fwd
 
     def _split_scope(self, fuse_backbone: bool = True) -> str:
-        """Which rewrite ``gemm="bf16x3" / "fp16x2"`` applies to this model: "dinov2" (DepthAnythingForDepthEstimation on Dinov2Backbone) or "dpt-vit"
-        (DPTForDepthEstimation on its plain ViT encoder with readout_type="project": DPT-Large).  Everything else raises NotImplementedError naming the model.
+        """Which rewrite ``gemm="bf16x3" / "fp16x2"`` applies to this model: "dinov2" (DepthAnythingForDepthEstimation on Dinov2Backbone), "dpt-vit"
+        (DPTForDepthEstimation on its plain ViT encoder with readout_type="project": DPT-Large) or "dpt-hybrid" (DPTForDepthEstimation with is_hybrid in the
+        published Intel/dpt-hybrid-midas geometry: four hooks, neck_ignore_stages [0, 1], readout_type="project", a BiT bottleneck backbone of three stages and 32
+        groups; any other hybrid is refused as "DPT-Hybrid ...").  Everything else raises NotImplementedError naming the model.
         ``self_contained=True`` covers exactly the models of the split modes, so the constructor asks here too; the refusal then names the keyword.  Reads the
         module graph and its configuration only."""
         m, what = self.model, f"{self.name!r} ({type(self.model).__name__}"
@@ -965,15 +1158,28 @@ class DepthPipe:
 
         def refuse(why):
             raise NotImplementedError(f"{tag}: {what}: {why} -- not built in the split modes; gemm='f32' runs the stock float32 graph")
-        if cfg.is_hybrid:
-            refuse("DPT-Hybrid (MiDaS 3.0 hybrid, Intel/dpt-hybrid-midas: BiT stem, identity readout on hooks 0 / 1)")
-        if getattr(m, "backbone", None) is not None or cfg.backbone_config is not None:
-            bname = type(m.backbone).__name__ if getattr(m, "backbone", None) is not None else cfg.backbone_config.model_type
-            refuse(f"a {bname} backbone (e.g. Intel/dpt-beit-large-512: BEiT's relative position bias has no input in vd3d_attention_x3)")
-        if cfg.readout_type != "project":
-            refuse(f"readout_type={cfg.readout_type!r} (only 'project' is built)")
-        if list(cfg.neck_ignore_stages or []):
-            refuse(f"neck_ignore_stages={cfg.neck_ignore_stages}")
+        hybrid = bool(cfg.is_hybrid)
+        if hybrid:   # exactly the geometry _rewrite_dpt_hybrid builds: the published Intel/dpt-hybrid-midas one, at the hidden sizes the kernels have
+            bc = cfg.backbone_config
+            bit = bc is not None and getattr(bc, "model_type", None) == "bit"
+            why = (f"{len(cfg.backbone_out_indices)} hooks / {len(cfg.neck_hidden_sizes)} neck stages" if len(cfg.backbone_out_indices) != 4 or len(cfg.neck_hidden_sizes) != 4
+                   else f"neck_ignore_stages={cfg.neck_ignore_stages}" if list(cfg.neck_ignore_stages or []) != [0, 1]
+                   else f"readout_type={cfg.readout_type!r}" if cfg.readout_type != "project"
+                   else "no BiT backbone" if not bit
+                   else f"a BiT backbone of layer_type={bc.layer_type!r}" if bc.layer_type != "bottleneck"
+                   else f"a BiT backbone with {len(bc.depths)} stages" if len(bc.depths) != 3
+                   else f"a BiT backbone with {bc.num_groups} groups" if int(bc.num_groups) != 32 else None)
+            if why is not None:
+                refuse(f"DPT-Hybrid (MiDaS 3.0 hybrid, Intel/dpt-hybrid-midas) with {why} (built: four hooks, neck_ignore_stages [0, 1], readout_type 'project', a BiT "
+                       "bottleneck backbone of three stages and 32 groups; the BiT stem feeds hooks 0 / 1 through an identity readout)")
+        else:
+            if getattr(m, "backbone", None) is not None or cfg.backbone_config is not None:
+                bname = type(m.backbone).__name__ if getattr(m, "backbone", None) is not None else cfg.backbone_config.model_type
+                refuse(f"a {bname} backbone (e.g. Intel/dpt-beit-large-512: BEiT's relative position bias has no input in vd3d_attention_x3)")
+            if cfg.readout_type != "project":
+                refuse(f"readout_type={cfg.readout_type!r} (only 'project' is built)")
+            if list(cfg.neck_ignore_stages or []):
+                refuse(f"neck_ignore_stages={cfg.neck_ignore_stages}")
         if m.head.projection is not None:
             refuse("a head projection (add_projection=True)")
         if cfg.use_batch_norm_in_fusion_residual:
@@ -982,7 +1188,7 @@ class DepthPipe:
         if d not in (384, 768, 1024) or d // nh != 64 or d % nh:
             refuse(f"hidden size {d} with {nh} heads (built: 384 / 768 / 1024, 64-wide heads)")
         for lay in m.neck.reassemble_stage.layers:
-            r = lay.resize
+            r = getattr(lay, "resize", None)   # (DPT-Hybrid's hooks 0 / 1 are nn.Identity layers)
             if isinstance(r, torch.nn.ConvTranspose2d) and not (r.kernel_size == r.stride and r.padding == (0, 0) and r.output_padding == (0, 0)
                                                                  and r.dilation == (1, 1) and r.groups == 1):
                 refuse(f"a reassemble ConvTranspose2d with kernel {r.kernel_size} / stride {r.stride} / padding {r.padding} (built: kernel == stride, no padding)")
@@ -990,7 +1196,7 @@ class DepthPipe:
         if not (len(hs) == 6 and isinstance(hs[1], torch.nn.Upsample) and isinstance(hs[3], torch.nn.ReLU) and isinstance(hs[5], torch.nn.ReLU)
                 and hs[4].kernel_size == (1, 1) and hs[2].out_channels in (16, 32, 64) and hs[1].scale_factor in (2, 2.0) and hs[1].align_corners):
             refuse("a depth head other than DPT's [conv, Upsample x2, conv -> 16 / 32 / 64, ReLU, conv 1x1, ReLU]")
-        return "dpt-vit"
+        return "dpt-hybrid" if hybrid else "dpt-vit"
 
     def _rewrite_dpt_vit(self):
         """The split-mode rewrite of a plain-ViT DPTForDepthEstimation (DPT-Large; _split_scope has accepted it): position embeddings memoised, the ViT
@@ -999,6 +1205,45 @@ class DepthPipe:
         self._cache_vit_position_embeddings()
         self._fuse_vit_layers()
         self._patch_dpt_upsampling()
+
+    def _patch_hybrid_embeddings(self):
+        """DPT-Hybrid's embeddings (DPTViTHybridEmbeddings; _split_scope has accepted the model) in the split modes: the 1 x 1 projection of the BiT stage-3 map
+        (1024 -> hidden) as vd3d_gemm_x3 over its pixel rows, with its bias -- [B, gh gw, hidden] directly, no flatten / transpose copy; CLS and the memoised
+        position embedding stay ATen element-wise kernels.  The BiT prefix in front of it: without ``self_contained`` the module graph on the float32 library
+        (conv_routes says so for every convolution and normalisation of it, by module name); with it _BitPrefix, on own kernels.  The stage-1 / stage-2 maps go
+        on as channels_last [B, C, h, w] tensors: hooks 0 / 1 of the reassemble stage."""
+        from transformers.models.dpt.modeling_dpt import BaseModelOutputWithIntermediateActivations as Out
+        R, gm, sc = self.renderer, self.gemm, self.self_contained
+        emb = self.model.dpt.embeddings
+        pm, bb = emb.projection, emb.backbone
+        names = {id(m): n for n, m in self.model.named_modules()}
+        if not _is_conv(pm, 1, 1, 0) or pm.in_channels % 16:
+            raise NotImplementedError(f"gemm={gm!r}: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
+        img = R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm)
+        prefix = _BitPrefix(self, bb, bit_prefix_plan(bb, names), names) if sc else None
+        lib_names = [names[id(m)] for m in bb.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.GroupNorm))]
+
+        def emb_fwd(pixel_values, interpolate_pos_encoding=False):
+            B, C, H, W = pixel_values.shape
+            if C != emb.num_channels:
+                raise ValueError("Make sure that the channel dimension of the pixel values match with the one set in the configuration.")
+            if not interpolate_pos_encoding and (H != emb.image_size[0] or W != emb.image_size[1]):
+                raise ValueError(f"Input image size ({H}*{W}) doesn't match model ({emb.image_size[0]}*{emb.image_size[1]}).")
+            pos = emb._resize_pos_embed(emb.position_embeddings, H // emb.patch_size, W // emb.patch_size)
+            if sc:
+                f1, f2, f3 = prefix(pixel_values)
+                hooks = [f1.permute(0, 3, 1, 2), f2.permute(0, 3, 1, 2)]
+            else:
+                maps = bb(pixel_values).feature_maps
+                for n in lib_names:
+                    self.conv_routes[n] = ("library", "the BiT prefix stays the module graph without self_contained=True")
+                hooks, f3 = [maps[i] for i in emb.residual_feature_map_index], maps[-1].permute(0, 2, 3, 1).contiguous()
+            tok = R.linear_x3(f3.reshape(B, f3.shape[1] * f3.shape[2], f3.shape[3]), img, pm.out_channels, pm.bias, mode=gm)
+            self.conv_routes[names[id(pm)]] = (gm, ("self-contained: " if sc else "") + "vd3d_gemm_x3 over the pixel rows")
+            self._count_conv(pm, tok)   # the bypassed Conv2d
+            x = torch.cat((emb.cls_token.expand(B, -1, -1), tok), dim=1) + pos
+            return Out(last_hidden_states=x, intermediate_activations=hooks)
+        emb.forward = emb_fwd
 
     def _cache_vit_position_embeddings(self):
         """DPTViTEmbeddings re-interpolates its position embedding (bilinear, 24 x 24 -> patch grid) on every forward; for a fixed input size the result is a
@@ -1226,6 +1471,8 @@ class DepthPipe:
         for the backbone, the EXECUTED convolution flops of the DPT neck / head counted during one forward."""
         th, tw = self.resize_target(h, w)
         bcfg = getattr(self.model.config, "backbone_config", None) or self.model.config
+        if not hasattr(bcfg, "patch_size"):   # DPT-Hybrid: the backbone configuration is the BiT prefix's; the transformer is the model's own
+            bcfg = self.model.config
         ps = int(bcfg.patch_size)
         T = (th // ps) * (tw // ps) + 1
         d, L = int(bcfg.hidden_size), int(bcfg.num_hidden_layers)

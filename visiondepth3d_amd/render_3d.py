@@ -1214,6 +1214,63 @@ class Renderer:
         _lib.check(self._L.vd3d_patchify_f32(self._ctx, _ptr(x), B, th, tw, p, _ptr(out)))
         return out
 
+    # ---- the BiT ResNet prefix of DPT-Hybrid (vd3d_bit.hip); tensors are contiguous float32 NHWC [B, H, W, C]
+    @staticmethod
+    def _nhwc_rows(*ts):
+        for t in ts:
+            if t is not None and not (t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous()):
+                raise ValueError("contiguous float32 NHWC [B, H, W, C] tensors expected")
+
+    def im2col(self, x: torch.Tensor, k: int, stride: int, pad, out=None) -> torch.Tensor:
+        """The rows of a k x k convolution run as a GEMM: contiguous float32 NHWC ``x`` [B, H, W, C], ``pad`` = (top, bottom, left, right) zeros ->
+        [B, Ho, Wo, Kp], column (ky * k + kx) * C + c (``im2col_gemm_weight``'s order), Kp = k k C rounded up to a multiple of 16 with a zero tail
+        (include/vd3d.h vd3d_im2col_nhwc_f32).  ``out``: the rows' buffer, every element of which is written."""
+        self._nhwc_rows(x)
+        B, H, W, Cc = x.shape
+        pt, pb, pl, pr = (int(v) for v in pad)
+        k, stride = int(k), int(stride)
+        if stride < 1 or H + pt + pb < k or W + pl + pr < k:
+            raise ValueError(f"im2col: a {H} x {W} map padded by {tuple(pad)} holds no {k} x {k} window")
+        Ho, Wo = (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
+        shape = (B, Ho, Wo, (k * k * Cc + 15) // 16 * 16)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"im2col: out must be a contiguous float32 tensor of shape {shape}")
+        self._enter(x, out)
+        _lib.check(self._L.vd3d_im2col_nhwc_f32(self._ctx, _ptr(x), B, H, W, Cc, k, stride, pt, pb, pl, pr, _ptr(out)))
+        return out
+
+    def maxpool3x3_s2(self, x: torch.Tensor, pad, pad_value: float = 0.0) -> torch.Tensor:
+        """F.max_pool2d(F.pad(x, pad, value=pad_value), 3, 2) for a contiguous float32 NHWC [B, H, W, C] tensor, ``pad`` = (top, bottom, left, right)
+        (include/vd3d.h vd3d_maxpool3x3_s2_nhwc_f32)."""
+        self._nhwc_rows(x)
+        B, H, W, Cc = x.shape
+        pt, pb, pl, pr = (int(v) for v in pad)
+        if H + pt + pb < 3 or W + pl + pr < 3:
+            raise ValueError(f"maxpool3x3_s2: a {H} x {W} map padded by {tuple(pad)} holds no 3 x 3 window")
+        out = torch.empty((B, (H + pt + pb - 3) // 2 + 1, (W + pl + pr - 3) // 2 + 1, Cc), dtype=torch.float32, device=x.device)
+        self._enter(x, out)
+        _lib.check(self._L.vd3d_maxpool3x3_s2_nhwc_f32(self._ctx, _ptr(x), B, H, W, Cc, pt, pb, pl, pr, float(pad_value), _ptr(out)))
+        return out
+
+    def groupnorm(self, x: torch.Tensor, groups: int, weight: torch.Tensor, bias: torch.Tensor, eps: float, residual=None, relu: bool = False, out=None) -> torch.Tensor:
+        """[relu](group_norm(x, groups, weight, bias, eps) [+ residual]) for contiguous float32 NHWC [B, H, W, C] tensors: mean first, then the centred sum of
+        squares, in one fixed summation order -- a frame's values do not depend on its batch (include/vd3d.h vd3d_groupnorm_nhwc_f32).  ``out`` may be ``x``."""
+        self._nhwc_rows(x, residual, out)
+        B, H, W, Cc = x.shape
+        if residual is not None and residual.shape != x.shape:
+            raise ValueError("groupnorm: the residual must have x's shape")
+        nb = int(self._L.vd3d_groupnorm_nhwc_f32_workspace_bytes(B, H * W, Cc, int(groups)))
+        if nb < 0:
+            raise NotImplementedError(f"groupnorm: {Cc} channels in {groups} groups (batch {B}, {H * W} pixels) not built")
+        ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+        out = torch.empty_like(x) if out is None else out
+        self._enter(x, residual, weight, bias, ws, out)
+        _lib.check(self._L.vd3d_groupnorm_nhwc_f32(self._ctx, _ptr(x), _ptr(residual) if residual is not None else None, _ptr(weight), _ptr(bias), float(eps),
+                                                   _abi.GN_RELU if relu else 0, B, H * W, Cc, int(groups), _ptr(ws), nb, _ptr(out)))
+        return out
+
     def detect_black_bars(self, frame_bgr: torch.Tensor):
         """detect_black_bars(frame_to_tensor(frame)) (core/render_3d.py:293-316) on a uint8 BGR frame -> (top, bottom)."""
         f = frame_bgr.to(self.device, torch.uint8).contiguous()
