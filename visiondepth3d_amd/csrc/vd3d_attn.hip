@@ -329,8 +329,17 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
 // of iteration it - 1 follows every wave's reads of it).  K is XOR-swizzled (16-byte chunk c of row r at chunk c ^ (r & 15): the DMA picks each lane's source
 // chunk, the LDS image stays lane-linear) so that the 16-lane groups of ds_read_b128 see 16 distinct chunks; V is linear (a ds_read_b64 of 32 lanes reads one
 // whole 256-byte row).  Every DMA source row is clamped to T - 1: no zero-padded image, nothing read past the tensor, logits of rows past T are finite before
-// they are masked to -inf (p = 0 exactly).  Per tile and wave: 128 MFMAs (8 192 matrix-pipe cycles) against ~100 VALU instructions of softmax; O is rescaled
-// only when some lane's running maximum grew (alpha = exp2(0) = 1 exactly for the others).
+// they are masked to -inf (p = 0 exactly).  O is rescaled only when some lane's running maximum grew (alpha = exp2(0) = 1 exactly for the others).
+// What the tile loop issues per wave and 64-row tile (profiles/r23_attn_f32_lean.md): 128 MFMAs (8 192 matrix-pipe cycles) and ~131 VALU instructions -- 32
+// v_sub, 32 v_exp, 33 v_add, 16 v_max3 + 3 v_max, 4 for the cross-half maximum (v_permlane32_swap) and the rescale test, and 11 of addresses (3 for the
+// tile's DMA, 8 bases of the paired V reads), down from 63 of addresses in the 4-wave form: the DMA sources are a scalar base per tile and pass plus a per-lane offset computed once, and the loop is
+// unrolled over the ring so that every LDS read is a loop-invariant register plus an immediate.  On gfx950 float32-input MFMA and the VALU share the FP32
+// ALUs: their times add wherever the instructions are scheduled, so issuing the next tile's S^T under the softmax is NOT an open lever here (two attempts
+// measured nothing); only fewer vector instructions per tile are.
+// A last tile with at most 32 live rows (T mod 64 in 1 .. 32) runs outside the loop with its second 32-row M tile left out of both products.  For S^T this is
+// exact on every input (those 16 logits are masked to -inf either way).  For P V it drops 32 MFMAs that add v * 0 to every accumulator, which changes a result
+// in two cases only, neither reachable from finite data: an accumulator that is exactly -0 (the + 0 made it +0) and a non-finite V in the clamped row T - 1
+// (inf * 0 made it NaN).
 #define AF_TILE (AT_BK * AT_D * 4)   // 16 384 bytes: 64 rows x 256
 #define AF_STAGE (2 * AF_TILE)       // K + V
 #define AF_LDS(NS) ((NS) * AF_STAGE)   // 98 304 (8 waves, three stages) / 65 536 (4 waves, two stages)
@@ -344,41 +353,50 @@ __global__ __launch_bounds__(AT_NT) void k_attn_bf16x3(const uint4* __restrict__
 // Per query both forms run the same operations in the same order (tiles ascending, the two S^T chains, masking, maximum, rescale, sum order, P V chain, division):
 // their results are bit-identical (tests/test_hip_attention_f32_forms.py).
 static_assert(2 * AF_LDS(2) <= 160 * 1024, "two 4-wave workgroups per CU");
+static_assert(AF_LDS(2) == 65536 && AF_LDS(3) == 98304, "the rings' dynamic LDS; the two-stage ring ends at byte 65 535, the reach of a DS instruction's offset field");
 // The two matrix products of one tile, each reading its stage of the ring through a restrict pointer: inlined, the LDS reads carry alias-scope information
 // (one scope per product, kept when the compiler pairs reads), and the compiler's wait-count pass then does not put a conservative vmcnt(0) behind every
 // LDS-DMA in front of them -- the ring is ordered by the kernel's own counted waits and barriers.
-// S^T[m] = K Q^T for the 32-row M tiles m = 0, 1 (q pre-scaled); K row r at sk + 256 r, 16-byte chunk c at position c ^ (r & 15)
-VD_DEV void af_st(const uint8_t* __restrict__ sk, const float (&qf)[32], int li, int kh, x3_f16 (&s)[2]) {
-  const int kswz = (li & 15) << 4;
+// Both take the ring stage as an argument that is a constant in every copy of the unrolled tile loop, and the lane's part of the address from loop-invariant
+// registers: a K read is one register plus an immediate (the paired V reads take one base per four rows).
+// NM = 2: the whole 64-row tile.  NM = 1: its first 32-row M tile only -- a last tile whose rows 32 .. 63 are all past T (the header above says what that leaves out).
+// S^T[m] = K Q^T for the 32-row M tiles m = 0, 1 (q pre-scaled); K row r at 256 r of its tile, 16-byte chunk c at position c ^ (r & 15):
+// kp[g] = at_lds + 256 li + (((8 kh + g) << 4) ^ ((li & 15) << 4)), the lane's row and swizzled chunk of k-steps 4 g .. 4 g + 3 in stage 0.  NM = 1 leaves
+// S^T[1] at -inf.  af_st_g is the four k-steps of one g (one restrict pointer, one alias scope each), af_st the product.
+template <int N> struct af_ic { static constexpr int value = N; };
+template <int NM, int G>
+VD_DEV void af_st_g(const uint8_t* __restrict__ kp, int stage, const float (&qf)[32], x3_f16 (&s)[2]) {
+  float4 kf[NM];
 #pragma unroll
-  for (int m = 0; m < 2; ++m)
+  for (int m = 0; m < NM; ++m) kf[m] = *reinterpret_cast<const float4*>(kp + stage * AF_STAGE + 32 * 256 * m);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) s[m][r] = 0.f;
+  for (int m = 0; m < NM; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].x, qf[4 * G], s[m], 0, 0, 0);
 #pragma unroll
-  for (int g = 0; g < 8; ++g) {
-    float4 kf[2];
+  for (int m = 0; m < NM; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].y, qf[4 * G + 1], s[m], 0, 0, 0);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) kf[m] = *reinterpret_cast<const float4*>(sk + (32 * m + li) * 256 + (((8 * kh + g) << 4) ^ kswz));
+  for (int m = 0; m < NM; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].z, qf[4 * G + 2], s[m], 0, 0, 0);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].x, qf[4 * g], s[m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].y, qf[4 * g + 1], s[m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].z, qf[4 * g + 2], s[m], 0, 0, 0);
-#pragma unroll
-    for (int m = 0; m < 2; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].w, qf[4 * g + 3], s[m], 0, 0, 0);
-  }
+  for (int m = 0; m < NM; ++m) s[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[m].w, qf[4 * G + 3], s[m], 0, 0, 0);
 }
-// O^T[dm] += V^T P^T: register r of M tile m is the K = 2 step of kv 32 m + (r & 3) + 8 (r >> 2) + 4 kh; V row kv at sv + 256 kv (linear), d = 2 li + dm
-VD_DEV void af_pv(const uint8_t* __restrict__ sv, const x3_f16 (&p)[2], int li, int kh, x3_f16 (&oacc)[2]) {
+template <int NM>
+VD_DEV void af_st(const uint8_t* const (&kp)[8], int stage, const float (&qf)[32], x3_f16 (&s)[2]) {
 #pragma unroll
   for (int m = 0; m < 2; ++m)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float2 vv = *reinterpret_cast<const float2*>(sv + (32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh) * 256 + li * 8);
-      oacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.x, p[m][r], oacc[0], 0, 0, 0);
-      oacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.y, p[m][r], oacc[1], 0, 0, 0);
-    }
+    for (int r = 0; r < 16; ++r) s[m][r] = m < NM ? 0.f : -INFINITY;
+  af_st_g<NM, 0>(kp[0], stage, qf, s); af_st_g<NM, 1>(kp[1], stage, qf, s); af_st_g<NM, 2>(kp[2], stage, qf, s); af_st_g<NM, 3>(kp[3], stage, qf, s);
+  af_st_g<NM, 4>(kp[4], stage, qf, s); af_st_g<NM, 5>(kp[5], stage, qf, s); af_st_g<NM, 6>(kp[6], stage, qf, s); af_st_g<NM, 7>(kp[7], stage, qf, s);
+}
+// O^T[dm] += V^T P^T: register r of M tile m is the K = 2 step of kv 32 m + (r & 3) + 8 (r >> 2) + 4 kh; V row kv at sv + 256 kv (linear), d = 2 li + dm:
+// va = 1 024 kh + 8 li.  One call is one M tile (M = 0, then M = 1: the chain's order).
+template <int M>
+VD_DEV void af_pv(const uint8_t* __restrict__ sv, const x3_f16 (&p)[2], uint32_t va, x3_f16 (&oacc)[2]) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float2 vv = *reinterpret_cast<const float2*>(sv + va + (32 * M + (r & 3) + 8 * (r >> 2)) * 256);
+    oacc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.x, p[M][r], oacc[0], 0, 0, 0);
+    oacc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.y, p[M][r], oacc[1], 0, 0, 0);
+  }
 }
 
 template <int NW, int NS>
@@ -406,17 +424,43 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_attn_f32(const flo
 
   // one tile's DMA: thread tid fills LDS chunks tid + 64 NW p (p < NP) of the K and of the V image = rows tid / 16 + 4 NW p, chunk position tid & 15 (4 NW is a
   // multiple of 16: the K swizzle of a thread is the same in every pass)
+  // A tile that lies inside T is fetched with no vector arithmetic: the lane's byte offsets inside a pass (row drow, its K and its V chunk; below 2^32: 31 token
+  // rows of 768 H bytes, H < 2^16) are computed once, and each DMA's source is a wave-uniform 64-bit base (tile and pass, scalar arithmetic) plus that 32-bit
+  // offset.  Only the tile that crosses T needs its rows clamped to T - 1 per lane: a uniform branch that the last tile alone takes.
   const int drow = tid >> 4, dpos = tid & 15, kchunk = dpos ^ (drow & 15);
+  const uint32_t tok_bytes = 3u * 4u * AT_D * (uint32_t)a.H;
+  const uint32_t koff = (uint32_t)drow * tok_bytes + (uint32_t)kchunk * 16u, voff = (uint32_t)drow * tok_bytes + (uint32_t)dpos * 16u;
+  const uint64_t kbase = reinterpret_cast<uint64_t>(base + a.H * AT_D), vbase = reinterpret_cast<uint64_t>(base + 2 * a.H * AT_D);
   auto dma = [&](int tile, int stage) {
     uint8_t* dst = at_lds + stage * AF_STAGE + wave * 1024;
+    if ((tile + 1) * AT_BK <= a.T) {
+      // the empty asm statements pin the two parts where they are used -- the base in scalar registers, the 32-bit offset widened here and not once in front
+      // of the loop -- so that the load is selected in its scalar-base + 32-bit-offset form instead of one 64-bit sum per lane and load
+      uint32_t ko = koff, vo = voff;
+      asm("" : "+v"(ko), "+v"(vo));
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int tok = min(tile * AT_BK + drow + 4 * NW * p, a.T - 1);
-      const float* src = base + (size_t)tok * tok_stride + a.H * AT_D;
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + kchunk * 4), (x3_lds_vp)(dst + p * (NW * 1024)), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + a.H * AT_D + dpos * 4), (x3_lds_vp)(dst + AF_TILE + p * (NW * 1024)), 16, 0, 0);
+      for (int p = 0; p < NP; ++p) {
+        const uint64_t row0 = (uint64_t)(tile * AT_BK + 4 * NW * p) * tok_bytes;
+        uint64_t ks = kbase + row0, vs = vbase + row0;
+        asm("" : "+s"(ks), "+s"(vs));
+        __builtin_amdgcn_global_load_lds((x3_glb_vp)(ks + ko), (x3_lds_vp)(dst + p * (NW * 1024)), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((x3_glb_vp)(vs + vo), (x3_lds_vp)(dst + AF_TILE + p * (NW * 1024)), 16, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const int tok = min(tile * AT_BK + drow + 4 * NW * p, a.T - 1);
+        const float* src = base + (size_t)tok * tok_stride + a.H * AT_D;
+        __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + kchunk * 4), (x3_lds_vp)(dst + p * (NW * 1024)), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((x3_glb_vp)(src + a.H * AT_D + dpos * 4), (x3_lds_vp)(dst + AF_TILE + p * (NW * 1024)), 16, 0, 0);
+      }
     }
   };
+  // the lane's part of every LDS read address (af_st, af_pv)
+  const uint8_t* kp[8];
+#pragma unroll
+  for (int g = 0; g < 8; ++g) kp[g] = at_lds + (li * 256 + (((8 * kh + g) << 4) ^ ((li & 15) << 4)));
+  const uint32_t va = (uint32_t)(kh * 1024 + li * 8);
 
   // Q of the wave's 32 queries (rows past T read row T - 1 and are never stored), pre-scaled by scale * log2 e
   float qf[32];
@@ -446,20 +490,21 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_attn_f32(const flo
 #pragma unroll
     for (int r = 0; r < 16; ++r) oacc[dm][r] = 0.f;
   float m_run = -INFINITY, l_half = 0.f;
-  int cur = 0;
-  for (int it = 0; it < a.nkv; ++it) {
+  // One tile.  stage: the ring stage it reads; NM = 2: the whole tile, NM = 1: a last tile with at most 32 live rows -- its second M tile is all past T and is
+  // left out of both products (k_attn_f32's header says what that changes).
+  auto tile = [&](int it, int stage, auto nm) __attribute__((always_inline)) {
+    constexpr int NM = decltype(nm)::value;
     const bool ahead = it + (NS - 1) < a.nkv;
-    if (NS == 3) { if (ahead) dma(it + 2, cur == 0 ? 2 : cur - 1); }
-    else { if (ahead) dma(it + 1, cur ^ 1); }   // the stage tile it - 1 left: every wave's reads of it returned before the barrier that ended iteration it - 1
-    const uint8_t* sk = at_lds + cur * AF_STAGE;
-    const uint8_t* sv = sk + AF_TILE;
+    // the stage tile it - 1 left: every wave's reads of it returned before the barrier that ended iteration it - 1
+    if (ahead) dma(it + (NS - 1), (stage + NS - 1) % NS);
+    const uint8_t* sv = at_lds + stage * AF_STAGE + AF_TILE;
     if (live) {
       // ---- S^T = K Q^T (pre-scaled logits)
       x3_f16 s[2];
-      af_st(sk, qf, li, kh, s);
+      af_st<NM>(kp, stage, qf, s);
       if ((it + 1) * AT_BK > a.T) {   // last tile: rows past T (a uniform branch off the hot path)
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
+        for (int m = 0; m < NM; ++m)
 #pragma unroll
           for (int r = 0; r < 16; ++r)
             if (it * AT_BK + 32 * m + (r & 3) + 8 * (r >> 2) + 4 * kh >= a.T) s[m][r] = -INFINITY;
@@ -470,7 +515,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_attn_f32(const flo
       for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[m][r]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      {   // the other lane half's maximum by v_permlane32_swap (both results hold one half's values in all 64 lanes), not through the LDS pipe
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
+        mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
+      }
       const float m_new = fmaxf(m_run, mx);
       if (__any(m_new > m_run)) {
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // 0 on the first tile (m_run = -inf), exactly 1 where the maximum did not grow
@@ -488,14 +536,27 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_attn_f32(const flo
         for (int r = 0; r < 16; ++r) { s[m][r] = __builtin_amdgcn_exp2f(s[m][r] - m_run); ps += s[m][r]; }
       l_half += ps;
       // ---- O^T += V^T P^T
-      af_pv(sv, s, li, kh, oacc);
+      af_pv<0>(sv, s, va, oacc);
+      if (NM == 2) af_pv<1>(sv, s, va, oacc);
     }
-    // before the barrier: this wave's reads of stage cur have returned (behind it, the next iteration's DMA overwrites that stage: tile it + 3 / it + 2) and
+    // before the barrier: this wave's reads of this stage have returned (behind it, the next iteration's DMA overwrites that stage: tile it + 3 / it + 2) and
     // tile it + 1 has landed (three stages: the four DMA instructions of tile it + 2 may stay in flight; two stages: tile it + 1 is the only one in flight)
     if (NS == 3 && ahead) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    cur = NS == 3 ? (cur == 2 ? 0 : cur + 1) : cur ^ 1;
+  };
+  // The tile loop is unrolled over the ring: copy u of the body serves the tiles it = u (mod NS), so the stage it reads (u) and the stage its DMA fills are
+  // compile-time constants and every LDS address of the loop is a loop-invariant register plus an immediate.  Waits and barrier are per tile as before -- each
+  // copy ends with the counted wait and the one barrier of its tile -- and the loop may end behind any copy.  A last tile with at most 32 live rows (T mod 64
+  // in 1 .. 32) is taken out of the loop: one more copy of the body, NM = 1, its stage a run-time value.
+  const int nfull = (a.nkv - 1) * AT_BK + 32 >= a.T ? a.nkv - 1 : a.nkv;
+  for (int it0 = 0; it0 < nfull; it0 += NS) {
+#pragma unroll
+    for (int u = 0; u < NS; ++u) {
+      if (it0 + u >= nfull) break;
+      tile(it0 + u, u, af_ic<2>());
+    }
   }
+  if (nfull < a.nkv) tile(nfull, nfull % NS, af_ic<1>());
 
   // ---- epilogue: out[b][q][h][16 g + 8 kh + 2 j + dm] = O^T_dm[register 4 g + j] / l
   const float l_tot = l_half + __shfl_xor(l_half, 32, 64);
