@@ -40,7 +40,8 @@ extern "C" {
  *    vd3d_conv3x3_s1_x2_* and vd3d_conv3x3_s2_x2_* (weight_bytes, pack_weights and the convolution each: DepthPipe(conv="fp16x2")),
  *    vd3d_resize_pil_bicubic_u8, vd3d_depth_preprocess_pil (DepthPipe(front_end="pil")), vd3d_dpt_head_tail_act_f32 (the sigmoid tail of the metric
  *    Depth-Anything heads under DepthPipe(self_contained=True)), vd3d_im2col_nhwc_f32, vd3d_maxpool3x3_s2_nhwc_f32, vd3d_groupnorm_nhwc_f32_workspace_bytes and
- *    vd3d_groupnorm_nhwc_f32: the BiT prefix of DPT-Hybrid under DepthPipe(self_contained=True). */
+ *    vd3d_groupnorm_nhwc_f32: the BiT prefix of DPT-Hybrid under DepthPipe(self_contained=True), vd3d_neck_poly_weight_bytes, vd3d_neck_poly_pack_f32 and
+ *    vd3d_neck_poly_conv_f32 (the float32 neck's transposed convolution + 3 x 3 convolution in polyphase form). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -694,6 +695,19 @@ int64_t vd3d_dpt_head_conv_weight_bytes(int Cin, int Cout);
 int vd3d_dpt_head_conv_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
 int vd3d_dpt_head_conv_f32(vd3d_ctx* ctx, const float* x, const float* b_in, int B, int ih, int iw, int oh, int ow, int Cin, const void* w_image, int Cout,
                            const float* b2_or_null, const float* w3_or_null, float b3, float scale, float* out);
+
+/* The neck's ConvTranspose2d(C, C, kernel_size=f, stride=f) with bias and the bias-free 3 x 3 / padding 1 convolution behind it as ONE exact-float32 kernel on the
+ * coarse map (v_mfma_f32_32x32x2_f32, float32 accumulation, no split-K, no atomics: a frame's bits depend neither on the batch nor on the call):
+ *     out[b][f i + pa][f j + pb][:] = sum_k Wc[k] x[b][i + di_k][j + dj_k][:] + sum_k bc[k]     over the blocks k of phase (pa, pb) whose coarse pixel is inside the map
+ * x float32 NHWC [B][h][w][Cin] -> out float32 NHWC [B][f h][f w][Cout]; the fine map between the two layers is never written.  Blocks: phases (pa, pb) row-major,
+ * inside a phase di ascending, then dj ascending; phase coordinate 0 reaches offsets {-1, 0}, f - 1 reaches {0, 1}, any other {0}: (f + 2)^2 blocks.  The caller
+ * composes Wc [block][Cout][Cin] and bc [block][Cout] (float32, contiguous) from the two layers' parameters; vd3d_neck_poly_pack_f32 lays Wc out for the kernel in
+ * vd3d_neck_poly_weight_bytes(Cin, Cout, f) bytes (host-only; < 0: shape not built): [block][slot Cin / KS][step KS / 8][k-half 2][oc Cout][4 floats], KS = 32 (16 where
+ * Cin is no multiple of 32), channel slot KS + k-half KS / 2 + 4 step + e.  Built: (Cin, Cout, f) = (96, 128, 4), (192, 128, 2), (48, 64, 4), (96, 64, 2); every pointer
+ * 16-byte aligned; anything else is VD3D_E_UNSUPPORTED and nothing is launched. */
+int64_t vd3d_neck_poly_weight_bytes(int Cin, int Cout, int f);
+int vd3d_neck_poly_pack_f32(vd3d_ctx* ctx, const float* Wc, int Cin, int Cout, int f, void* image);
+int vd3d_neck_poly_conv_f32(vd3d_ctx* ctx, const float* x, int B, int h, int w, int Cin, const void* w_image, const float* bc, int Cout, int f, float* out);
 
 /* The reassemble stage's transposed convolutions of DPT-Large (DPTReassembleLayer.resize = ConvTranspose2d(C, C, kernel_size=s, stride=s, padding=0), s = 4 / 2):
  * kernel == stride, so the windows do not overlap and the layer is a GEMM Y[p][(i, j, co)] = sum_ci X[p][ci] W[ci][co][i][j] (vd3d_gemm_x3 with the weight

@@ -2002,6 +2002,31 @@ VD3D_EXPORT int vd3d_dpt_head_conv_f32(vd3d_ctx* c, const float* x, const float*
   HIPCHK(hipGetLastError());
   return 0;
 }
+VD3D_EXPORT int64_t vd3d_neck_poly_weight_bytes(int Cin, int Cout, int f) { return (int64_t)vd_neck_poly_weight_bytes(Cin, Cout, f); }
+VD3D_EXPORT int vd3d_neck_poly_pack_f32(vd3d_ctx* c, const float* Wc, int Cin, int Cout, int f, void* image) {
+  if (!c || !Wc || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  if (vd_neck_poly_weight_bytes(Cin, Cout, f) < 0)
+    return set_err(VD3D_E_UNSUPPORTED, "neck_poly: shape not built: %d -> %d channels, factor %d (built: 96 -> 128 and 48 -> 64 with factor 4, 192 -> 128 and 96 -> 64 with factor 2)",
+                   Cin, Cout, f);
+  if ((reinterpret_cast<uintptr_t>(image) & 15) || (reinterpret_cast<uintptr_t>(Wc) & 15))
+    return set_err(VD3D_E_UNSUPPORTED, "neck_poly: the composed weights and the weight image must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_neck_poly_pack(c->stream, Wc, Cin, Cout, f, image)) return set_err(VD3D_E_HIP, "neck_poly: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_neck_poly_conv_f32(vd3d_ctx* c, const float* x, int B, int h, int w, int Cin, const void* w_image, const float* bc, int Cout, int f, float* out) {
+  if (!c || !x || !w_image || !bc || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (!vd_neck_poly_shape_ok(B, h, w, Cin, Cout, f))
+    return set_err(VD3D_E_UNSUPPORTED, "neck_poly: shape not built: %d -> %d channels, factor %d, batch %d, %d x %d (built: 96 -> 128 and 48 -> 64 with factor 4, 192 -> 128 and "
+                   "96 -> 64 with factor 2; a batch's fine map below 2^31 pixels, its coarse map below 2^31 elements)", Cin, Cout, f, B, h, w);
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(bc) & 15) || (reinterpret_cast<uintptr_t>(out) & 15))
+    return set_err(VD3D_E_UNSUPPORTED, "neck_poly: x, the weight image, the bias blocks and the output must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_neck_poly_conv_f32(c->stream, x, B, h, w, Cin, w_image, bc, Cout, f, out)) return set_err(VD3D_E_HIP, "neck_poly: the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 VD3D_EXPORT int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* c, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out) {
   if (!c || !y || !out || B < 1 || H < 1 || W < 1 || s < 1 || C < 1) return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));

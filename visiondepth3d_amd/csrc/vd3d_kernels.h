@@ -273,6 +273,13 @@ bool vd_launch_dpt_head_conv_pack(hipStream_t s, const float* W, int Cin, int Co
 bool vd_dpt_head_conv_shape_ok(int B, int ih, int iw, int oh, int ow, int Cin, int Cout, bool tail);
 bool vd_launch_dpt_head_conv_f32(hipStream_t s, const float* x, const float* b_in, int B, int ih, int iw, int oh, int ow, int Cin, const void* wimg, int Cout,
                                  const float* b2, const float* w3, float b3, float scale, float* out);
+// vd3d_conv_poly.hip: conv3x3(convT_{k = s = f}(x) + b_t) on the coarse map in polyphase form, exact float32 (v_mfma_f32_32x32x2_f32); Wc / bc: the composed
+// (f + 2)^2 blocks [block][Cout][Cin] / [block][Cout] (depth.py neck_poly_compose)
+int vd_neck_poly_blocks(int f);
+long long vd_neck_poly_weight_bytes(int Cin, int Cout, int f);
+bool vd_launch_neck_poly_pack(hipStream_t s, const float* Wc, int Cin, int Cout, int f, void* img);
+bool vd_neck_poly_shape_ok(int B, int h, int w, int Cin, int Cout, int f);
+bool vd_launch_neck_poly_conv_f32(hipStream_t s, const float* x, int B, int h, int w, int Cin, const void* wimg, const float* bc, int Cout, int f, float* out);
 // vd3d_conv_x3.hip: the convolutions of the RIFE interpolation network on the same kernel (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
 // bias / PReLU / residual epilogue, channel slices of strided NHWC buffers); vd3d_conv_ifn.hip: the float32 glue between its blocks
 long long vd_conv_ifn_weight_bytes(int kind, int Cin, int Cout);

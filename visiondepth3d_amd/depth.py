@@ -157,6 +157,43 @@ def _is_conv(m, k, s, p):
     return m.kernel_size == (k, k) and m.stride == (s, s) and m.padding == (p, p) and m.dilation == (1, 1) and m.groups == 1
 
 
+def neck_poly_offsets(f: int):
+    """The blocks of the polyphase form of conv3x3(ConvTranspose2d(kernel = stride = f)) in the order vd3d_neck_poly_conv_f32 sums them: [(pa, pb, di, dj)], phases
+    (pa, pb) row-major, inside a phase di ascending, then dj ascending.  A fine tap dy in {-1, 0, 1} of phase coordinate a lands in coarse offset (a + dy) // f:
+    coordinate 0 reaches {-1, 0}, f - 1 reaches {0, 1}, any other {0}.  (f + 2)^2 blocks: 36 for f = 4 (2.25 per output pixel), 16 for f = 2 (4)."""
+    if int(f) != f or f < 2:
+        raise ValueError(f"neck_poly: factor {f!r}: an integer of at least 2 expected")
+    reach = [sorted({(a + d) // f for d in (-1, 0, 1)}) for a in range(f)]
+    return [(pa, pb, di, dj) for pa in range(f) for pb in range(f) for di in reach[pa] for dj in reach[pb]]
+
+
+def neck_poly_compose(wt: torch.Tensor, bt, w3: torch.Tensor, f: int, dtype=torch.float32):
+    """ConvTranspose2d(C, C, kernel_size=f, stride=f) (weight ``wt`` [C_in, C, f, f], bias ``bt`` [C] or None) followed by a bias-free 3 x 3 / padding 1 convolution
+    (``w3`` [C_out, C, 3, 3]) as one linear map on the COARSE grid -> (Wc [blocks, C_out, C_in], bc [blocks, C_out]) float32 in ``neck_poly_offsets(f)``'s order:
+        out[:, f i + pa, f j + pb] = sum over the blocks k of phase (pa, pb) whose coarse pixel (i + di, j + dj) lies inside the map of  Wc[k] @ x[:, i + di, j + dj] + bc[k]
+    Wc[k] sums W3[dy, dx] @ Wt[(pa + dy) % f, (pb + dx) % f]^T over the fine taps (dy, dx) that land in offset (di, dj) = ((pa + dy) // f, (pb + dx) // f), bc[k] sums
+    W3[dy, dx] @ bt over the same taps (a coarse pixel outside the map contributes neither: the convolution pads the fine map with zeros, not with the bias).
+    Composed in float64, rounded once to ``dtype``.  C_in x blocks / f^2 multiply-adds per output pixel and channel instead of C_in + 9 C."""
+    offs = neck_poly_offsets(f)
+    if wt.dim() != 4 or w3.dim() != 4 or tuple(wt.shape[2:]) != (f, f) or tuple(w3.shape[2:]) != (3, 3) or w3.shape[1] != wt.shape[1]:
+        raise ValueError(f"neck_poly: weights {tuple(wt.shape)} / {tuple(w3.shape)} are not [C_in, C, {f}, {f}] and [C_out, C, 3, 3]")
+    if bt is not None and tuple(bt.shape) != (wt.shape[1],):
+        raise ValueError(f"neck_poly: bias {tuple(bt.shape)} is not [{wt.shape[1]}]")
+    wt64, w364 = wt.detach().to(torch.float64), w3.detach().to(torch.float64)
+    bt64 = torch.zeros(wt.shape[1], dtype=torch.float64, device=wt.device) if bt is None else bt.detach().to(torch.float64)
+    Wc = torch.zeros(len(offs), w3.shape[0], wt.shape[0], dtype=torch.float64, device=wt.device)
+    bc = torch.zeros(len(offs), w3.shape[0], dtype=torch.float64, device=wt.device)
+    at = {o: k for k, o in enumerate(offs)}
+    for pa in range(f):
+        for pb in range(f):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    k = at[pa, pb, (pa + dy) // f, (pb + dx) // f]
+                    Wc[k] += w364[:, :, dy + 1, dx + 1] @ wt64[:, :, (pa + dy) % f, (pb + dx) % f].t()
+                    bc[k] += w364[:, :, dy + 1, dx + 1] @ bt64
+    return Wc.to(dtype).contiguous(), bc.to(dtype).contiguous()
+
+
 def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     """Patch-embedding weight [C, 3, p, p] (kernel == stride: every patch is one GEMM row) -> [C, Kp]: the flattened (c, ky, kx) columns, zero-padded from 3 p^2
     to the next multiple of 16 (vd3d_gemm_x3's K unit; p = 14: 588 -> 592).  vd3d_patchify_f32 writes the matching rows, zero tail included."""
@@ -428,7 +465,10 @@ class DepthPipe:
         size; ``conv_routes`` reads ("fp16x2" | "library", reason).  In the default float32 mode (``gemm="f32"``, ``conv=None``, with a renderer) the head's up-sampling, its second
         convolution and everything behind it run as ONE exact-float32 MFMA launch (``vd3d_dpt_head_conv_f32``: 32 | 64 | 128 -> 32 channels);
         ``conv_routes["head.conv2"]`` is then ``("f32-fused", ...)``, or ``("library", reason)`` where the three launches stay (a shape that is not
-        built, ``VD3D_HEAD_FUSED=0``).
+        built, ``VD3D_HEAD_FUSED=0``).  In the same mode (not ``self_contained``) the up-scaling reassemble stages' transposed convolution and the 3 x 3 neck
+        convolution behind it run as ONE exact-float32 MFMA launch on the coarse map (``vd3d_neck_poly_conv_f32``, composed per parameter version by
+        ``neck_poly_compose``: DA-V2-Base's and -Small's shapes); ``conv_routes["neck.reassemble_stage.layers.{0,1}.resize"]`` and ``["neck.convs.{0,1}"]`` are
+        then ``("f32-poly", ...)``, or ``("library", reason)`` (a shape that is not built, ``VD3D_NECK_POLY=0``).
         ``renderer``: a ``visiondepth3d_amd.render_3d.Renderer`` on the SAME stream as the network (default stream); when given the
         image-processor front end, the residual-add + LayerNorm pairs and the DPT up-samplings run as fused HIP launches.
         ``model`` / ``processor``: an already constructed Hugging Face depth model and its image-processor constants
@@ -828,11 +868,58 @@ class DepthPipe:
         head.forward = head_fwd
         stage = self.model.neck.reassemble_stage
 
+        # float32 mode: the up-scaling stages' ConvTranspose2d (kernel == stride == f, bias) and the bias-free 3 x 3 neck convolution behind it are one linear map;
+        # composed per parameter version on the coarse grid (neck_poly_compose) they run as ONE exact-float32 MFMA launch (vd3d_neck_poly_conv_f32) with 2.25 (f = 4) /
+        # 4 (f = 2) coarse taps per output pixel instead of 9 fine ones, and the fine map between them is never written.  VD3D_NECK_POLY=0: A/B switch back.
+        neck = self.model.neck
+        poly_on = self.gemm == "f32" and cm is None and not sc and f32 and self.device.type == "cuda"
+        poly_stages = [i for i in (0, 1) if poly_on and i < len(stage.layers) and i < len(neck.convs) and isinstance(stage.layers[i].resize, torch.nn.ConvTranspose2d)]
+        poly_img, poly_pending = {}, {}   # per stage: (parameter versions, packed blocks or None); the blocks the reassemble stage hands to neck.convs[i] in this forward
+
+        def poly_route(i):
+            rz, cv = stage.layers[i].resize, neck.convs[i]
+            if os.environ.get("VD3D_NECK_POLY", "1") == "0":
+                return None, "VD3D_NECK_POLY=0"
+            f = rz.kernel_size[0]
+            if not (rz.kernel_size == rz.stride == (f, f) and f >= 2 and rz.padding == (0, 0) and rz.output_padding == (0, 0) and rz.dilation == (1, 1) and rz.groups == 1
+                    and _is_conv(cv, 3, 1, 1) and cv.bias is None and cv.in_channels == rz.out_channels and cv.padding_mode == "zeros"):
+                return None, "not a ConvTranspose2d with kernel == stride in front of a bias-free 3 x 3 / stride 1 / padding 1 convolution"
+            ts = [t for t in (rz.weight, rz.bias, cv.weight) if t is not None]
+            try:
+                key = tuple((t.data_ptr(), t._version) for t in ts)
+            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
+                key = tuple((t.data_ptr(),) for t in ts)
+            if poly_img.get(i, (None, None))[0] != key:
+                poly_img[i] = (key, R.neck_poly_pack(*neck_poly_compose(rz.weight, rz.bias, cv.weight, f), f))   # None: shape not built
+            if poly_img[i][1] is None:
+                return None, f"shape not built: {rz.in_channels} -> {cv.out_channels} channels, factor {f}"
+            return poly_img[i][1], f"{rz.in_channels} -> {cv.out_channels} channels, factor {f}: {len(neck_poly_offsets(f))} composed blocks"
+
+        for i in poly_stages:
+            def poly_conv_fwd(x, i=i, m=neck.convs[i], rz=stage.layers[i].resize):
+                packed = poly_pending.pop(i, None)
+                if packed is None:   # the reassemble stage ran the transposed convolution itself
+                    return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
+                f = rz.kernel_size[0]
+                if self._flop_count is not None:   # what the bypassed transposed convolution's hook adds (the module graph's count; this module's own hook still runs)
+                    self._flop_count[0] += 2.0 * rz.out_channels * (f * x.shape[2]) * (f * x.shape[3]) * rz.in_channels * f * f
+                return R.neck_poly_conv(x.contiguous(memory_format=CL), packed)
+            neck.convs[i].forward = poly_conv_fwd
+
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
+            poly_pending.clear()
             for i, hs in enumerate(hidden_states):
                 B, _, Cn = hs.shape
                 x = hs[:, 1:].reshape(B, patch_height, patch_width, Cn).permute(0, 3, 1, 2)   # NHWC storage, NCHW view: channels_last
+                if i in poly_stages:
+                    packed, why = poly_route(i) if x.dtype == torch.float32 else (None, f"{x.dtype} map")
+                    route = ("f32-poly" if packed is not None else "library", why)
+                    self.conv_routes[names[id(stage.layers[i].resize)]] = self.conv_routes[names[id(neck.convs[i])]] = route
+                    if packed is not None:
+                        poly_pending[i] = packed
+                        out.append(stage.layers[i].projection(x))   # the coarse map; neck.convs[i] is the composed launch
+                        continue
                 out.append(stage.layers[i](x))
             return out
         stage.forward = self._self_contained_reassemble(names) if sc else reassemble_fwd

@@ -1185,6 +1185,38 @@ class Renderer:
                                                   _ptr(b2) if tail else None, _ptr(w3) if tail else None, float(b3), float(scale), _ptr(out)))
         return out
 
+    def neck_poly_pack(self, Wc: torch.Tensor, bc: torch.Tensor, f: int):
+        """Lay the composed blocks of ``depth.neck_poly_compose`` (Wc [blocks, Cout, Cin], bc [blocks, Cout]) out for ``neck_poly_conv`` -> (image, bc on the device,
+        Cin, Cout, f); ``None`` when (Cin, Cout, f) is not built ((96, 128, 4), (192, 128, 2), (48, 64, 4), (96, 64, 2))."""
+        f = int(f)
+        if Wc.dim() != 3 or bc.dim() != 2 or Wc.shape[0] != (f + 2) ** 2 or tuple(bc.shape) != tuple(Wc.shape[:2]):
+            raise ValueError(f"neck_poly_pack: Wc {tuple(Wc.shape)} / bc {tuple(bc.shape)} are not [{(f + 2) ** 2}, Cout, Cin] and [{(f + 2) ** 2}, Cout]")
+        Cout, Cin = int(Wc.shape[1]), int(Wc.shape[2])
+        nb = int(self._L.vd3d_neck_poly_weight_bytes(Cin, Cout, f))
+        if nb < 0:
+            return None
+        w = Wc.detach().to(self.device, torch.float32).contiguous()
+        b = bc.detach().to(self.device, torch.float32).contiguous().clone()
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(self._L.vd3d_neck_poly_pack_f32(self._ctx, _ptr(w), Cin, Cout, f, _ptr(img)))
+        return img, b, Cin, Cout, f
+
+    def neck_poly_conv(self, x, packed):
+        """conv3x3(ConvTranspose2d_{kernel = stride = f}(x) + bias) on the coarse channels_last float32 map ``x`` [B, Cin, h, w] in one exact-float32 kernel
+        (include/vd3d.h vd3d_neck_poly_conv_f32) -> channels_last [B, Cout, f h, f w]; ``packed`` = ``neck_poly_pack(...)``."""
+        self._nhwc_f32(x)
+        if packed is None:
+            raise ValueError("neck_poly_conv: the shape is not built (neck_poly_pack returned None)")
+        img, b, Cin, Cout, f = packed
+        B, Cx, h, w = x.shape
+        if Cx != Cin:
+            raise ValueError(f"neck_poly_conv: the map has {Cx} channels, the packed weights take {Cin}")
+        out = torch.empty((B, Cout, f * h, f * w), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        self._enter(x, img, b, out)
+        _lib.check(self._L.vd3d_neck_poly_conv_f32(self._ctx, _ptr(x), B, h, w, Cin, _ptr(img), _ptr(b), Cout, f, _ptr(out)))
+        return out
+
     def depth_to_space_bias(self, y, B: int, H: int, W: int, s: int, bias=None):
         """The scatter of a kernel == stride ConvTranspose2d run as a GEMM: contiguous float32 ``y`` [B*H*W, s*s*C] (columns in (i, j, c) order) ->
         channels_last [B, C, H*s, W*s] with out[b, c, y*s+i, x*s+j] = y[(b*H+y)*W+x, (i*s+j)*C+c] + bias[c] (include/vd3d.h vd3d_depth_to_space_bias_nhwc_f32)."""
