@@ -41,7 +41,8 @@ extern "C" {
  *    vd3d_resize_pil_bicubic_u8, vd3d_depth_preprocess_pil (DepthPipe(front_end="pil")), vd3d_dpt_head_tail_act_f32 (the sigmoid tail of the metric
  *    Depth-Anything heads under DepthPipe(self_contained=True)), vd3d_im2col_nhwc_f32, vd3d_maxpool3x3_s2_nhwc_f32, vd3d_groupnorm_nhwc_f32_workspace_bytes and
  *    vd3d_groupnorm_nhwc_f32: the BiT prefix of DPT-Hybrid under DepthPipe(self_contained=True), vd3d_neck_poly_weight_bytes, vd3d_neck_poly_pack_f32 and
- *    vd3d_neck_poly_conv_f32 (the float32 neck's transposed convolution + 3 x 3 convolution in polyphase form). */
+ *    vd3d_neck_poly_conv_f32 (the float32 neck's transposed convolution + 3 x 3 convolution in polyphase form), vd3d_depthpro_preprocess_u8
+ *    and vd3d_depthpro_post_f32 (DepthPro's image-processor front end and post-process). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -754,6 +755,21 @@ enum { VD3D_GN_RELU = 1 };
 int64_t vd3d_groupnorm_nhwc_f32_workspace_bytes(int B, int64_t P, int C, int G);
 int vd3d_groupnorm_nhwc_f32(vd3d_ctx* ctx, const float* x, const float* residual_or_null, const float* gamma, const float* beta, float eps, int flags, int B,
                             int64_t P, int C, int G, void* workspace, int64_t workspace_bytes, float* out);
+
+/* ---- DepthPro (transformers' DepthProForDepthEstimation; visiondepth3d_amd/depth_pro.py states both in torch).  "ATen's bilinear" below is
+ * F.interpolate(mode="bilinear", align_corners=False, antialias=False) with a size given: equal sizes are the identity; otherwise scale = float(in) / out,
+ * src = max(scale (d + 0.5) - 0.5, 0), i0 = min(floor(src), in - 1), l1 = clamp(src - i0, 0, 1), i1 = i0 + (i0 < in - 1), l0 = 1 - l1 and
+ * out = l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11), every operation rounded to float32 on its own.  Every refusal is VD3D_E_UNSUPPORTED with a message,
+ * and nothing is launched.
+ *
+ * DepthProImageProcessor: frames_bgr uint8 [B][H][W][3] -> out float32 planar [B][3][S][S] in R, G, B order.  Rescale and normalise first -- a table of the byte,
+ * (float(v) - 255 mean[c]) / (255 std[c]), a subtraction and a division -- then ATen's bilinear of the float image.  mean_host / std_host: 3 floats each, R, G, B.
+ * S a multiple of 4, out 16-byte aligned, every side 1 .. 2^20, std non-zero. */
+int vd3d_depthpro_preprocess_u8(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B, int H, int W, int S, const float* mean_host, const float* std_host, float* out);
+/* DepthProImageProcessor.post_process_depth_estimation: pred float32 [B][S][S] -> out [B][oH][oW] = 1 / clamp(resize(pred * oW / focal), 1e-4, 1e4), with
+ * focal = 0.5 oW / tan(0.5 deg2rad(fov[b])) -- fov_or_null: the model's field of view in degrees, float32 [B] in DEVICE memory (no host synchronisation), NULL:
+ * no scaling -- resize = ATen's bilinear, skipped for oH == oW == S.  tan is evaluated in float64 and narrowed to float32 (within 1 ulp; the narrowing is a second rounding).  NaN stays NaN. */
+int vd3d_depthpro_post_f32(vd3d_ctx* ctx, const float* pred, const float* fov_or_null, int B, int S, int oH, int oW, float* out);
 
 /* ---- preview visualisers: generate_preview_image, core/preview_utils.py:23-84, the exactly defined types.
  * left / right: uint8 BGR [h][w][3] eyes (outputs of vd3d_pixel_shift).  out: [h][w][3], except HSBS: [h][2*(w/2)][3].

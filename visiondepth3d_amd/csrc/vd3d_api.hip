@@ -2081,6 +2081,33 @@ VD3D_EXPORT int vd3d_groupnorm_nhwc_f32(vd3d_ctx* c, const float* x, const float
   return 0;
 }
 
+// ---- DepthPro (vd3d_depthpro.hip): every refusal below returns before anything is launched
+#define DP_ALIGN16(p) ((reinterpret_cast<uintptr_t>(p) & 15) == 0)
+VD3D_EXPORT int vd3d_depthpro_preprocess_u8(vd3d_ctx* c, const uint8_t* frames_bgr, int B, int H, int W, int S, const float* mean_host, const float* std_host, float* out) {
+  if (!c || !frames_bgr || !mean_host || !std_host || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || H < 1 || W < 1 || S < 4 || S % 4)
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_preprocess: batch %d, frame %d x %d and side %d: at least one frame and one pixel, the side a multiple of 4", B, H, W, S);
+  if (H > (1 << 20) || W > (1 << 20) || S > (1 << 20)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_preprocess: a side past 2^20 (%d x %d -> %d)", H, W, S);
+  for (int i = 0; i < 3; ++i)
+    if (!(std_host[i] != 0.f)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_preprocess: std[%d] is zero or NaN", i);
+  if (!DP_ALIGN16(out)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_preprocess: the output must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depthpro_preprocess_u8(c->stream, frames_bgr, B, H, W, S, mean_host, std_host, out)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_preprocess: too many pixels for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_depthpro_post_f32(vd3d_ctx* c, const float* pred, const float* fov_or_null, int B, int S, int oH, int oW, float* out) {
+  if (!c || !pred || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || S < 1 || oH < 1 || oW < 1 || S > (1 << 20) || oH > (1 << 20) || oW > (1 << 20))
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_post: empty shape or a side past 2^20: batch %d, prediction %d x %d, output %d x %d", B, S, S, oH, oW);
+  if ((reinterpret_cast<uintptr_t>(pred) & 3) || (reinterpret_cast<uintptr_t>(out) & 3) || (reinterpret_cast<uintptr_t>(fov_or_null) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_post: the prediction, the field of view and the output must be 4-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depthpro_post_f32(c->stream, pred, fov_or_null, B, S, oH, oW, out)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_post: too many pixels for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 VD3D_EXPORT int vd3d_preview_image(vd3d_ctx* c, int type, const uint8_t* left_bgr, const uint8_t* right_bgr, int h, int w, uint8_t* out_bgr) {
   if (!c || !left_bgr || !right_bgr || !out_bgr || h < 1 || w < 1) return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));

@@ -309,6 +309,9 @@ bool vd_launch_maxpool3x3_s2_nhwc_f32(hipStream_t s, const float* x, int B, int 
 long long vd_groupnorm_workspace_bytes(int B, long long P, int C, int G);   // < 0: shape not built
 bool vd_launch_groupnorm_nhwc_f32(hipStream_t s, const float* x, const float* res, const float* gamma, const float* beta, float eps, int relu, int B, long long P, int C,
                                   int G, void* ws, float* out);
+// ---- vd3d_depthpro.hip: DepthPro's front end and post-process (the C entry points check shapes and alignment; false = a grid too large)
+bool vd_launch_depthpro_preprocess_u8(hipStream_t s, const uint8_t* frames, int B, int H, int W, int S, const float mean[3], const float std[3], float* out);
+bool vd_launch_depthpro_post_f32(hipStream_t s, const float* pred, const float* fov, int B, int S, int oH, int oW, float* out);
 // ---- vd3d_handoff.hip
 // form: 0 = the library's choice (the separable kernel for up-scaling), 1 = the general kernel, 2 = the separable kernel (false where it does not apply)
 bool vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,

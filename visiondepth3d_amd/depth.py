@@ -50,6 +50,9 @@ MODEL_ZOO = {
     # Intel/dpt-hybrid-midas ("MiDaS 3.0"): ViT-B/16 behind a BiT ResNet-50 prefix (stages 1 - 3, weight-standardised convolutions, GroupNorm(32)); hooks 0 / 1 are the
     # prefix's stage-1 / stage-2 maps and go to the neck as they are (neck_ignore_stages), hooks 2 / 3 are ViT layers 8 / 11 through the "project" readout
     "dpt-hybrid-midas": dict(arch="dpt", hybrid=True, hidden=768, layers=12, heads=12, out_indices=[2, 5, 8, 11], neck=[256, 512, 768, 768], fusion=256),
+    # apple/DepthPro-hf (DepthProForDepthEstimation): three DINOv2 ViT-L/16 encoders (image, patch, field of view) at 384 x 384 over a 1 + 9 + 25 patch pyramid of
+    # the 1536 x 1536 input; depth_pro.py states the geometry (as far as it is known here) and the processor
+    "depth-pro": dict(arch="depth_pro", hidden=1024, layers=24, heads=16, fusion=256),
 }
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -58,12 +61,17 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 PROCESSORS = {
     "da": dict(size=(518, 518), keep_aspect_ratio=True, multiple=14, mean=IMAGENET_MEAN, std=IMAGENET_STD),
     "dpt": dict(size=(384, 384), keep_aspect_ratio=False, multiple=1, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)),
+    # DepthProImageProcessor: 1536 x 1536, no aspect keeping, BILINEAR (PIL resample 2) without antialias AFTER rescale + normalise, mean = std = 0.5
+    "depth_pro": dict(size=(1536, 1536), keep_aspect_ratio=False, multiple=1, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), resample=2),
 }
 
 
 def build_config(name: str):
     from transformers import DepthAnythingConfig, Dinov2Config
     z = MODEL_ZOO[name]
+    if z["arch"] == "depth_pro":
+        from . import depth_pro
+        return depth_pro.config()
     if z["arch"] == "dpt":
         from transformers import DPTConfig
         if z.get("hybrid"):   # the published config.json of Intel/dpt-hybrid-midas
@@ -437,6 +445,16 @@ class DepthPipe:
         one launch of ``vd3d_depth_preprocess_pil`` (two with an inference size); on the CPU, and for a geometry past the kernel's tap budget, the
         integer statement ``pil_resample.pixel_values`` gives the same values.  ``front_end_route`` ("kernel" | "statement") says which ran last.
         The mode takes uint8 frames only (TypeError otherwise).  Any other value of the keyword raises ValueError.
+        DepthPro (``"depth-pro"``, ``DepthProForDepthEstimation``: apple/DepthPro-hf; ``depth_pro.py`` states the geometry as far as it is known here): ``__call__``,
+        ``infer_bgr_u8``, ``depth_frames_u8`` and ``at_inference_size`` give what ``pipeline("depth-estimation")`` gives -- the processor's own order (rescale and normalise,
+        THEN a bilinear resize without antialias to 1536 x 1536: ``front_end="float"``; ``"pil"`` is refused by name, there is no Pillow pass in this processor), the
+        model, and the processor's post-process at the size the pipeline saw: depth x width / focal from the model's field of view, bilinear resize, 1 / clamp(depth,
+        1e-4, 1e4).  With a renderer both ends are one launch each (``vd3d_depthpro_preprocess_u8`` for uint8 frames without an ``inference_size`` -- with one, or for
+        other frame types, the front end runs as ATen operators and ``front_end_route`` reads "statement" instead of "kernel"; ``vd3d_depthpro_post_f32``, the field of
+        view never leaves the device); on the CPU the same arithmetic runs in ATen.  ``raw=True`` returns the MODEL-RESOLUTION inverse depth (scale for the model's width, clamp, reciprocal,
+        no resize) -- a deviation: the pipeline resizes before the reciprocal.  A model without the field-of-view branch is not scaled.  The network itself runs its
+        stock float32 graph: ``gemm="bf16x3"`` / ``"fp16x2"`` and ``self_contained=True`` refuse DepthPro by name (the rewrite is not built), and so does tiled depth
+        (its blend evaluates a bicubic post-process); ``bars=`` consumes the uint8 planes and works unchanged.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
         GEMMs and the attention (64-wide heads) is the library's exact-float32 kernel (``vd3d_attention_f32``: both products on the float32-input
         matrix cores, float32 online softmax); ``"bf16x3"`` -- OPT-IN: the library's own split-bf16 GEMM (``vd3d_gemm_x3``: every float32 operand exactly split into three bf16
@@ -534,14 +552,25 @@ class DepthPipe:
             raise TypeError("DepthPipe runs in float32 (reference precision) or bfloat16")
         if model is None:
             cfg = build_config(name)
-            if MODEL_ZOO[name]["arch"] == "dpt":
+            if MODEL_ZOO[name]["arch"] == "depth_pro":
+                from transformers import DepthProForDepthEstimation as Net
+            elif MODEL_ZOO[name]["arch"] == "dpt":
                 from transformers import DPTForDepthEstimation as Net
             else:
                 from transformers import DepthAnythingForDepthEstimation as Net
             model = Net(cfg).eval()
             synthetic_weights_(model, seed)
             processor = processor or PROCESSORS[MODEL_ZOO[name]["arch"]]
-        self.arch = "da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "generic"
+        self.arch = {"DepthAnythingForDepthEstimation": "da", "DepthProForDepthEstimation": "depth_pro"}.get(type(model).__name__, "generic")
+        if self.arch == "depth_pro":
+            if front_end == "pil":   # the processor is no Pillow resize: it normalises first and resizes the FLOAT image (torchvision, no antialias)
+                raise NotImplementedError(f"front_end='pil': {name!r} (DepthProForDepthEstimation) -- DepthProImageProcessor rescales and normalises first and resizes the float "
+                                          "tensor bilinearly without antialias; there is no 8-bit Pillow pass to reproduce, front_end='float' IS the processor's own order")
+            if gemm != "f32" or self_contained:   # refused by name before the renderer or a device is touched
+                self.model = model
+                self._split_scope(fuse_backbone)
+            if processor is None:
+                processor = PROCESSORS["depth_pro"]
         if self.self_contained:   # refused here, by name, on the module graph as it was handed in: no renderer call, nothing moved to a device yet
             self.model = model
             scope = self._split_scope(fuse_backbone)
@@ -623,7 +652,8 @@ class DepthPipe:
         if not os.path.isdir(path):
             raise FileNotFoundError(f"{path}: not a local checkpoint folder (this build environment has no network)")
         model = AutoModelForDepthEstimation.from_pretrained(path, local_files_only=True)
-        proc = dict(PROCESSORS["da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "dpt"])
+        pro = type(model).__name__ == "DepthProForDepthEstimation"
+        proc = dict(PROCESSORS["da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "depth_pro" if pro else "dpt"])
         pc = os.path.join(path, "preprocessor_config.json")
         if os.path.exists(pc):
             with open(pc) as f:
@@ -639,7 +669,10 @@ class DepthPipe:
                 proc["mean"] = tuple(float(v) for v in j["image_mean"])
             if j.get("image_std") is not None:
                 proc["std"] = tuple(float(v) for v in j["image_std"])
-            if int(j.get("resample", 3)) != 3:
+            if pro:   # DepthProImageProcessor: bilinear (PIL resample 2) on the normalised float image, the one processor built with that filter
+                if int(j.get("resample", 2)) != 2 or not all(j.get(k, True) for k in ("do_resize", "do_rescale", "do_normalize")):
+                    raise NotImplementedError("a DepthPro image processor other than rescale + normalise + bilinear resize (PIL resample 2) is not built")
+            elif int(j.get("resample", 3)) != 3:
                 raise NotImplementedError("image processors other than bicubic (PIL resample 3) are not built")
         return cls(os.path.basename(os.path.normpath(path)), device=device, dtype=dtype, model=model, processor=proc, **kw)
 
@@ -1238,6 +1271,10 @@ class DepthPipe:
         tag = "self_contained=True" if self.self_contained else f"gemm={self.gemm!r}"
         if self.arch == "da" and type(m.backbone).__name__ == "Dinov2Backbone" and fuse_backbone:
             return "dinov2"
+        if type(m).__name__ == "DepthProForDepthEstimation":
+            raise NotImplementedError(f"{tag}: {what} -- DepthPro runs its stock float32 graph between the own front end and post-process (gemm='f32'); the split-mode "
+                                      "rewrite of its three encoders, neck, fusion stage, head and field-of-view branch is not built -- nothing is substituted "
+                                      "silently")
         if type(m).__name__ != "DPTForDepthEstimation" or not fuse_backbone:
             raise NotImplementedError(f"{tag}: {what} -- the split modes rewrite the fused DINOv2 backbone (Depth-Anything V1 / V2, Distill-Any-Depth) and the "
                                       "plain-ViT DPT (DPT-Large), with fuse_backbone=True; this model runs its stock float32 graph -- nothing is substituted silently")
@@ -1394,6 +1431,8 @@ class DepthPipe:
             oH, oW = int(inference_size[1]), int(inference_size[0])
         else:
             oH, oW = H, W
+        if self.arch == "depth_pro":
+            return self._infer_depth_pro(frames_bgr, inference_size, raw, oH, oW)
         if self.front_end == "pil":
             pred = self.model(pixel_values=self._pil_pixel_values(frames_bgr, inference_size)).predicted_depth
             if raw:
@@ -1427,6 +1466,37 @@ class DepthPipe:
             return pred.float()
         pred = F.interpolate(pred.float().unsqueeze(1), size=(oH, oW), mode="bicubic", align_corners=False).squeeze(1)
         return pred
+
+    def _infer_depth_pro(self, frames_bgr, inference_size, raw, oH, oW):
+        """infer_bgr_u8 for DepthProForDepthEstimation: the processor (rescale + normalise, THEN the bilinear resize without antialias to 1536 x 1536), the model,
+        and DepthProImageProcessor.post_process_depth_estimation at the size the pipeline saw -- depth * width / focal from the model's field of view (when it has
+        that branch), bilinear resize, 1 / clamp(depth, 1e-4, 1e4).  With a renderer the post-process is one launch (vd3d_depthpro_post_f32; the field of
+        view stays on the device) and, for uint8 frames without an inference size, so is the front end (vd3d_depthpro_preprocess_u8).  With an ``inference_size`` (the
+        pre-resize hands the processor non-integer pixels) or non-uint8 frames the front end is depth_pro.preprocess_statement, the same arithmetic as ATen operators on
+        the device, and without a renderer so is the post-process (post_statement).  ``front_end_route`` ("kernel" | "statement") says which front end ran last.
+        ``raw``: the model-resolution inverse depth, scaled for the model's own width and not resized (the pipeline resizes BEFORE the reciprocal)."""
+        from . import depth_pro
+        size = tuple(int(v) for v in self.proc["size"])
+        if size[0] != size[1]:
+            raise NotImplementedError(f"depth-pro: a processor size of {size} -- DepthPro takes square inputs")
+        f = frames_bgr.to(self.device)
+        if self.renderer is not None and inference_size is None and f.dtype == torch.uint8:
+            x = self.renderer.depthpro_preprocess(f, size[0], self.proc["mean"], self.proc["std"])
+            self.front_end_route = "kernel"
+        else:
+            self.front_end_route = "statement"
+            if inference_size is not None:   # hf_batch_safe_pipe: img.resize(inference_size, BICUBIC) first (:1113-1116), in its float statement as for every model
+                f = F.interpolate(f.flip(-1).permute(0, 3, 1, 2).float(), size=(int(inference_size[1]), int(inference_size[0])), mode="bicubic", antialias=True,
+                                  align_corners=False).clamp_(0, 255).permute(0, 2, 3, 1).flip(-1)
+            x = depth_pro.preprocess_statement(f, size, self.proc["mean"], self.proc["std"])
+        out = self.model(pixel_values=x.to(self.dtype))
+        pred = out.predicted_depth.float().contiguous()
+        fov = None if out.field_of_view is None else out.field_of_view.float()
+        if raw:
+            oH = oW = pred.shape[-1]
+        if self.renderer is not None:
+            return self.renderer.depthpro_post(pred, fov, oH, oW)
+        return depth_pro.post_statement(pred, fov, oH, oW, resize=not raw)
 
     @torch.no_grad()
     def depth_frames_u8(self, frames_bgr: torch.Tensor, inference_size=None, invert: bool = False, tiled: bool = False, tile: int = 512,
@@ -1490,6 +1560,9 @@ class DepthPipe:
         replaces the network."""
         if self.renderer is None:
             raise RuntimeError("infer_tiled_bgr_u8 needs DepthPipe(renderer=...): the tile gather and blend are HIP kernels")
+        if self.arch == "depth_pro" and model_call is None:
+            raise NotImplementedError(f"tiled depth: {self.name!r} (DepthProForDepthEstimation) -- the tile blend evaluates the pipeline's BICUBIC post-process of every tile; "
+                                      "DepthPro's is a bilinear resize followed by a reciprocal -- not built")
         from .depth_tiles import tile_plan
         R = self.renderer
         f = frames_bgr.to(self.device)
@@ -1556,6 +1629,8 @@ class DepthPipe:
     def flops_per_frame(self, h: int, w: int) -> float:
         """Dense-GEMM flop estimate for MFMA accounting: 2*params_linear*tokens + 4*T^2*d per layer
         for the backbone, the EXECUTED convolution flops of the DPT neck / head counted during one forward."""
+        if self.arch == "depth_pro":
+            raise NotImplementedError(f"flops_per_frame: {self.name!r} (DepthProForDepthEstimation) -- the estimate is not built for the three-encoder patch pyramid")
         th, tw = self.resize_target(h, w)
         bcfg = getattr(self.model.config, "backbone_config", None) or self.model.config
         if not hasattr(bcfg, "patch_size"):   # DPT-Hybrid: the backbone configuration is the BiT prefix's; the transformer is the model's own

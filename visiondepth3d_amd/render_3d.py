@@ -1303,6 +1303,38 @@ class Renderer:
                                                    _abi.GN_RELU if relu else 0, B, H * W, Cc, int(groups), _ptr(ws), nb, _ptr(out)))
         return out
 
+    # ---- DepthPro (vd3d_depthpro.hip; depth_pro.py holds the statements)
+    def depthpro_preprocess(self, frames_bgr: torch.Tensor, size: int, mean, std) -> torch.Tensor:
+        """DepthProImageProcessor in one launch: uint8 BGR [B, H, W, 3] -> contiguous float32 pixel_values [B, 3, size, size] -- rescale and normalise as a
+        table of the byte, then the bilinear resize without antialias (include/vd3d.h vd3d_depthpro_preprocess_u8; ``depth_pro.preprocess_statement``)."""
+        f = frames_bgr.to(self.device)
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+            raise TypeError("depthpro_preprocess takes uint8 [B,H,W,3] BGR frames")
+        f = f.contiguous()
+        B, H, W, _ = f.shape
+        out = torch.empty((B, 3, int(size), int(size)), dtype=torch.float32, device=self.device)
+        m = (C.c_float * 3)(*[float(v) for v in mean]); s = (C.c_float * 3)(*[float(v) for v in std])
+        self._enter(f, out)
+        _lib.check(self._L.vd3d_depthpro_preprocess_u8(self._ctx, _ptr(f), B, H, W, int(size), m, s, _ptr(out)))
+        return out
+
+    def depthpro_post(self, pred: torch.Tensor, fov, oH: int, oW: int, out=None) -> torch.Tensor:
+        """DepthPro's post-process in one launch: float32 [B, S, S] and the field of view (float32 [B] on the device, degrees, or None) -> inverse depth
+        [B, oH, oW]: scale by oW / focal, bilinear resize (skipped for oH == oW == S), clamp to [1e-4, 1e4], reciprocal.  The field of view is read by the
+        kernel: no host synchronisation (include/vd3d.h vd3d_depthpro_post_f32; ``depth_pro.post_statement``)."""
+        if pred.dtype != torch.float32 or pred.dim() != 3 or pred.shape[1] != pred.shape[2] or not pred.is_contiguous():
+            raise ValueError("depthpro_post: a contiguous float32 [B, S, S] prediction expected")
+        B, S, _ = pred.shape
+        if fov is not None:
+            fov = fov.to(pred.device, torch.float32).reshape(-1).contiguous()
+            if fov.numel() != B:
+                raise ValueError("depthpro_post: one field of view per frame expected")
+        if out is None:
+            out = torch.empty((B, int(oH), int(oW)), dtype=torch.float32, device=pred.device)
+        self._enter(pred, fov, out)
+        _lib.check(self._L.vd3d_depthpro_post_f32(self._ctx, _ptr(pred), _ptr(fov) if fov is not None else None, B, S, int(oH), int(oW), _ptr(out)))
+        return out
+
     def detect_black_bars(self, frame_bgr: torch.Tensor):
         """detect_black_bars(frame_to_tensor(frame)) (core/render_3d.py:293-316) on a uint8 BGR frame -> (top, bottom)."""
         f = frame_bgr.to(self.device, torch.uint8).contiguous()
