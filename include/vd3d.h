@@ -42,7 +42,8 @@ extern "C" {
  *    Depth-Anything heads under DepthPipe(self_contained=True)), vd3d_im2col_nhwc_f32, vd3d_maxpool3x3_s2_nhwc_f32, vd3d_groupnorm_nhwc_f32_workspace_bytes and
  *    vd3d_groupnorm_nhwc_f32: the BiT prefix of DPT-Hybrid under DepthPipe(self_contained=True), vd3d_neck_poly_weight_bytes, vd3d_neck_poly_pack_f32 and
  *    vd3d_neck_poly_conv_f32 (the float32 neck's transposed convolution + 3 x 3 convolution in polyphase form), vd3d_depthpro_preprocess_u8
- *    and vd3d_depthpro_post_f32 (DepthPro's image-processor front end and post-process). */
+ *    and vd3d_depthpro_post_f32 (DepthPro's image-processor front end and post-process), vd3d_head_upconv_gather_f32 (the fine half of the float32 head's
+ *    first convolution as coarse GEMM + fine gather). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -709,6 +710,17 @@ int vd3d_dpt_head_conv_f32(vd3d_ctx* ctx, const float* x, const float* b_in, int
 int64_t vd3d_neck_poly_weight_bytes(int Cin, int Cout, int f);
 int vd3d_neck_poly_pack_f32(vd3d_ctx* ctx, const float* Wc, int Cin, int Cout, int f, void* image);
 int vd3d_neck_poly_conv_f32(vd3d_ctx* ctx, const float* x, int B, int h, int w, int Cin, const void* w_image, const float* bc, int Cout, int f, float* out);
+
+/* The fine half of conv3x3(upsample_bilinear(conv1x1(x) + b_p)) (the last fusion layer's projection, the align_corners up-sampling and the head's bias-free 3 x 3 /
+ * padding 1 convolution: all linear, so all channel mixing is ONE GEMM on the coarse map, Z[b][i][j][t][o] = sum_c (W_t P)[o][c] x[b][i][j][c] + (W_t b_p)[o] for
+ * the 9 taps t = 3 ky + kx, which the caller runs):
+ *     out[b][Y][X][o] = sum over t = 0 .. 8 ascending with (Y + ky - 1, X + kx - 1) inside [0, H) x [0, W) of bilinear(Z[b][:][:][t][o]; Y + ky - 1, X + kx - 1)
+ * Z float32 [B][h][w][9][Cout] -> out float32 NHWC [B][H][W][Cout], the convolution WITHOUT its bias.  Coordinates as vd3d_upsample_bilinear_nhwc's float32 path
+ * (s = (float)(h - 1) / (float)(H - 1), f = s * (float)y, truncation, the < h - 1 clamp, l1 = f - (float)i0, l0 = 1.f - l1); per tap the corner weights ly * lx are
+ * rounded products and every value is one fmaf chain from 0 in the order taps ascending, corners (y0, x0), (y0, x1), (y1, x0), (y1, x1), summed by one lane: no
+ * atomics, bits depend neither on the batch nor on the call.  Built: Cout = 64 | 32; H, W >= 2 (any size, not only 2 h x 2 w; a down-sampling factor above about
+ * 9 is refused); both pointers 16-byte aligned; anything else is VD3D_E_UNSUPPORTED and nothing is launched. */
+int vd3d_head_upconv_gather_f32(vd3d_ctx* ctx, const float* z, int B, int h, int w, int H, int W, int Cout, float* out);
 
 /* The reassemble stage's transposed convolutions of DPT-Large (DPTReassembleLayer.resize = ConvTranspose2d(C, C, kernel_size=s, stride=s, padding=0), s = 4 / 2):
  * kernel == stride, so the windows do not overlap and the layer is a GEMM Y[p][(i, j, co)] = sum_ci X[p][ci] W[ci][co][i][j] (vd3d_gemm_x3 with the weight

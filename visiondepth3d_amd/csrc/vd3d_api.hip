@@ -2027,6 +2027,18 @@ VD3D_EXPORT int vd3d_neck_poly_conv_f32(vd3d_ctx* c, const float* x, int B, int 
   HIPCHK(hipGetLastError());
   return 0;
 }
+VD3D_EXPORT int vd3d_head_upconv_gather_f32(vd3d_ctx* c, const float* z, int B, int h, int w, int H, int W, int Cout, float* out) {
+  // the shape first: a refusal needs neither a context nor a device
+  if (!vd_head_upconv_shape_ok(B, h, w, H, W, Cout))
+    return set_err(VD3D_E_UNSUPPORTED, "head_upconv: shape not built: %d output channels, batch %d, %d x %d -> %d x %d (built: 64 and 32 channels; an output of at least "
+                   "2 x 2; a coarse row below 2^31 elements; a down-sampling factor of at most about 9)", Cout, B, h, w, H, W);
+  if (!c || !z || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if ((reinterpret_cast<uintptr_t>(z) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return set_err(VD3D_E_UNSUPPORTED, "head_upconv: Z and the output must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_head_upconv_gather_f32(c->stream, z, B, h, w, H, W, Cout, out)) return set_err(VD3D_E_HIP, "head_upconv: the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 VD3D_EXPORT int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* c, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out) {
   if (!c || !y || !out || B < 1 || H < 1 || W < 1 || s < 1 || C < 1) return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));

@@ -280,6 +280,10 @@ long long vd_neck_poly_weight_bytes(int Cin, int Cout, int f);
 bool vd_launch_neck_poly_pack(hipStream_t s, const float* Wc, int Cin, int Cout, int f, void* img);
 bool vd_neck_poly_shape_ok(int B, int h, int w, int Cin, int Cout, int f);
 bool vd_launch_neck_poly_conv_f32(hipStream_t s, const float* x, int B, int h, int w, int Cin, const void* wimg, const float* bc, int Cout, int f, float* out);
+// vd3d_head_upconv.hip: the fine half of conv3x3(up(conv1x1(h) + b)) as coarse GEMM + fine gather: Z [B][h][w][9][Cout] (depth.py head_upconv_compose) -> the 9 taps'
+// bilinear samples summed per fine pixel, NHWC [B][H][W][Cout]
+bool vd_head_upconv_shape_ok(int B, int h, int w, int H, int W, int Cout);
+bool vd_launch_head_upconv_gather_f32(hipStream_t s, const float* z, int B, int h, int w, int H, int W, int Cout, float* out);
 // vd3d_conv_x3.hip: the convolutions of the RIFE interpolation network on the same kernel (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
 // bias / PReLU / residual epilogue, channel slices of strided NHWC buffers); vd3d_conv_ifn.hip: the float32 glue between its blocks
 long long vd_conv_ifn_weight_bytes(int kind, int Cin, int Cout);

@@ -202,6 +202,30 @@ def neck_poly_compose(wt: torch.Tensor, bt, w3: torch.Tensor, f: int, dtype=torc
     return Wc.to(dtype).contiguous(), bc.to(dtype).contiguous()
 
 
+HEAD_UPCONV_BUILT = ((128, 64), (64, 32))   # (C, C_out) of head.conv1 that vd3d_head_upconv_gather_f32 builds and the probe cleared (profiles/r26_head_upconv.md)
+
+
+def head_upconv_compose(proj_w: torch.Tensor, proj_b, conv1_w: torch.Tensor, dtype=torch.float32):
+    """A 1 x 1 projection (weight ``proj_w`` [C, C_in, 1, 1] or [C, C_in], bias ``proj_b`` [C] or None), a bilinear up-sampling and a bias-free 3 x 3 convolution
+    (``conv1_w`` [C_out, C, 3, 3], zero padding) have nothing non-linear between them, the up-sampling U acts per channel and a tap's matrix W_t per pixel:
+        conv1(U(P h + b_p)) = sum over the 9 taps t of  S_t U ( (W_t P) h + W_t b_p )           (S_t: the tap's shift on the fine grid, zero outside it)
+    -> (Wc [9 * C_out, C_in], bc [9 * C_out]): tap t = 3 ky + kx, channel t * C_out + o,
+        Wc[t * C_out + o, i] = sum_c conv1_w[o, c, ky, kx] proj_w[c, i],      bc[t * C_out + o] = sum_c conv1_w[o, c, ky, kx] proj_b[c]
+    (folding W_t b_p into the coarse map relies on the interpolation weights summing to one).  Composed in float64, rounded once to ``dtype``.  The coarse GEMM
+    Z = h Wc^T + bc has a quarter of the fine map's pixels: 9 C_in multiply-adds per coarse pixel and channel instead of C_in per coarse and 9 C per fine one."""
+    if conv1_w.dim() != 4 or tuple(conv1_w.shape[2:]) != (3, 3):
+        raise ValueError(f"head_upconv: convolution weight {tuple(conv1_w.shape)} is not [C_out, C, 3, 3]")
+    Co, Cm = int(conv1_w.shape[0]), int(conv1_w.shape[1])
+    if proj_w.dim() not in (2, 4) or proj_w.shape[0] != Cm or (proj_w.dim() == 4 and tuple(proj_w.shape[2:]) != (1, 1)):
+        raise ValueError(f"head_upconv: projection weight {tuple(proj_w.shape)} is not [{Cm}, C_in, 1, 1]")
+    if proj_b is not None and tuple(proj_b.shape) != (Cm,):
+        raise ValueError(f"head_upconv: projection bias {tuple(proj_b.shape)} is not [{Cm}]")
+    P = proj_w.detach().to(torch.float64).reshape(Cm, -1)
+    W = conv1_w.detach().to(torch.float64).permute(2, 3, 0, 1).reshape(9, Co, Cm)   # [t = 3 ky + kx][o][c]
+    b = torch.zeros(Cm, dtype=torch.float64, device=P.device) if proj_b is None else proj_b.detach().to(torch.float64)
+    return (W @ P).reshape(9 * Co, -1).to(dtype).contiguous(), (W @ b).reshape(9 * Co).to(dtype).contiguous()
+
+
 def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     """Patch-embedding weight [C, 3, p, p] (kernel == stride: every patch is one GEMM row) -> [C, Kp]: the flattened (c, ky, kx) columns, zero-padded from 3 p^2
     to the next multiple of 16 (vd3d_gemm_x3's K unit; p = 14: 588 -> 592).  vd3d_patchify_f32 writes the matching rows, zero tail included."""
@@ -487,6 +511,9 @@ class DepthPipe:
         convolution behind it run as ONE exact-float32 MFMA launch on the coarse map (``vd3d_neck_poly_conv_f32``, composed per parameter version by
         ``neck_poly_compose``: DA-V2-Base's and -Small's shapes); ``conv_routes["neck.reassemble_stage.layers.{0,1}.resize"]`` and ``["neck.convs.{0,1}"]`` are
         then ``("f32-poly", ...)``, or ``("library", reason)`` (a shape that is not built, ``VD3D_NECK_POLY=0``).
+        There too the last fusion layer's biased 1 x 1 projection, its up-sampling and ``head.conv1`` run as one library GEMM on the coarse map (``head_upconv_compose``:
+        C -> 9 C_out channels) and ``vd3d_head_upconv_gather_f32`` on the fine one; ``conv_routes["neck.fusion_stage.layers.<last>.projection"]`` and ``["head.conv1"]`` are
+        then ``("f32-upconv", ...)``, or ``("library", reason)`` (a shape that is not built, ``VD3D_HEAD_UPCONV=0``).
         ``renderer``: a ``visiondepth3d_amd.render_3d.Renderer`` on the SAME stream as the network (default stream); when given the
         image-processor front end, the residual-add + LayerNorm pairs and the DPT up-samplings run as fused HIP launches.
         ``model`` / ``processor``: an already constructed Hugging Face depth model and its image-processor constants
@@ -813,6 +840,12 @@ class DepthPipe:
             y = conv_nb(unit.convolution2, y)
             return R.bias_act(y, unit.convolution2.bias, r1=x, r2=extra, want_relu_copy=want_relu)
 
+        # float32 mode: the LAST fusion layer's projection, its up-sampling and head.conv1 as coarse GEMM + fine gather (head_upconv_compose).  "route": set below
+        # where the route exists; "armed": inside the model's own forward, where the head consumes the neck's output (the neck called alone materialises the
+        # up-sampled projection as ever); "pending": what the last fusion layer hands to head_fwd in this forward.
+        upconv = {"route": None, "armed": False, "pending": None}
+        last_fusion = self.model.neck.fusion_stage.layers[-1]
+
         for layer in self.model.neck.fusion_stage.layers:
             def fusion_fwd(hidden_state, residual=None, size=None, layer=layer):
                 fused = f32 and hidden_state.dtype == torch.float32 and hidden_state.shape[1] % 4 == 0
@@ -830,6 +863,12 @@ class DepthPipe:
                 tgt = (2 * hidden_state.shape[2], 2 * hidden_state.shape[3]) if size is None else tuple(size)
                 if sc and not (fused and layer.projection.bias is not None):
                     raise NotImplementedError(f"self_contained=True: {names[id(layer)]}: a float32 map with channels in multiples of 4 and a projection with a bias expected")
+                if fused and layer is last_fusion and upconv["route"] is not None and upconv["armed"]:
+                    wb, why = upconv["route"](layer, tgt)
+                    self.conv_routes[names[id(layer.projection)]] = self.conv_routes[names[id(self.model.head.conv1)]] = ("f32-upconv" if wb is not None else "library", why)
+                    if wb is not None:
+                        upconv["pending"] = (hidden_state, tgt, wb)
+                        return hidden_state   # the residual output on the coarse map: head_fwd runs the composed GEMM and the gather on it
                 if fused and layer.projection.bias is not None:
                     return R.upsample_bilinear_bias((conv1x1_x3 if sc else conv_nb)(layer.projection, hidden_state), tgt, layer.projection.bias)
                 return layer.projection(up(hidden_state, tgt))
@@ -870,9 +909,65 @@ class DepthPipe:
                 return None, "a bias or the 1x1 weight is not 16-byte aligned"
             return head_img["img"], f"{m.in_channels} -> {m.out_channels} channels"
 
+        # float32 mode (where the polyphase neck is on): the last fusion layer's biased 1 x 1 projection, its up-sampling and head.conv1 (3 x 3, zero padding) are one
+        # linear map; all channel mixing runs as ONE library GEMM on the coarse map (C -> 9 C_out channels, composed per parameter version by head_upconv_compose), and
+        # vd3d_head_upconv_gather_f32 sums the 9 taps' bilinear samples per fine pixel: a quarter of conv1's flops, and neither the projected nor the up-sampled map is
+        # written.  VD3D_HEAD_UPCONV=0: A/B switch back.
+        n_fusion = len(self.model.neck.fusion_stage.layers)
+        upconv_on = (self.gemm == "f32" and cm is None and not sc and f32 and self.device.type == "cuda" and tail_operands is not None
+                     and head.head_in_index in (-1, n_fusion - 1))
+        upconv_w = {}   # (parameter versions, (Wc, bc) on the device)
+
+        def upconv_route(layer, tgt):
+            pj, c1 = layer.projection, head.conv1
+            if os.environ.get("VD3D_HEAD_UPCONV", "1") == "0":
+                return None, "VD3D_HEAD_UPCONV=0"
+            if not (_is_conv(pj, 1, 1, 0) and pj.bias is not None and _is_conv(c1, 3, 1, 1) and c1.padding_mode == "zeros" and c1.in_channels == pj.out_channels):
+                return None, "not a biased 1 x 1 projection in front of a 3 x 3 / stride 1 / padding 1 / zeros convolution"
+            if (c1.in_channels, c1.out_channels) not in HEAD_UPCONV_BUILT:
+                return None, f"shape not built: {c1.in_channels} -> {c1.out_channels} channels"
+            if tgt[0] < 2 or tgt[1] < 2:
+                return None, f"output {tgt[0]} x {tgt[1]} below 2 x 2"
+            ts = (pj.weight, pj.bias, c1.weight)
+            try:
+                key = tuple((t.data_ptr(), t._version) for t in ts)
+            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
+                key = tuple((t.data_ptr(),) for t in ts)
+            if upconv_w.get("key") != key:
+                upconv_w["key"], upconv_w["wb"] = key, head_upconv_compose(pj.weight, pj.bias, c1.weight)
+            return upconv_w["wb"], f"{pj.in_channels} -> 9 x {c1.out_channels} channels on the coarse map"
+
+        def upconv_run(hc, tgt, wb):
+            hc = hc.contiguous(memory_format=CL)
+            B, Cc, hh, ww = hc.shape
+            z = F.linear(hc.permute(0, 2, 3, 1).reshape(B * hh * ww, Cc), wb[0], wb[1])   # the NHWC storage is the row matrix
+            y1 = R.head_upconv_gather(z.view(B, hh, ww, -1), tgt, head.conv1.out_channels)
+            if self._flop_count is not None:   # the module graph's count: what conv_nb adds for the projection (on the coarse map) and for conv1
+                self._flop_count[0] += 2.0 * last_fusion.projection.out_channels * hh * ww * Cc
+                self._count_conv(head.conv1, y1)
+            return y1
+
+        if upconv_on:
+            upconv["route"] = upconv_route
+            model_fwd = self.model.forward
+
+            def armed_fwd(*args, **kwargs):   # the head follows the neck in here and nowhere else
+                upconv["armed"], upconv["pending"] = True, None
+                try:
+                    return model_fwd(*args, **kwargs)
+                finally:
+                    upconv["armed"], upconv["pending"] = False, None
+            self.model.forward = armed_fwd
+
         def head_fwd(hidden_states, patch_height, patch_width):
             x = hidden_states[head.head_in_index]
             size = (int(patch_height * head.patch_size), int(patch_width * head.patch_size))
+            pend, upconv["pending"] = upconv["pending"], None
+            if pend is not None and pend[0] is not x:
+                raise RuntimeError("head_upconv: the head did not receive the last fusion layer's output")
+
+            def conv1_nb():   # head.conv1 without its bias: the composed pair on the coarse map the last fusion layer handed through (a float32 map), or the convolution
+                return upconv_run(*pend) if pend is not None else conv_nb(head.conv1, x.contiguous(memory_format=CL))
             if tail_operands is not None and x.dtype == torch.float32:
                 img = None
                 if head_fused:
@@ -881,13 +976,13 @@ class DepthPipe:
                         img, why = None, f"output {size[0]} x {size[1]} below 2 x 2"
                     self.conv_routes[names[id(head.conv2)]] = ("f32-fused" if img is not None else "library", why)
                 if img is not None:
-                    y1 = conv_nb(head.conv1, x.contiguous(memory_format=CL))
+                    y1 = conv1_nb()
                     if self._flop_count is not None:   # exactly what conv_nb(head.conv2, .) and the tail line below add
                         n_out = float(head.conv2.out_channels) * size[0] * size[1]
                         self._flop_count[0] += 2.0 * n_out * head.conv2.in_channels * 9 + 2.0 * n_out
                     w3, b3 = tail_operands()
                     return R.dpt_head_conv(y1, head.conv1.bias, size, img, head.conv2.bias, w3, b3, float(head.max_depth))
-                h = R.upsample_bilinear_bias(conv_nb(head.conv1, x.contiguous(memory_format=CL)), size, head.conv1.bias)
+                h = R.upsample_bilinear_bias(conv1_nb(), size, head.conv1.bias)
                 y = conv_nb(head.conv2, h)
                 if self._flop_count is not None:
                     self._flop_count[0] += 2.0 * y.numel() / y.shape[0]   # the 1x1 convolution to one channel inside the tail kernel

@@ -1217,6 +1217,19 @@ class Renderer:
         _lib.check(self._L.vd3d_neck_poly_conv_f32(self._ctx, _ptr(x), B, h, w, Cin, _ptr(img), _ptr(b), Cout, f, _ptr(out)))
         return out
 
+    def head_upconv_gather(self, z, size, Cout: int):
+        """The fine half of conv3x3(upsample_bilinear(conv1x1(x) + b)) in "coarse GEMM + fine gather" form (include/vd3d.h vd3d_head_upconv_gather_f32): contiguous
+        float32 ``z`` [B, h, w, 9 * Cout] (or [B, h, w, 9, Cout]; ``depth.head_upconv_compose``'s channels, tap-major) -> channels_last [B, Cout, H, W], the sum of the
+        9 taps' bilinear samples per fine pixel: the convolution WITHOUT its bias.  Cout 64 | 32."""
+        Cout, H, W = int(Cout), int(size[0]), int(size[1])
+        if not (torch.is_tensor(z) and z.dtype == torch.float32 and z.dim() in (4, 5) and z.is_contiguous() and z.numel() == z.shape[0] * z.shape[1] * z.shape[2] * 9 * Cout):
+            raise ValueError(f"head_upconv_gather: a contiguous float32 [B, h, w, 9 * {Cout}] tensor expected")
+        B, h, w = (int(v) for v in z.shape[:3])
+        out = torch.empty((B, Cout, H, W), dtype=torch.float32, device=z.device, memory_format=torch.channels_last)
+        self._enter(z, out)
+        _lib.check(self._L.vd3d_head_upconv_gather_f32(self._ctx, _ptr(z), B, h, w, H, W, Cout, _ptr(out)))
+        return out
+
     def depth_to_space_bias(self, y, B: int, H: int, W: int, s: int, bias=None):
         """The scatter of a kernel == stride ConvTranspose2d run as a GEMM: contiguous float32 ``y`` [B*H*W, s*s*C] (columns in (i, j, c) order) ->
         channels_last [B, C, H*s, W*s] with out[b, c, y*s+i, x*s+j] = y[(b*H+y)*W+x, (i*s+j)*C+c] + bias[c] (include/vd3d.h vd3d_depth_to_space_bias_nhwc_f32)."""
