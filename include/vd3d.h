@@ -43,7 +43,8 @@ extern "C" {
  *    vd3d_groupnorm_nhwc_f32: the BiT prefix of DPT-Hybrid under DepthPipe(self_contained=True), vd3d_neck_poly_weight_bytes, vd3d_neck_poly_pack_f32 and
  *    vd3d_neck_poly_conv_f32 (the float32 neck's transposed convolution + 3 x 3 convolution in polyphase form), vd3d_depthpro_preprocess_u8
  *    and vd3d_depthpro_post_f32 (DepthPro's image-processor front end and post-process), vd3d_head_upconv_gather_f32 (the fine half of the float32 head's
- *    first convolution as coarse GEMM + fine gather). */
+ *    first convolution as coarse GEMM + fine gather), vd3d_head_conv_gather_weight_bytes, vd3d_head_conv_gather_tile, vd3d_head_conv_gather_pack_weights and
+ *    vd3d_head_conv_gather_f32 (the float32 head's up-sampling + second convolution + tail as coarse GEMM + fine gather in one launch). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -721,6 +722,26 @@ int vd3d_neck_poly_conv_f32(vd3d_ctx* ctx, const float* x, int B, int h, int w, 
  * atomics, bits depend neither on the batch nor on the call.  Built: Cout = 64 | 32; H, W >= 2 (any size, not only 2 h x 2 w; a down-sampling factor above about
  * 9 is refused); both pointers 16-byte aligned; anything else is VD3D_E_UNSUPPORTED and nothing is launched. */
 int vd3d_head_upconv_gather_f32(vd3d_ctx* ctx, const float* z, int B, int h, int w, int H, int W, int Cout, float* out);
+
+/* vd3d_dpt_head_conv_f32's function with the tail -- out[B][oh][ow] = max(b3 + sum_o w3[o] * max(conv3x3(up(y1 + b1))[o] + b2[o], 0), 0) * scale, Cin -> 32 channels --
+ * in "coarse GEMM + fine gather" form, one launch: conv3x3(up(y1 + b1)) = sum over the 9 taps t = 3 ky + kx of S_t up(W_t y1 + W_t b1), so all channel mixing runs
+ * on the COARSE map (float32 operands on v_mfma_f32_32x32x2_f32) and the fine map keeps 36 multiply-adds per value; Z is produced and consumed in LDS.
+ *     y1 float32 NHWC [B][ih][iw][Cin] (conv1 WITHOUT its bias); Wt the tap-major weight [9 x 32][Cin], row t 32 + o = W[o][:][ky][kx]; bc [9][32],
+ *     bc[t][o] = sum_c W[o][c][ky][kx] b1[c] (the caller composes both); b2, w3 [32].
+ * Arithmetic: Z_t[p][o] is one fmaf chain from 0 over the channels in the order q = 0 .. Cin / 8 - 1, j = 0 .. 3: channel 8 q + j, then 8 q + 4 + j; then + bc[t][o].
+ * A fine value a[o] is one chain acc = fmaf(w, z, acc) from 0 over the taps ascending whose fine position is inside the map (a tap outside contributes nothing,
+ * bias included), corners (y0, x0), (y0, x1), (y1, x0), (y1, x1), weights the rounded products ly * lx of vd3d_upsample_bilinear_nhwc's float32 coordinates
+ * (vd3d_head_upconv_gather_f32's order); the tail is s = fmaf(max(a[o] + b2[o], 0), w3[o], s) from 0 for o ascending, out = max(s + b3, 0) * scale.  No split-K, no
+ * atomics: bits depend neither on the batch nor on the call.  Association differs from vd3d_dpt_head_conv_f32 (which samples x and adds b): close, not equal bits.
+ * vd3d_head_conv_gather_pack_weights lays Wt out in vd3d_head_conv_gather_weight_bytes(Cin) bytes (host-only; < 0: not built): [tap 9][q Cin / 8][lane 64][4 floats],
+ * lane = 32 kh + o holding channels 8 q + 4 kh + 0 .. 3 of output channel o.  vd3d_head_conv_gather_tile (host-only) reports the fine tile th x tw the launch would
+ * cut the map into.  Built: Cin 32 | 64 | 128; oh, ow >= 2 (any size; a down-sampling factor above about 6 is refused); y1, Wt, the image, bc, b2, w3 16-byte
+ * aligned.  Anything else is VD3D_E_UNSUPPORTED and nothing is launched. */
+int64_t vd3d_head_conv_gather_weight_bytes(int Cin);
+int vd3d_head_conv_gather_tile(int ih, int iw, int oh, int ow, int Cin, int* th, int* tw);
+int vd3d_head_conv_gather_pack_weights(vd3d_ctx* ctx, const float* Wt, int Cin, void* image);
+int vd3d_head_conv_gather_f32(vd3d_ctx* ctx, const float* y1, int B, int ih, int iw, int oh, int ow, int Cin, const void* w_image, const float* bc, const float* b2,
+                              const float* w3, float b3, float scale, float* out);
 
 /* The reassemble stage's transposed convolutions of DPT-Large (DPTReassembleLayer.resize = ConvTranspose2d(C, C, kernel_size=s, stride=s, padding=0), s = 4 / 2):
  * kernel == stride, so the windows do not overlap and the layer is a GEMM Y[p][(i, j, co)] = sum_ci X[p][ci] W[ci][co][i][j] (vd3d_gemm_x3 with the weight

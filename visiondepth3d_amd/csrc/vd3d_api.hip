@@ -2039,6 +2039,40 @@ VD3D_EXPORT int vd3d_head_upconv_gather_f32(vd3d_ctx* c, const float* z, int B, 
   HIPCHK(hipGetLastError());
   return 0;
 }
+VD3D_EXPORT int64_t vd3d_head_conv_gather_weight_bytes(int Cin) { return (int64_t)vd_head_conv_gather_weight_bytes(Cin); }
+VD3D_EXPORT int vd3d_head_conv_gather_tile(int ih, int iw, int oh, int ow, int Cin, int* th, int* tw) {
+  if (!vd_head_conv_gather_shape_ok(1, ih, iw, oh, ow, Cin, th, tw))
+    return set_err(VD3D_E_UNSUPPORTED, "head_conv_gather: shape not built: %d input channels, %d x %d -> %d x %d (built: 32 | 64 | 128 channels; an output of at least 2 x 2; "
+                   "a down-sampling factor of at most about 6)", Cin, ih, iw, oh, ow);
+  return 0;
+}
+VD3D_EXPORT int vd3d_head_conv_gather_pack_weights(vd3d_ctx* c, const float* Wt, int Cin, void* image) {
+  if (vd_head_conv_gather_weight_bytes(Cin) < 0)
+    return set_err(VD3D_E_UNSUPPORTED, "head_conv_gather: shape not built: %d input channels (built: 32 | 64 | 128 -> 32 with the tail)", Cin);
+  if (!c || !Wt || !image) return set_err(VD3D_E_INVALID, "bad argument");
+  if ((reinterpret_cast<uintptr_t>(image) & 15) || (reinterpret_cast<uintptr_t>(Wt) & 15))
+    return set_err(VD3D_E_UNSUPPORTED, "head_conv_gather: the composed weights and the weight image must be 16-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_head_conv_gather_pack(c->stream, Wt, Cin, image)) return set_err(VD3D_E_HIP, "head_conv_gather: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_head_conv_gather_f32(vd3d_ctx* c, const float* y1, int B, int ih, int iw, int oh, int ow, int Cin, const void* w_image, const float* bc,
+                                          const float* b2, const float* w3, float b3, float scale, float* out) {
+  // the shape first: a refusal needs neither a context nor a device
+  if (!vd_head_conv_gather_shape_ok(B, ih, iw, oh, ow, Cin, nullptr, nullptr))
+    return set_err(VD3D_E_UNSUPPORTED, "head_conv_gather: shape not built: %d input channels, batch %d, %d x %d -> %d x %d (built: 32 | 64 | 128 -> 32 with the tail; an output of "
+                   "at least 2 x 2; a coarse row below 2^31 elements; a down-sampling factor of at most about 6)", Cin, B, ih, iw, oh, ow);
+  if (!c || !y1 || !w_image || !bc || !b2 || !w3 || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if ((reinterpret_cast<uintptr_t>(y1) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(bc) & 15) || (reinterpret_cast<uintptr_t>(b2) & 15) ||
+      (reinterpret_cast<uintptr_t>(w3) & 15) || (reinterpret_cast<uintptr_t>(out) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "head_conv_gather: y1, the weight image, bc, b2 and w3 must be 16-byte aligned (the output 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_head_conv_gather_f32(c->stream, y1, B, ih, iw, oh, ow, Cin, w_image, bc, b2, w3, b3, scale, out))
+    return set_err(VD3D_E_HIP, "head_conv_gather: the dynamic LDS opt-in or the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 VD3D_EXPORT int vd3d_depth_to_space_bias_nhwc_f32(vd3d_ctx* c, const float* y, const float* bias_or_null, int B, int H, int W, int s, int C, float* out) {
   if (!c || !y || !out || B < 1 || H < 1 || W < 1 || s < 1 || C < 1) return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));

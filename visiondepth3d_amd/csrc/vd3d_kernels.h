@@ -284,6 +284,14 @@ bool vd_launch_neck_poly_conv_f32(hipStream_t s, const float* x, int B, int h, i
 // bilinear samples summed per fine pixel, NHWC [B][H][W][Cout]
 bool vd_head_upconv_shape_ok(int B, int h, int w, int H, int W, int Cout);
 bool vd_launch_head_upconv_gather_f32(hipStream_t s, const float* z, int B, int h, int w, int H, int W, int Cout, float* out);
+
+// vd3d_head_gather.hip: up-sampling + head.conv2 (3 x 3, Cin -> 32) + tail as coarse GEMM + fine gather in ONE launch, Z kept in LDS: y1 NHWC [B][ih][iw][Cin] (conv1
+// without its bias), the packed tap-major composed weights (depth.py head_conv2_compose), bc [9][32] -> [B][oh][ow].  Cin 32 | 64 | 128; th / tw: the fitted tile.
+long long vd_head_conv_gather_weight_bytes(int Cin);
+bool vd_launch_head_conv_gather_pack(hipStream_t s, const float* Wt, int Cin, void* img);
+bool vd_head_conv_gather_shape_ok(int B, int ih, int iw, int oh, int ow, int Cin, int* th, int* tw);
+bool vd_launch_head_conv_gather_f32(hipStream_t s, const float* y1, int B, int ih, int iw, int oh, int ow, int Cin, const void* wimg, const float* bc, const float* b2,
+                                    const float* w3, float b3, float scale, float* out);
 // vd3d_conv_x3.hip: the convolutions of the RIFE interpolation network on the same kernel (kind: 3 x 3 stride 1 | 3 x 3 stride 2 | transposed 4 x 4 stride 2;
 // bias / PReLU / residual epilogue, channel slices of strided NHWC buffers); vd3d_conv_ifn.hip: the float32 glue between its blocks
 long long vd_conv_ifn_weight_bytes(int kind, int Cin, int Cout);

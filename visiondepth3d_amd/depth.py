@@ -226,6 +226,26 @@ def head_upconv_compose(proj_w: torch.Tensor, proj_b, conv1_w: torch.Tensor, dty
     return (W @ P).reshape(9 * Co, -1).to(dtype).contiguous(), (W @ b).reshape(9 * Co).to(dtype).contiguous()
 
 
+HEAD_CONV2_GATHER_BUILT = (32, 64, 128)    # C_in of head.conv2 (-> 32 channels) that vd3d_head_conv_gather_f32 builds
+HEAD_CONV2_GATHER_ROUTED = (32, 64)        # ... and routes by default: those whose probe cleared its bar (profiles/r27_head_conv2_gather.md)
+
+
+def head_conv2_compose(conv2_w: torch.Tensor, conv1_b: torch.Tensor, dtype=torch.float32):
+    """A bias ``conv1_b`` [C], a bilinear up-sampling U and a bias-free 3 x 3 convolution (``conv2_w`` [C_out, C, 3, 3], zero padding) have nothing non-linear between
+    them (``head_upconv_compose``'s identity with the identity as projection):
+        conv2(U(y1 + b1)) = sum over the 9 taps t of  S_t U ( W_t y1 + W_t b1 )
+    -> (Wt [9 * C_out, C], bc [9 * C_out]): tap t = 3 ky + kx, row t * C_out + o,  Wt[t * C_out + o, c] = conv2_w[o, c, ky, kx],  bc[t * C_out + o] = sum_c conv2_w[o, c, ky, kx] b1[c].
+    Computed in float64, rounded once to ``dtype`` (Wt is a permutation of the weight: exact)."""
+    if conv2_w.dim() != 4 or tuple(conv2_w.shape[2:]) != (3, 3):
+        raise ValueError(f"head_conv2: convolution weight {tuple(conv2_w.shape)} is not [C_out, C, 3, 3]")
+    Co, Cm = int(conv2_w.shape[0]), int(conv2_w.shape[1])
+    if tuple(conv1_b.shape) != (Cm,):
+        raise ValueError(f"head_conv2: bias {tuple(conv1_b.shape)} is not [{Cm}]")
+    W = conv2_w.detach().to(torch.float64).permute(2, 3, 0, 1).reshape(9, Co, Cm)   # [t = 3 ky + kx][o][c]
+    b = conv1_b.detach().to(torch.float64)
+    return W.reshape(9 * Co, Cm).to(dtype).contiguous(), (W @ b).reshape(9 * Co).to(dtype).contiguous()
+
+
 def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     """Patch-embedding weight [C, 3, p, p] (kernel == stride: every patch is one GEMM row) -> [C, Kp]: the flattened (c, ky, kx) columns, zero-padded from 3 p^2
     to the next multiple of 16 (vd3d_gemm_x3's K unit; p = 14: 588 -> 592).  vd3d_patchify_f32 writes the matching rows, zero tail included."""
@@ -507,7 +527,9 @@ class DepthPipe:
         size; ``conv_routes`` reads ("fp16x2" | "library", reason).  In the default float32 mode (``gemm="f32"``, ``conv=None``, with a renderer) the head's up-sampling, its second
         convolution and everything behind it run as ONE exact-float32 MFMA launch (``vd3d_dpt_head_conv_f32``: 32 | 64 | 128 -> 32 channels);
         ``conv_routes["head.conv2"]`` is then ``("f32-fused", ...)``, or ``("library", reason)`` where the three launches stay (a shape that is not
-        built, ``VD3D_HEAD_FUSED=0``).  In the same mode (not ``self_contained``) the up-scaling reassemble stages' transposed convolution and the 3 x 3 neck
+        built, ``VD3D_HEAD_FUSED=0``).  For 32 | 64 input channels (``HEAD_CONV2_GATHER_ROUTED``) that launch takes the "coarse GEMM + fine gather" form
+        (``vd3d_head_conv_gather_f32``, composed per parameter version by ``head_conv2_compose``: all channel mixing on the coarse map, Z kept in LDS, close but
+        not equal bits); the reason string names the form, ``VD3D_HEAD_CONV2_GATHER=0`` switches back and ``=1`` routes every built count.  In the same mode (not ``self_contained``) the up-scaling reassemble stages' transposed convolution and the 3 x 3 neck
         convolution behind it run as ONE exact-float32 MFMA launch on the coarse map (``vd3d_neck_poly_conv_f32``, composed per parameter version by
         ``neck_poly_compose``: DA-V2-Base's and -Small's shapes); ``conv_routes["neck.reassemble_stage.layers.{0,1}.resize"]`` and ``["neck.convs.{0,1}"]`` are
         then ``("f32-poly", ...)``, or ``("library", reason)`` (a shape that is not built, ``VD3D_NECK_POLY=0``).
@@ -909,6 +931,26 @@ class DepthPipe:
                 return None, "a bias or the 1x1 weight is not 16-byte aligned"
             return head_img["img"], f"{m.in_channels} -> {m.out_channels} channels"
 
+        # ... the same launch in "coarse GEMM + fine gather" form (vd3d_head_conv_gather_f32: a third of conv2's flops), where the channel count is routed
+        # (HEAD_CONV2_GATHER_ROUTED: a rule on the shape alone; VD3D_HEAD_CONV2_GATHER=1 routes every built count, =0 none) and the launch is not refused
+        gather_img = {}   # (parameter versions, (image, bc, C_in) or None)
+
+        def head_conv2_gather(in_size, size):
+            m = head.conv2
+            sw = os.environ.get("VD3D_HEAD_CONV2_GATHER", "")
+            if sw == "0" or m.out_channels != 32 or m.in_channels not in (HEAD_CONV2_GATHER_BUILT if sw == "1" else HEAD_CONV2_GATHER_ROUTED) or m.padding_mode != "zeros":
+                return None
+            if R.head_conv_gather_tile(in_size, size, m.in_channels) is None:   # a ratio no tile serves
+                return None
+            ts = (m.weight, head.conv1.bias)
+            try:
+                key = tuple((t.data_ptr(), t._version) for t in ts)
+            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
+                key = tuple((t.data_ptr(),) for t in ts)
+            if gather_img.get("key") != key:
+                gather_img["key"], gather_img["img"] = key, R.head_conv_gather_pack(*head_conv2_compose(m.weight, head.conv1.bias))
+            return gather_img["img"]
+
         # float32 mode (where the polyphase neck is on): the last fusion layer's biased 1 x 1 projection, its up-sampling and head.conv1 (3 x 3, zero padding) are one
         # linear map; all channel mixing runs as ONE library GEMM on the coarse map (C -> 9 C_out channels, composed per parameter version by head_upconv_compose), and
         # vd3d_head_upconv_gather_f32 sums the 9 taps' bilinear samples per fine pixel: a quarter of conv1's flops, and neither the projected nor the up-sampled map is
@@ -974,6 +1016,10 @@ class DepthPipe:
                     img, why = head_conv2_image()
                     if img is not None and (size[0] < 2 or size[1] < 2):
                         img, why = None, f"output {size[0]} x {size[1]} below 2 x 2"
+                    gimg = None
+                    if img is not None:
+                        gimg = head_conv2_gather((int(x.shape[2]), int(x.shape[3])) if pend is None else pend[1], size)
+                        why += ", form gather (coarse GEMM + fine gather)" if gimg is not None else ", form conv"
                     self.conv_routes[names[id(head.conv2)]] = ("f32-fused" if img is not None else "library", why)
                 if img is not None:
                     y1 = conv1_nb()
@@ -981,6 +1027,8 @@ class DepthPipe:
                         n_out = float(head.conv2.out_channels) * size[0] * size[1]
                         self._flop_count[0] += 2.0 * n_out * head.conv2.in_channels * 9 + 2.0 * n_out
                     w3, b3 = tail_operands()
+                    if gimg is not None:
+                        return R.dpt_head_conv(y1, head.conv1.bias, size, gimg, head.conv2.bias, w3, b3, float(head.max_depth), form="gather")
                     return R.dpt_head_conv(y1, head.conv1.bias, size, img, head.conv2.bias, w3, b3, float(head.max_depth))
                 h = R.upsample_bilinear_bias(conv1_nb(), size, head.conv1.bias)
                 y = conv_nb(head.conv2, h)

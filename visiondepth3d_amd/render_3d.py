@@ -1160,11 +1160,54 @@ class Renderer:
         _lib.check(self._L.vd3d_dpt_head_conv_pack_weights(self._ctx, _ptr(w), Cin, Cout, _ptr(img)))
         return img
 
-    def dpt_head_conv(self, x, b_in, size, w_image, b2=None, w3=None, b3: float = 0.0, scale: float = 1.0, Cout=None):
+    def head_conv_gather_pack(self, Wt: torch.Tensor, bc: torch.Tensor):
+        """Lay ``depth.head_conv2_compose``'s tap-major weight ``Wt`` [9 * 32, Cin] and bias ``bc`` [9 * 32] out for ``dpt_head_conv(form="gather")`` -> (image, bc on
+        the device, Cin); ``None`` when Cin is not built (32 | 64 | 128)."""
+        if Wt.dim() != 2 or Wt.shape[0] != 288 or tuple(bc.shape) != (288,):
+            raise ValueError(f"head_conv_gather_pack: Wt {tuple(Wt.shape)} / bc {tuple(bc.shape)} are not [288, Cin] and [288]")
+        Cin = int(Wt.shape[1])
+        nb = int(self._L.vd3d_head_conv_gather_weight_bytes(Cin))
+        if nb < 0:
+            return None
+        w = Wt.detach().to(self.device, torch.float32).contiguous()
+        b = bc.detach().to(self.device, torch.float32).contiguous().clone()
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(self._L.vd3d_head_conv_gather_pack_weights(self._ctx, _ptr(w), Cin, _ptr(img)))
+        return img, b, Cin
+
+    def head_conv_gather_tile(self, in_size, size, Cin: int):
+        """The fine tile (th, tw) ``dpt_head_conv(form="gather")`` cuts an ``in_size`` -> ``size`` map into; ``None`` where the launch would be refused."""
+        th, tw = C.c_int(0), C.c_int(0)
+        if self._L.vd3d_head_conv_gather_tile(int(in_size[0]), int(in_size[1]), int(size[0]), int(size[1]), int(Cin), C.byref(th), C.byref(tw)) != 0:
+            return None
+        return th.value, tw.value
+
+    def dpt_head_conv(self, x, b_in, size, w_image, b2=None, w3=None, b3: float = 0.0, scale: float = 1.0, Cout=None, form: str = "conv"):
         """conv3x3(upsample_bilinear_bias(x, size, b_in)) in one exact-float32 kernel (include/vd3d.h vd3d_dpt_head_conv_f32), W given as
         ``dpt_head_conv_pack(W)``.  With ``b2`` and ``w3`` (Cout 32): -> [B,h,w] = relu(b3 + sum_c w3[c] relu(y + b2[c])) * scale, ``dpt_head_tail``'s function;
-        without (Cout 64): -> channels_last [B,Cout,h,w], the convolution without a bias."""
+        without (Cout 64): -> channels_last [B,Cout,h,w], the convolution without a bias.
+        ``form="gather"``: the same function with the tail as coarse GEMM + fine gather in one launch (vd3d_head_conv_gather_f32; close, not equal bits): ``w_image``
+        is then ``head_conv_gather_pack(...)``, whose composed bias already holds ``b_in`` (``b_in`` itself is not read)."""
         self._nhwc_f32(x)
+        if form == "gather":
+            if b2 is None or w3 is None or w_image is None:
+                raise ValueError("dpt_head_conv: the gather form needs the tail's b2 and w3 and a packed image (head_conv_gather_pack)")
+            img, bc, Cin = w_image
+            B, Cx, ih, iw = x.shape
+            oh, ow = int(size[0]), int(size[1])
+            if Cx != Cin:
+                raise ValueError(f"dpt_head_conv: the map has {Cx} channels, the packed weights take {Cin}")
+            for name, t in (("b2", b2), ("w3", w3)):
+                if not (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 32):
+                    raise ValueError(f"dpt_head_conv: {name} must be 32 contiguous float32 values")
+            out = torch.empty((B, oh, ow), dtype=torch.float32, device=x.device)
+            self._enter(x, img, bc, b2, w3, out)
+            _lib.check(self._L.vd3d_head_conv_gather_f32(self._ctx, _ptr(x), B, ih, iw, oh, ow, Cin, _ptr(img), _ptr(bc), _ptr(b2), _ptr(w3), float(b3), float(scale),
+                                                         _ptr(out)))
+            return out
+        if form != "conv":
+            raise ValueError(f"dpt_head_conv: form {form!r} is not 'conv' or 'gather'")
         if (b2 is None) != (w3 is None):
             raise ValueError("dpt_head_conv: b2 and w3 go together")
         B, Cin, ih, iw = x.shape
