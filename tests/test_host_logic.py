@@ -542,3 +542,47 @@ def test_dpt_neck_head_rewrite_is_the_module_graph():
         px_stock = ph * pw * (1 + 4 + 16 + 64)                                   # the projections' output pixels in the stock graph ...
         px_mine = -(-ph // 2) * -(-pw // 2) + ph * pw * (1 + 4 + 16)              # ... and their input pixels (the stride-2 reassemble map rounds up)
         assert abs((stock - mine) - 2.0 * Cf * Cf * (px_stock - px_mine)) <= 1e-9 * stock, (stock, mine)
+
+
+def test_per_version_cache_rebuilds_exactly_when_a_parameter_changes():
+    """depth._PerVersion: one build for repeated get; a rebuild after an in-place update of ONE tensor of several and after a parameter's .data is replaced; tensors
+    made under torch.inference_mode() (no version counter: the key is the address) work; a None value is cached, not rebuilt on every call."""
+    import torch
+    from visiondepth3d_amd.depth import _PerVersion
+    a, b = torch.nn.Parameter(torch.ones(4)), torch.nn.Parameter(torch.zeros(3))
+    builds = []
+    cache = _PerVersion(lambda: (builds.append(1), float(a.detach().sum() + b.detach().sum()))[1])
+    assert cache.get(a, b) == 4.0 and cache.get(a, b) == 4.0 and cache.get(a, None, b) == 4.0 and len(builds) == 1
+    with torch.no_grad():
+        b.copy_(torch.full((3,), 2.0))
+    assert cache.get(a, b) == 10.0 and cache.get(a, b) == 10.0 and len(builds) == 2
+    a.data = torch.full((4,), 3.0)                       # another storage (the old one is still alive: the address differs)
+    assert cache.get(a, b) == 18.0 and cache.get(a, b) == 18.0 and len(builds) == 3
+    with torch.inference_mode():
+        t, u = torch.ones(5), torch.ones(5)
+    with pytest.raises(RuntimeError):
+        t._version
+    inf = _PerVersion(lambda: builds.append(1) or len(builds))
+    assert inf.get(t) == 4 and inf.get(t) == 4 and inf.get(u) == 5 and inf.get(u) == 5
+    none = _PerVersion(lambda: builds.append(1))         # "shape not built"
+    assert none.get(a) is None and none.get(a) is None and len(builds) == 6
+
+
+def test_switch_table_states_every_route_switch(monkeypatch):
+    """depth._switch / _SWITCHES: the five A/B switches; "0" reads False and "1" True for each, unset (and anything else) the table's default -- True for four,
+    None for the tri-state VD3D_HEAD_CONV2_GATHER (the shape rule decides); VD3D_NECK_GLUE alone is read at construction."""
+    from visiondepth3d_amd.depth import _SWITCHES, _switch
+    assert sorted(_SWITCHES) == ["VD3D_HEAD_CONV2_GATHER", "VD3D_HEAD_FUSED", "VD3D_HEAD_UPCONV", "VD3D_NECK_GLUE", "VD3D_NECK_POLY"]
+    for name, (default, read, zero) in _SWITCHES.items():
+        assert default is (None if name == "VD3D_HEAD_CONV2_GATHER" else True) and zero
+        assert read == ("construction" if name == "VD3D_NECK_GLUE" else "forward")
+        monkeypatch.delenv(name, raising=False)
+        assert _switch(name) is default
+        monkeypatch.setenv(name, "0")
+        assert _switch(name) is False
+        monkeypatch.setenv(name, "1")
+        assert _switch(name) is True
+        monkeypatch.setenv(name, "yes")
+        assert _switch(name) is default
+    with pytest.raises(KeyError):
+        _switch("VD3D_NO_SUCH_SWITCH")

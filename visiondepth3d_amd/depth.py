@@ -56,6 +56,7 @@ MODEL_ZOO = {
 }
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
+_CL = torch.channels_last
 # image-processor constants (preprocessor_config.json of the checkpoints): DA = DPTImageProcessor(size 518, keep_aspect_ratio,
 # ensure_multiple_of 14, bicubic, ImageNet mean/std); DPT-Large = 384 x 384, no aspect keeping, mean = std = 0.5
 PROCESSORS = {
@@ -350,7 +351,8 @@ class _BitPrefix:
     """The BiT ResNet prefix of DPT-Hybrid on renderer R without a library call (self_contained=True): ``plan`` = bit_prefix_plan(backbone).  The standardised
     weights (bit_standardized_weight) are folded and packed once, here; activations are contiguous float32 NHWC [B, H, W, C] from the first launch to the last.
     Per bottleneck: three GEMM / convolution launches (four in a stage's first layer, whose shortcut is a convolution too; an im2col launch in front of a strided
-    one) and one vd3d_groupnorm_nhwc_f32 behind each -- the last one with the shortcut and the ReLU in its apply pass.  A call returns the stage-1, -2 and -3 maps."""
+    one) and one vd3d_groupnorm_nhwc_f32 behind each (one fixed summation order: batch-independent, bit-repeatable) -- the last one with the shortcut and the ReLU in
+    its apply pass; the stem's pool is vd3d_maxpool3x3_s2_nhwc_f32 (TensorFlow "same" padding).  A call returns the stage-1, -2 and -3 maps."""
 
     def __init__(self, pipe, backbone, plan, names):
         self.pipe, self.bb, self.plan, self.names = pipe, backbone, plan, names
@@ -411,24 +413,31 @@ class _BitPrefix:
         return maps
 
 
+class _PerVersion:
+    """``get(*tensors)`` -> the value of ``build()``, built ONCE per version of the parameters it is made of.  The key is (data_ptr, _version) per tensor (None entries
+    are skipped): an in-place update (load_state_dict, .copy_) bumps a version counter, a replaced ``.data`` moves the address, and either is picked up at the next
+    call -- no compose, pack or host read per call.  Inference tensors (created / loaded under torch.inference_mode()) track no version counter; they are
+    immutable outside inference mode, so the storage address alone identifies the value.  A None value ("shape not built") is cached like any other."""
+
+    def __init__(self, build):
+        self.build, self.key, self.value = build, None, None
+
+    def get(self, *tensors):
+        ts = [t for t in tensors if t is not None]
+        try:
+            key = tuple((t.data_ptr(), t._version) for t in ts)
+        except RuntimeError:
+            key = tuple((t.data_ptr(),) for t in ts)
+        if key != self.key:
+            self.value, self.key = self.build(), key
+        return self.value
+
+
 def _head_tail_operands(conv3: torch.nn.Conv2d):
     """() -> (w3, b3) of the head's 1x1 convolution to one channel, for vd3d_dpt_head_tail_f32.  The scalar bias is read on the host ONCE per parameter
-    version (no per-call sync); an in-place update of the parameters (load_state_dict, .copy_) bumps their version counters and is picked up at the
-    next call."""
-    tail = {"key": None, "w3": None, "b3": 0.0}
-
-    def operands():
-        w, b = conv3.weight, conv3.bias
-        try:
-            key = (w.data_ptr(), w._version, b.data_ptr(), b._version)
-        except RuntimeError:   # inference tensors (created / loaded under torch.inference_mode()) track no version counter: immutable outside
-            key = (w.data_ptr(), b.data_ptr())   # inference mode, so the storage address identifies the value (ADVICE r5)
-        if tail["key"] != key:
-            tail["w3"] = w.detach().reshape(-1).contiguous()
-            tail["b3"] = float(b.detach().float().item())
-            tail["key"] = key
-        return tail["w3"], tail["b3"]
-    return operands
+    version (_PerVersion: no per-call sync)."""
+    tail = _PerVersion(lambda: (conv3.weight.detach().reshape(-1).contiguous(), float(conv3.bias.detach().float().item())))
+    return lambda: tail.get(conv3.weight, conv3.bias)
 
 
 _TUNABLE_DIR = None
@@ -470,6 +479,344 @@ CONV_X3_MIN_TILES = 200
 # smallest size that did not lose on balance at one frame -- the batch a batch-blind rule has to be safe for.
 CONV_X2_MIN_TILES = 50
 
+# The A/B switches of the neck / head routes (environment variables): name -> (what unset or any other value means, when it is read, what "0" does); "1" reads True.
+# VD3D_HEAD_CONV2_GATHER alone is tri-state: unset (None) the shape rule decides.  Setting one between two forwards of a pipe flips the per-forward ones.
+_SWITCHES = {
+    "VD3D_NECK_GLUE": (True, "construction", "the float32 neck / head keep the module graph's own bias, ReLU and add passes; every composed route below is off too"),
+    "VD3D_HEAD_FUSED": (True, "forward", "head.conv2 and the tail stay three launches instead of one vd3d_dpt_head_conv_f32"),
+    "VD3D_HEAD_CONV2_GATHER": (None, "forward", "the fused head launch keeps its conv form; 1: the gather form for every built C_in, unset: for HEAD_CONV2_GATHER_ROUTED"),
+    "VD3D_HEAD_UPCONV": (True, "forward", "the last projection, its up-sampling and head.conv1 stay separate launches"),
+    "VD3D_NECK_POLY": (True, "forward", "the reassemble stage's transposed convolution and neck.convs[i] stay two library calls"),
+}
+
+
+def _switch(name: str):
+    """The A/B switch ``name`` of _SWITCHES as it stands in the environment NOW: False for "0", True for "1", the table's default for unset or anything else."""
+    return {"0": False, "1": True}.get(os.environ.get(name), _SWITCHES[name][0])
+
+
+class _ConvRouter:
+    """Where the convolutions of the DPT neck / fusion stage / head of ``pipe`` run (Depth-Anything's rewrite and DPT-Large's / DPT-Hybrid's alike).  ``f32``: the float32
+    glue is on (float32 pipe, VD3D_NECK_GLUE not "0"); without it every method here declines and the modules run as they are.
+      * ``conv_nb(m, x)``: m's convolution WITHOUT its bias, counted for flops_per_frame (the modules' hooks are bypassed): ``conv_x2``, else ``conv_x3``, else the library's.
+      * ``conv_x2``: ``gemm="fp16x2"`` with ``conv=None`` -- vd3d_conv3x3_x2 where it builds the shape and the launch has 256 tiles of 16 x 32 or more.
+      * ``conv_x3``: ``conv="bf16x3"`` | ``"fp16x2"`` -- the 3 x 3 / stride 1 / padding 1 convolutions (``neck.convs``, the fusion stage's residual units, the head's
+        two) on the tile convolution of the mode (Renderer.TILE_CONVS), one 8 x 32 tile kernel for every routed convolution: vd3d_conv3x3_x3, the three-term /
+        six-product arithmetic of the GEMM (include/vd3d.h), or vd3d_conv3x3_s1_x2, the two-term fp16 arithmetic of its mode (three products per MAC, weights
+        pre-scaled per output channel by an exact power of two, |x| < 65 504; vd3d_conv3x3_x2 stays the route of ``conv=None``) -- for 32 / 64 / 128 / 256 output
+        channels and input channels in multiples of 16.  Maps below the measured launch-size rule stay on the library (CONV_X3_MIN_TILES tiles of 8 x 32 over the batch;
+        CONV_X2_MIN_TILES PER FRAME in fp16x2, whose rule reads the map and the module, never the batch size); nothing else falls back.  ``pipe.conv_routes``
+        (module name -> (mode | "library", reason)) records, per forward, where each of these convolutions ran and why.
+      * ``self_contained=True``: no size rule -- EVERY 3 x 3 stride-1 convolution takes the tile convolution (DPT-Large: 4 x 4 to 48 x 48 maps at 384 x 384), the fusion layers'
+        1 x 1 projections run as vd3d_gemm_x3 over the pixel rows (``conv1x1_x3``), and a module the mode cannot route is refused by name, never handed to a library.
+    The weight images (``conv_img``, ``conv3_img``, ``gemm_img``) are keyed by id(module) and PACK ONCE, at first use: no parameter-version tracking (unlike _PerVersion)."""
+
+    def __init__(self, pipe, f32: bool):
+        self.pipe, self.R, self.f32, self.sc, self.cm, self.names = pipe, pipe.renderer, f32, pipe.self_contained, pipe.conv, pipe._names
+        self.min_tiles = CONV_X2_MIN_TILES if self.cm == "fp16x2" else CONV_X3_MIN_TILES
+        self.conv_img, self.conv3_img, self.gemm_img = {}, {}, {}   # None = shape not built
+        if self.cm is not None and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
+            for m in pipe.model.neck.convs:
+                if self.sc and m.bias is not None:
+                    raise NotImplementedError(f"self_contained=True: {self.names[id(m)]} has a bias (the stock neck convolutions have none) -- not built")
+                if m.bias is None:
+                    m.forward = lambda x, m=m: self._or_library(m, x, self.conv_x3(m, x))
+
+    def record(self, label, operand, why, *modules):
+        """The one route record: conv_routes[name] = (label, why) for each module where the route runs (``operand`` is not None), ("library", why) where not."""
+        for m in modules:
+            self.pipe.conv_routes[self.names[id(m)]] = (label if operand is not None else "library", why)
+
+    def up(self, x, size):
+        if x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] % 8 == 0 and x.is_contiguous(memory_format=_CL):
+            return self.R.upsample_bilinear(x, size)
+        return F.interpolate(x, size=size, mode="bilinear", align_corners=True)
+
+    def conv_x2(self, m, x):
+        if self.pipe.gemm != "fp16x2" or self.cm is not None or not self.f32 or not _is_conv(m, 3, 1, 1) or x.dtype != torch.float32:
+            return None
+        if id(m) not in self.conv_img:
+            self.conv_img[id(m)] = self.R.conv3x3_x2_pack(m.weight)
+        # one workgroup per 16 x 32 output tile: below one tile per CU the library's split-K kernels win (19 x 33 maps with 768 input channels: measured 0.43 vs 0.17 ms)
+        if self.conv_img[id(m)] is None or x.shape[0] * ((x.shape[2] + 15) // 16) * ((x.shape[3] + 31) // 32) < 256:
+            return None
+        return self.R.conv3x3_x2(x.contiguous(memory_format=_CL), self.conv_img[id(m)], m.out_channels)
+
+    def conv_x3(self, m, x):
+        cm, R = self.cm, self.R
+        if cm is None or not self.f32 or not _is_conv(m, 3, 1, 1) or x.dtype != torch.float32:
+            return None
+        if id(m) not in self.conv3_img:
+            self.conv3_img[id(m)] = R.conv3x3_tile_pack(m.weight, cm, 1)
+        img = self.conv3_img[id(m)]
+        if img is None:
+            if self.sc:
+                raise NotImplementedError(f"self_contained=True: {self.names[id(m)]}: vd3d_conv3x3_{R.TILE_CONVS[cm, 1]} does not build {m.in_channels} -> {m.out_channels} channels")
+            return self.record(cm, None, f"shape not built: {m.in_channels} -> {m.out_channels} channels", m)
+        why = "self-contained"   # no size rule: every map, the 19 x 33 ones included
+        if not self.sc:
+            # one workgroup per 8 x 32 output tile; fp16x2's rule reads the map alone, never the batch: a frame's route and bits do not depend on what it is batched with
+            tiles = (1 if cm == "fp16x2" else x.shape[0]) * ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)
+            if tiles < self.min_tiles:
+                return self.record(cm, None, f"size rule: {tiles} tiles < {self.min_tiles}", m)
+            why = f"{tiles} tiles"
+        self.record(cm, img, why, m)
+        return R.conv3x3_tile(x.contiguous(memory_format=_CL), img, m.out_channels, cm, 1)
+
+    def _or_library(self, m, x, y):   # y, or the library's convolution of x by module m without its bias where no kernel took it (y is None): refused if self-contained
+        if y is None and self.sc:
+            raise NotImplementedError(f"self_contained=True: {self.names[id(m)]} is not a float32 3 x 3 / stride 1 / padding 1 convolution -- not built")
+        return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups) if y is None else y
+
+    def conv_nb(self, m, x):
+        y = self.conv_x2(m, x)
+        if y is None:
+            y = self.conv_x3(m, x)
+        if y is None:
+            y = self._or_library(m, x, None).contiguous(memory_format=_CL)
+        self.pipe._count_conv(m, y)
+        return y
+
+    def conv1x1_x3(self, m, x):
+        """Self-contained: a 1 x 1 convolution WITHOUT its bias as vd3d_gemm_x3 over the pixel rows of a channels_last map (its NHWC storage is the row matrix)."""
+        pipe, name = self.pipe, self.names[id(m)]
+        if not _is_conv(m, 1, 1, 0) or m.in_channels % 16 or x.dtype != torch.float32:
+            raise NotImplementedError(f"self_contained=True: {name} is not a float32 1 x 1 convolution with C_in a multiple of 16 -- not built")
+        if id(m) not in self.gemm_img:
+            self.gemm_img[id(m)] = self.R.gemm_x3_pack(m.weight.reshape(m.out_channels, m.in_channels), pipe.gemm)
+        rows = x.contiguous(memory_format=_CL).permute(0, 2, 3, 1)   # [B, h, w, C] contiguous
+        y = self.R.linear_x3(rows, self.gemm_img[id(m)], m.out_channels, None, mode=pipe.gemm).permute(0, 3, 1, 2)
+        pipe.conv_routes[name] = (pipe.gemm, "self-contained: vd3d_gemm_x3 over the pixel rows")
+        pipe._count_conv(m, y)   # what conv_nb adds for the same module
+        return y
+
+    def head_tail3(self, y1, conv1, conv2, size, tail, scale, act="relu"):
+        """The three-launch head tail (DA and DPT): ``y1`` = conv1 without its bias -> the bias inside the align_corners up-sampling to ``size``, conv2 bias-free,
+        then ONE launch for bias, ReLU, the 1 x 1 convolution to one channel (``tail()`` = its operands), bias, ReLU | Sigmoid and ``scale`` (vd3d_dpt_head_tail_f32 | vd3d_dpt_head_tail_act_f32: torch.sigmoid's CPU values)."""
+        y = self.conv_nb(conv2, self.R.upsample_bilinear_bias(y1, size, conv1.bias))
+        self.pipe._count_flops(2.0 * y.numel() / y.shape[0])   # the 1x1 convolution to one channel inside the tail kernel
+        if act == "sigmoid":   # vd3d_dpt_head_tail_act_f32
+            return self.R.dpt_head_tail(y, conv2.bias, *tail(), scale, act="sigmoid")
+        return self.R.dpt_head_tail(y, conv2.bias, *tail(), scale)
+
+
+class _Route:
+    """A composed route of the default float32 mode (``gemm="f32"``, hence ``conv=None`` and no ``self_contained``; a renderer on the GPU; the float32 glue on).
+    ``route(...)`` -> (operand | None, why): ``decide`` reads the route's switch (_SWITCHES, per forward) and its shape rules and takes the operand from a
+    _PerVersion (composed and packed once per parameter version); _ConvRouter.record notes (``label`` | "library", why) under the names of ``modules``."""
+    label, modules = None, ()
+
+    def route(self, *args):
+        operand, why = self.decide(*args)
+        self.cr.record(self.label, operand, why, *self.modules)
+        return operand, why
+
+
+class _PolyRoute(_Route):
+    """"f32-poly": an up-scaling reassemble stage's ConvTranspose2d ``rz`` (kernel == stride == f, bias) and the bias-free 3 x 3 neck convolution ``cv`` behind it are one
+    linear map; composed on the coarse grid (neck_poly_compose) they run as ONE exact-float32 MFMA launch (vd3d_neck_poly_conv_f32: DA-V2-Base's and -Small's shapes)
+    with 2.25 (f = 4) / 4 (f = 2) coarse taps per output pixel instead of 9 fine ones, and the fine map between them is never written.  conv_routes of both modules
+    (``neck.reassemble_stage.layers.{0,1}.resize``, ``neck.convs.{0,1}``) read ("f32-poly", ...), or ("library", reason): a shape that is not built, VD3D_NECK_POLY=0.
+    ``pending``: the packed blocks the reassemble stage hands to ``cv`` in this forward (None: it ran the transposed convolution itself)."""
+    label = "f32-poly"
+
+    def __init__(self, cr, rz, cv):
+        self.cr, self.rz, self.cv, self.modules, self.pending = cr, rz, cv, (rz, cv), None
+        self.packed = _PerVersion(lambda: cr.R.neck_poly_pack(*neck_poly_compose(rz.weight, rz.bias, cv.weight, rz.kernel_size[0]), rz.kernel_size[0]))
+        cv.forward = self.conv_fwd
+
+    def decide(self, x):
+        rz, cv, f = self.rz, self.cv, self.rz.kernel_size[0]
+        if x.dtype != torch.float32:
+            return None, f"{x.dtype} map"
+        if not _switch("VD3D_NECK_POLY"):
+            return None, "VD3D_NECK_POLY=0"
+        if not (rz.kernel_size == rz.stride == (f, f) and f >= 2 and rz.padding == (0, 0) and rz.output_padding == (0, 0) and rz.dilation == (1, 1) and rz.groups == 1
+                and _is_conv(cv, 3, 1, 1) and cv.bias is None and cv.in_channels == rz.out_channels and cv.padding_mode == "zeros"):
+            return None, "not a ConvTranspose2d with kernel == stride in front of a bias-free 3 x 3 / stride 1 / padding 1 convolution"
+        packed = self.packed.get(rz.weight, rz.bias, cv.weight)
+        if packed is None:
+            return None, f"shape not built: {rz.in_channels} -> {cv.out_channels} channels, factor {f}"
+        return packed, f"{rz.in_channels} -> {cv.out_channels} channels, factor {f}: {len(neck_poly_offsets(f))} composed blocks"
+
+    def conv_fwd(self, x):
+        rz, m, f = self.rz, self.cv, self.rz.kernel_size[0]
+        packed, self.pending = self.pending, None
+        if packed is None:
+            return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
+        self.cr.pipe._count_flops(2.0 * rz.out_channels * (f * x.shape[2]) * (f * x.shape[3]) * rz.in_channels * f * f)   # the bypassed transposed convolution's hook
+        return self.cr.R.neck_poly_conv(x.contiguous(memory_format=_CL), packed)
+
+
+class _UpconvRoute(_Route):
+    """"f32-upconv": the LAST fusion layer's biased 1 x 1 projection ``proj``, its up-sampling and ``head.conv1`` (3 x 3, zero padding) are one linear map; all channel
+    mixing runs as ONE library GEMM on the coarse map (head_upconv_compose: C -> 9 C_out channels) and vd3d_head_upconv_gather_f32 sums the 9 taps' bilinear samples
+    per fine pixel: a quarter of conv1's flops, and neither the projected nor the up-sampled map is written.  conv_routes of both modules
+    (``neck.fusion_stage.layers.<last>.projection``, ``head.conv1``) read ("f32-upconv", ...), or ("library", reason): a shape that is not built, VD3D_HEAD_UPCONV=0.
+    ``armed``: inside the model's own forward, where the head consumes the neck's output (the neck called alone materialises the up-sampled projection as ever);
+    ``pending``: (coarse map, target size, (Wc, bc)), what the last fusion layer hands to the head in this forward."""
+    label = "f32-upconv"
+
+    def __init__(self, cr, proj, conv1):
+        self.cr, self.proj, self.conv1, self.modules, self.armed, self.pending = cr, proj, conv1, (proj, conv1), False, None
+        self.wb = _PerVersion(lambda: head_upconv_compose(proj.weight, proj.bias, conv1.weight))
+        model, model_fwd = cr.pipe.model, cr.pipe.model.forward
+
+        def armed_fwd(*args, **kwargs):   # the head follows the neck in here and nowhere else
+            self.armed, self.pending = True, None
+            try:
+                return model_fwd(*args, **kwargs)
+            finally:
+                self.armed, self.pending = False, None
+        model.forward = armed_fwd
+
+    def decide(self, tgt):
+        pj, c1 = self.proj, self.conv1
+        if not _switch("VD3D_HEAD_UPCONV"):
+            return None, "VD3D_HEAD_UPCONV=0"
+        if not (_is_conv(pj, 1, 1, 0) and pj.bias is not None and _is_conv(c1, 3, 1, 1) and c1.padding_mode == "zeros" and c1.in_channels == pj.out_channels):
+            return None, "not a biased 1 x 1 projection in front of a 3 x 3 / stride 1 / padding 1 / zeros convolution"
+        if (c1.in_channels, c1.out_channels) not in HEAD_UPCONV_BUILT:
+            return None, f"shape not built: {c1.in_channels} -> {c1.out_channels} channels"
+        if tgt[0] < 2 or tgt[1] < 2:
+            return None, f"output {tgt[0]} x {tgt[1]} below 2 x 2"
+        return self.wb.get(pj.weight, pj.bias, c1.weight), f"{pj.in_channels} -> 9 x {c1.out_channels} channels on the coarse map"
+
+    def take(self, x):   # what the last fusion layer handed over in this forward (None: nothing) -- for the head, whose input x it must be
+        pend, self.pending = self.pending, None
+        if pend is not None and pend[0] is not x:
+            raise RuntimeError("head_upconv: the head did not receive the last fusion layer's output")
+        return pend
+
+    def run(self, hc, tgt, wb):   # head.conv1 without its bias from the coarse map hc: the composed GEMM over its rows (the NHWC storage is the row matrix) and the gather
+        hc = hc.contiguous(memory_format=_CL)
+        B, Cc, hh, ww = hc.shape
+        z = F.linear(hc.permute(0, 2, 3, 1).reshape(B * hh * ww, Cc), wb[0], wb[1])
+        y1 = self.cr.R.head_upconv_gather(z.view(B, hh, ww, -1), tgt, self.conv1.out_channels)
+        self.cr.pipe._count_flops(2.0 * self.proj.out_channels * hh * ww * Cc)   # the module graph's count: what conv_nb adds for the projection (on the coarse map) ...
+        self.cr.pipe._count_conv(self.conv1, y1)                                # ... and for conv1
+        return y1
+
+
+class _HeadFusedRoute(_Route):
+    """"f32-fused": the head's up-sampling, its second convolution and everything behind it as ONE exact-float32 MFMA launch (vd3d_dpt_head_conv_f32: 32 | 64 | 128 ->
+    32 channels).  conv_routes["head.conv2"] reads ("f32-fused", ...), or ("library", reason) where the three launches stay (a shape that is not built,
+    VD3D_HEAD_FUSED=0).  For 32 | 64 input channels (HEAD_CONV2_GATHER_ROUTED: a rule on the shape alone) the launch takes the "coarse GEMM + fine gather" form
+    (vd3d_head_conv_gather_f32, composed by head_conv2_compose: all channel mixing on the coarse map, Z kept in LDS, a third of conv2's flops, close but not equal
+    bits) where the launch is not refused; the reason string names the form, VD3D_HEAD_CONV2_GATHER=0 switches back and =1 routes every built count.  Operand: (image, form)."""
+    label = "f32-fused"
+
+    def __init__(self, cr, head, tail):
+        self.cr, self.head, self.tail, self.modules = cr, head, tail, (head.conv2,)
+        self.img = _PerVersion(lambda: cr.R.dpt_head_conv_pack(head.conv2.weight) if head.conv2.out_channels == 32 else None)
+        self.gimg = _PerVersion(lambda: cr.R.head_conv_gather_pack(*head_conv2_compose(head.conv2.weight, head.conv1.bias)))
+
+    def decide(self, in_size, size):
+        head, m, sw = self.head, self.head.conv2, _switch("VD3D_HEAD_CONV2_GATHER")
+        if not _switch("VD3D_HEAD_FUSED"):
+            return None, "VD3D_HEAD_FUSED=0"
+        if not _is_conv(m, 3, 1, 1):
+            return None, "not a 3 x 3 / stride 1 / padding 1 convolution"
+        img = self.img.get(m.weight)
+        if img is None:
+            return None, f"shape not built: {m.in_channels} -> {m.out_channels} channels"
+        if head.conv1.bias.data_ptr() % 16 or m.bias.data_ptr() % 16 or self.tail()[0].data_ptr() % 16:
+            return None, "a bias or the 1x1 weight is not 16-byte aligned"
+        if size[0] < 2 or size[1] < 2:
+            return None, f"output {size[0]} x {size[1]} below 2 x 2"
+        # the gather form: where the channel count is routed, a tile serves the ratio (else the launch would be refused) and the image is built
+        if (sw is not False and m.out_channels == 32 and m.in_channels in (HEAD_CONV2_GATHER_BUILT if sw else HEAD_CONV2_GATHER_ROUTED) and m.padding_mode == "zeros"
+                and self.cr.R.head_conv_gather_tile(in_size, size, m.in_channels) is not None and self.gimg.get(m.weight, head.conv1.bias) is not None):
+            return (self.gimg.value, "gather"), f"{m.in_channels} -> {m.out_channels} channels, form gather (coarse GEMM + fine gather)"
+        return (img, "conv"), f"{m.in_channels} -> {m.out_channels} channels, form conv"
+
+
+class _FusionStage:
+    """The fusion stage of ``pipe`` (transformers FeatureFusionLayer / PreActResidualLayer, reproduced verbatim otherwise; DA and DPT alike) with the float32 glue on:
+    every convolution runs WITHOUT its bias pass (_ConvRouter.conv_nb) and the glue between two convolutions is one HIP launch -- bias + ReLU in place behind a
+    unit's first convolution; bias + unit input (+ the fusion layer's running state) behind its second one, which also writes the ReLU'd copy the next unit starts
+    from; the layer's 1 x 1 projection runs BEFORE its up-sampling (both are linear and per-pixel / per-channel: conv1x1(up(x)) == up(conv1x1(x)), a quarter of the
+    pixels) and hands its bias to the up-sampling kernel (interpolation weights sum to one).  The last layer hands its coarse map to ``upconv`` where that route runs."""
+
+    def __init__(self, pipe, cr, upconv=None):
+        self.pipe, self.cr, self.upconv, self.last = pipe, cr, upconv, pipe.model.neck.fusion_stage.layers[-1]
+        for layer in pipe.model.neck.fusion_stage.layers:
+            layer.forward = lambda hidden_state, residual=None, size=None, layer=layer: self.forward(layer, hidden_state, residual, size)
+
+    def res_unit(self, unit, x, x_relu=None, extra=None, want_relu=False):
+        """PreActResidualLayer: conv2(relu(conv1(relu(x)))) + x [then extra + that]; optionally also relu(result)."""
+        R, conv_nb = self.cr.R, self.cr.conv_nb
+        x = x.contiguous(memory_format=_CL)
+        h = torch.relu(x) if x_relu is None else x_relu
+        y = R.bias_act(conv_nb(unit.convolution1, h), unit.convolution1.bias, relu=True)
+        y = conv_nb(unit.convolution2, y)
+        return R.bias_act(y, unit.convolution2.bias, r1=x, r2=extra, want_relu_copy=want_relu)
+
+    def forward(self, layer, hidden_state, residual, size):
+        cr, res_unit, up = self.cr, self.res_unit, self.upconv
+        fused = cr.f32 and hidden_state.dtype == torch.float32 and hidden_state.shape[1] % 4 == 0
+        if residual is not None:
+            if hidden_state.shape != residual.shape:
+                residual = F.interpolate(residual, size=(hidden_state.shape[2], hidden_state.shape[3]), mode="bilinear", align_corners=False)
+            if fused:
+                hidden_state, hr = res_unit(layer.residual_layer1, residual, extra=hidden_state.contiguous(memory_format=_CL), want_relu=True)
+                hidden_state = res_unit(layer.residual_layer2, hidden_state, x_relu=hr)
+            else:
+                hidden_state = layer.residual_layer2(hidden_state + layer.residual_layer1(residual))
+        else:
+            hidden_state = res_unit(layer.residual_layer2, hidden_state) if fused else layer.residual_layer2(hidden_state)
+        tgt = (2 * hidden_state.shape[2], 2 * hidden_state.shape[3]) if size is None else tuple(size)
+        if cr.sc and not (fused and layer.projection.bias is not None):
+            raise NotImplementedError(f"self_contained=True: {cr.names[id(layer)]}: a float32 map with channels in multiples of 4 and a projection with a bias expected")
+        if fused and layer is self.last and up is not None and up.armed:
+            wb, _ = up.route(tgt)
+            if wb is not None:
+                up.pending = (hidden_state, tgt, wb)
+                return hidden_state   # the residual output on the coarse map: the head runs the composed GEMM and the gather on it
+        if fused and layer.projection.bias is not None:
+            return cr.R.upsample_bilinear_bias((cr.conv1x1_x3 if cr.sc else cr.conv_nb)(layer.projection, hidden_state), tgt, layer.projection.bias)
+        return layer.projection(cr.up(hidden_state, tgt))
+
+
+class _DaHead:
+    """Depth-Anything's DepthEstimationHead in three forms.  With the float32 glue on and a head of the stock shape ([conv 3 x 3, up-sampling, conv 3 x 3 -> 16 / 32 /
+    64, ReLU, conv 1 x 1, ReLU] with biases; the metric heads' Sigmoid() * max_depth under self_contained=True only -- without the keyword they route as they always
+    did): conv1 bias-free (or the ``upconv`` route's gather on the coarse map the last fusion layer handed through), then either ONE launch for the rest (``fused``,
+    in conv or gather form) or the three-launch tail (_ConvRouter.head_tail3).  Anything else: the stock module graph on vd3d_upsample_bilinear_nhwc."""
+
+    def __init__(self, pipe, cr):
+        self.pipe, self.cr, self.head, self.tail, self.fused, self.upconv = pipe, cr, pipe.model.head, None, None, None
+        head, sc, layers = self.head, pipe.self_contained, pipe.model.neck.fusion_stage.layers
+        self.tail_act = "relu" if isinstance(head.activation2, torch.nn.ReLU) else "sigmoid" if sc and isinstance(head.activation2, torch.nn.Sigmoid) else None
+        if (cr.f32 and self.tail_act is not None and head.conv2.out_channels in (16, 32, 64) and head.conv3.kernel_size == (1, 1)
+                and head.conv2.bias is not None and head.conv3.bias is not None and head.conv1.bias is not None):
+            self.tail = _head_tail_operands(head.conv3)
+        if sc and self.tail is None:
+            raise NotImplementedError(f"self_contained=True: {pipe.name!r}: a depth head other than [conv 3 x 3, up-sampling, conv 3 x 3 -> 16 / 32 / 64, ReLU, conv 1 x 1, "
+                                      f"ReLU | Sigmoid] with biases (its last activation is {type(head.activation2).__name__}) -- not built")
+        if pipe.gemm == "f32" and pipe.device.type == "cuda" and self.tail is not None:   # (the kernels read device memory: a pipe on the CPU keeps its graph)
+            self.fused = _HeadFusedRoute(cr, head, self.tail)
+            if head.head_in_index in (-1, len(layers) - 1):
+                self.upconv = _UpconvRoute(cr, layers[-1].projection, head.conv1)
+        head.forward = self.forward
+
+    def forward(self, hidden_states, patch_height, patch_width):
+        head, cr = self.head, self.cr
+        x = hidden_states[head.head_in_index]
+        size = (int(patch_height * head.patch_size), int(patch_width * head.patch_size))
+        pend = self.upconv.take(x) if self.upconv is not None else None
+        if self.tail is None or x.dtype != torch.float32:
+            h = cr.up(head.conv1(x), size)
+            h = head.conv3(head.activation1(head.conv2(h)))
+            return (head.activation2(h) * head.max_depth).squeeze(dim=1)
+        op = self.fused.route((int(x.shape[2]), int(x.shape[3])) if pend is None else pend[1], size)[0] if self.fused is not None else None
+        y1 = self.upconv.run(*pend) if pend is not None else cr.conv_nb(head.conv1, x.contiguous(memory_format=_CL))   # head.conv1 without its bias
+        if op is None:
+            return cr.head_tail3(y1, head.conv1, head.conv2, size, self.tail, float(head.max_depth), self.tail_act)
+        n_out = float(head.conv2.out_channels) * size[0] * size[1]
+        self.pipe._count_flops(2.0 * n_out * head.conv2.in_channels * 9 + 2.0 * n_out)   # exactly what conv_nb(head.conv2, .) and head_tail3's tail line add
+        return cr.R.dpt_head_conv(y1, head.conv1.bias, size, op[0], head.conv2.bias, *self.tail(), float(head.max_depth), form=op[1])
+
 
 class DepthPipe:
     """``pipe(images, inference_size=None) -> [{"predicted_depth": Tensor[h, w]}]`` (reference protocol) plus a
@@ -510,32 +857,15 @@ class DepthPipe:
         The split modes cover the DINOv2 family (Depth-Anything V1 / V2, Distill-Any-Depth) and DPT-Large (a plain-ViT ``DPTForDepthEstimation`` with
         readout_type="project"; its readout / 1x1 projections and the transposed convolutions of the reassemble stage go on ``vd3d_gemm_x3`` too, see
         ``_patch_dpt_vit_reassemble_head``) and DPT-Hybrid in its published geometry (``"dpt-hybrid-midas"``, MiDaS 3.0: ViT-B/16 behind a BiT ResNet-50 prefix;
-        ``_split_scope`` states the geometry): the ViT layers, the 1 x 1 embedding projection of the prefix's stage-3 map and hooks 2 / 3 of the reassemble stage
-        run as for DPT-Large, hooks 0 / 1 are the prefix's stage-1 / stage-2 maps and go to the neck as they are, and the prefix itself stays the module graph on the
-        float32 library (``conv_routes`` says so per module) unless ``self_contained`` is given.  Anything else -- any other hybrid, BEiT / Swin backbones, ZoeDepth,
-        DepthPro -- raises NotImplementedError; with ``gemm="f32"`` a DPT model runs its stock module graph unchanged.
+        ``_split_scope`` states the geometry; ``_patch_hybrid_embeddings`` what runs where: the prefix stays the module graph on the float32 library unless
+        ``self_contained`` is given).  Anything else -- any other hybrid, BEiT / Swin backbones, ZoeDepth, DepthPro -- raises NotImplementedError; with ``gemm="f32"``
+        a DPT model runs its stock module graph unchanged.
         ``conv``: ``None`` (default) -- the 3 x 3 convolutions of the DPT neck / fusion stage / head run as they always did per mode: library float32
-        convolutions in ``"f32"`` and ``"bf16x3"``, ``vd3d_conv3x3_x2`` where its rules allow in ``"fp16x2"``.  ``"bf16x3"`` -- OPT-IN, only with
-        ``gemm="bf16x3"`` (else ValueError): the 3 x 3 / stride 1 / padding 1 convolutions -- ``neck.convs``, the fusion stage's residual units, the head's
-        two (DA and DPT-Large alike) -- run on ``vd3d_conv3x3_x3``, the same three-term / six-product arithmetic as the GEMM (include/vd3d.h), for 32 / 64 /
-        128 / 256 output channels and input channels in multiples of 16.  Maps below the measured launch-size rule (``CONV_X3_MIN_TILES``) stay on the
-        library; nothing else falls back.  ``conv_routes`` (module name -> ("bf16x3" | "library", reason)) records, per forward, where each of these
-        convolutions ran and why.  ``"fp16x2"`` -- OPT-IN, only with ``gemm="fp16x2"`` (else ValueError): the same convolutions, for the same channel
-        counts, on ``vd3d_conv3x3_s1_x2`` -- the same 8 x 32 tile kernel in the two-term fp16 arithmetic of the mode (three products per MAC, weights
-        pre-scaled per output channel by an exact power of two, |x| < 65 504).  One kernel takes every routed convolution (``vd3d_conv3x3_x2`` stays the route
-        of ``conv=None``); maps below ``CONV_X2_MIN_TILES`` tiles PER FRAME stay on the library -- the rule reads the map and the module, never the batch
-        size; ``conv_routes`` reads ("fp16x2" | "library", reason).  In the default float32 mode (``gemm="f32"``, ``conv=None``, with a renderer) the head's up-sampling, its second
-        convolution and everything behind it run as ONE exact-float32 MFMA launch (``vd3d_dpt_head_conv_f32``: 32 | 64 | 128 -> 32 channels);
-        ``conv_routes["head.conv2"]`` is then ``("f32-fused", ...)``, or ``("library", reason)`` where the three launches stay (a shape that is not
-        built, ``VD3D_HEAD_FUSED=0``).  For 32 | 64 input channels (``HEAD_CONV2_GATHER_ROUTED``) that launch takes the "coarse GEMM + fine gather" form
-        (``vd3d_head_conv_gather_f32``, composed per parameter version by ``head_conv2_compose``: all channel mixing on the coarse map, Z kept in LDS, close but
-        not equal bits); the reason string names the form, ``VD3D_HEAD_CONV2_GATHER=0`` switches back and ``=1`` routes every built count.  In the same mode (not ``self_contained``) the up-scaling reassemble stages' transposed convolution and the 3 x 3 neck
-        convolution behind it run as ONE exact-float32 MFMA launch on the coarse map (``vd3d_neck_poly_conv_f32``, composed per parameter version by
-        ``neck_poly_compose``: DA-V2-Base's and -Small's shapes); ``conv_routes["neck.reassemble_stage.layers.{0,1}.resize"]`` and ``["neck.convs.{0,1}"]`` are
-        then ``("f32-poly", ...)``, or ``("library", reason)`` (a shape that is not built, ``VD3D_NECK_POLY=0``).
-        There too the last fusion layer's biased 1 x 1 projection, its up-sampling and ``head.conv1`` run as one library GEMM on the coarse map (``head_upconv_compose``:
-        C -> 9 C_out channels) and ``vd3d_head_upconv_gather_f32`` on the fine one; ``conv_routes["neck.fusion_stage.layers.<last>.projection"]`` and ``["head.conv1"]`` are
-        then ``("f32-upconv", ...)``, or ``("library", reason)`` (a shape that is not built, ``VD3D_HEAD_UPCONV=0``).
+        convolutions in ``"f32"`` and ``"bf16x3"``, ``vd3d_conv3x3_x2`` where its rules allow in ``"fp16x2"``.  ``"bf16x3"`` / ``"fp16x2"`` -- OPT-IN, only with
+        the ``gemm`` of the same name (else ValueError): the 3 x 3 / stride 1 / padding 1 convolutions of the neck, the fusion stage and the head (DA and DPT-Large
+        alike) run on the tile convolution of the mode above a measured launch-size rule, and ``conv_routes`` (module name -> (mode | "library", reason)) records, per
+        forward, where each ran and why: ``_ConvRouter``.  The default float32 mode (``gemm="f32"``, hence ``conv=None``; with a renderer) composes three routes of its own, each
+        recorded in ``conv_routes`` and each with an A/B switch (``_SWITCHES``): ``_HeadFusedRoute`` ("f32-fused"), ``_PolyRoute`` ("f32-poly"), ``_UpconvRoute`` ("f32-upconv").
         ``renderer``: a ``visiondepth3d_amd.render_3d.Renderer`` on the SAME stream as the network (default stream); when given the
         image-processor front end, the residual-add + LayerNorm pairs and the DPT up-samplings run as fused HIP launches.
         ``model`` / ``processor``: an already constructed Hugging Face depth model and its image-processor constants
@@ -549,26 +879,14 @@ class DepthPipe:
         ``self_contained``: ``False`` (default) -- everything above.  ``True`` -- OPT-IN, only with ``gemm="bf16x3"``, ``conv="bf16x3"`` or ``gemm="fp16x2"``, ``conv="fp16x2"``, float32, a renderer on a
         GPU and ``fuse_backbone=True`` (else ValueError naming what is missing), and only for the models of the split modes -- ``DepthAnythingForDepthEstimation`` on
         ``Dinov2Backbone`` whose head ends in ReLU (relative) or Sigmoid (metric: Depth-Anything-V2-Metric-*), and DPT-Large as ``_split_scope`` accepts it
-        and DPT-Hybrid likewise (else NotImplementedError naming the model, raised before the renderer or a device is touched): the forward makes NO hipBLASLt / MIOpen / AOTriton call.  On top of the two split modes, the patch embedding runs
-        as ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, the reassemble stage's 1 x 1 projections as ``vd3d_gemm_x3`` over the token rows, its transposed
-        convolutions as ``vd3d_gemm_x3`` + ``vd3d_depth_to_space_bias_nhwc_f32``, its 3 x 3 stride-2 convolution on ``vd3d_conv3x3_s2_x3``, the fusion layers'
-        1 x 1 projections as ``vd3d_gemm_x3`` over the pixel rows, and EVERY 3 x 3 stride-1 convolution on ``vd3d_conv3x3_x3`` (no size rule).  A module the
-        mode cannot route is refused by name, never handed to a library.  ``conv_routes`` names every routed module and holds no ``"library"`` value.  The
-        library selection is skipped: TunableOp is not enabled, ``torch.backends.cudnn.benchmark`` is not touched, ``tuned_gemm`` / ``miopen_find`` read
-        False.  Per output element every kernel sums in one fixed order and nothing is split along K, so a frame's prediction does not depend on the batch it
-        is in or on the ROCm release's solution tables.  With the fp16x2 pair every route above takes that mode's kernels (``vd3d_gemm_x3`` and
-        ``vd3d_attention_x3`` in mode fp16x2, ``vd3d_conv3x3_s2_x2``, ``vd3d_conv3x3_s1_x2``), the route labels read ``("fp16x2", "self-contained...")`` and
-        the mode's range contract holds in front of every one of them.  A metric head's ``Sigmoid() * max_depth`` runs inside the tail launch
-        (``vd3d_dpt_head_tail_act_f32``: torch.sigmoid's CPU values); without the keyword a metric model routes as it always did, its head the module graph.
-        DPT-Large under the keyword: its patch embedding (16 x 16, K = 768) takes the same patchify + GEMM route, the reassemble stage keeps the split modes'
-        readout / projection / transposed-convolution GEMMs and runs hook 3's 3 x 3 stride-2 convolution on the stride-2 tile convolution, and ``neck.convs``,
-        the fusion stage and the head's two 3 x 3 convolutions take the tile convolution at every map size (4 x 4 to 48 x 48 at 384 x 384).
-        DPT-Hybrid under the keyword: the BiT prefix runs on own kernels too (``_BitPrefix``), on float32 NHWC rows from the first launch to the last -- the weight
-        standardisation folded once at construction (``bit_standardized_weight``: the module's own expression, on the CPU), 1 x 1 convolutions as ``vd3d_gemm_x3``
-        over the pixel rows, 3 x 3 stride-1 convolutions on the tile convolution of the mode, everything strided (the 7 x 7 stem, two 3 x 3, two 1 x 1 shortcuts; TensorFlow
-        "same" padding) as ``vd3d_im2col_nhwc_f32`` + ``vd3d_gemm_x3``, every GroupNorm(32) with its ReLU / shortcut add as ``vd3d_groupnorm_nhwc_f32`` (one fixed
-        summation order: batch-independent, bit-repeatable) and the stem's pool as ``vd3d_maxpool3x3_s2_nhwc_f32``.  A prefix module the mode does not build (a bias, a
-        pre-activation layer, groups other than 32, ``global_padding`` other than "same") is refused by name before the renderer or a device is touched."""
+        and DPT-Hybrid likewise (else NotImplementedError naming the model, raised before the renderer or a device is touched): the forward makes NO hipBLASLt / MIOpen / AOTriton call.
+        On top of the two split modes every remaining convolution takes a kernel of the mode's pair -- the patch embedding (``_patch_patch_embedding``), the reassemble
+        stage (``_self_contained_reassemble``; DPT: ``_patch_dpt_vit_reassemble_head``), ``neck.convs``, the fusion stage and the head at every map size
+        (``_ConvRouter``, ``_DaHead``: a metric head's ``Sigmoid() * max_depth`` runs inside the tail launch), DPT-Hybrid's BiT prefix (``_BitPrefix``) -- and a module
+        the mode cannot route is refused by name, never handed to a library.  ``conv_routes`` names every routed module and holds no ``"library"`` value; with the
+        fp16x2 pair its labels read ``("fp16x2", "self-contained...")`` and the mode's range contract holds in front of every route.  The library selection is skipped:
+        TunableOp is not enabled, ``torch.backends.cudnn.benchmark`` is not touched, ``tuned_gemm`` / ``miopen_find`` read False.  Per output element every kernel sums
+        in one fixed order and nothing is split along K, so a frame's prediction does not depend on the batch it is in or on the ROCm release's solution tables."""
         self.name, self.device, self.dtype = name, torch.device(device), dtype
         if gemm not in ("f32", "bf16x3", "fp16x2"):
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
@@ -581,7 +899,7 @@ class DepthPipe:
                                              ("conv='bf16x3'", pair or gemm != "bf16x3"), ("dtype=torch.float32", dtype == torch.float32),
                                              ("a renderer on a GPU", renderer is not None and torch.device(device).type == "cuda"),
                                              ("fuse_backbone=True", bool(fuse_backbone)),
-                                             ("the neck glue launches (VD3D_NECK_GLUE=0 is set)", os.environ.get("VD3D_NECK_GLUE", "1") != "0")) if not ok]
+                                             ("the neck glue launches (VD3D_NECK_GLUE=0 is set)", _switch("VD3D_NECK_GLUE"))) if not ok]
             if missing:
                 raise ValueError("self_contained=True needs " + ", ".join(missing))
         if conv is not None and gemm != conv:
@@ -638,6 +956,7 @@ class DepthPipe:
         self.model = model.eval().to(self.device, dtype)
         if channels_last and self.device.type == "cuda":
             self.model = self.model.to(memory_format=torch.channels_last)
+        self._names = {id(m): n for n, m in self.model.named_modules()}   # built once, here: every rewrite and every conv_routes key reads it
         self.mean = torch.tensor(self.proc["mean"], device=self.device, dtype=torch.float32).view(1, 3, 1, 1)
         self.std = torch.tensor(self.proc["std"], device=self.device, dtype=torch.float32).view(1, 3, 1, 1)
         self.n_params = sum(p.numel() for p in self.model.parameters())
@@ -746,359 +1065,52 @@ class DepthPipe:
 
     def _count_conv(self, m, y):
         """flops_per_frame: a convolution module m that a rewrite runs without calling it adds, for its output y, what the counting hook would have added."""
+        self._count_flops(2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1])
+
+    def _count_flops(self, n: float):
+        """flops_per_frame: ``n`` flops a rewrite executes outside any counted convolution module (the only two places that add to the count: this and _count_conv)."""
         if self._flop_count is not None:
-            self._flop_count[0] += 2.0 * y.numel() / y.shape[0] * (m.in_channels // m.groups) * m.kernel_size[0] * m.kernel_size[1]
+            self._flop_count[0] += n
 
     def _patch_dpt_upsampling(self):
-        """The DPT neck / head between the library convolutions (transformers DepthAnythingReassembleStage / PreActResidualLayer /
-        FeatureFusionLayer / DepthEstimationHead; the module graphs are otherwise reproduced verbatim):
-          * the align_corners=True bilinear up-samplings run on vd3d_upsample_bilinear_nhwc;
-          * float32 (the reference's precision): every convolution runs WITHOUT its bias pass and the glue between two convolutions is one
-            HIP launch -- bias + ReLU in place behind a unit's first convolution; bias + unit input (+ the fusion layer's running state) behind
-            its second one, which also writes the ReLU'd copy the next unit starts from; a convolution in front of an up-sampling hands its bias
-            to the up-sampling kernel (interpolation weights sum to one); the fusion layer's 1x1 projection runs BEFORE its up-sampling (both
-            are linear and per-pixel / per-channel: conv1x1(up(x)) == up(conv1x1(x)), a quarter of the pixels); behind the head's second
-            convolution one launch does bias, ReLU, the 1x1 convolution to one channel, bias, ReLU and max_depth (vd3d_dpt_head_tail_f32);
-          * the reassemble stage hands the token tensor to its 1x1 projection as a channels_last VIEW ([B,T,C] minus CLS is NHWC storage)
-            instead of a NCHW copy that MIOpen converts back.
-        Same function as the module graph up to float32 association (tests/test_hip_depth_e2e.py: 1e-4 of the range on the prediction,
-        identical uint8 planes up to the stated bar)."""
-        R = self.renderer
-        f32 = self.dtype == torch.float32 and os.environ.get("VD3D_NECK_GLUE", "1") != "0"   # 0: A/B switch back to the module graph's own passes
-        CL = torch.channels_last
-        sc = self.self_contained   # no library call: what cannot be routed to a kernel of this library is refused (the constructor has checked float32 + glue)
+        """The DPT neck / head between the library convolutions (transformers DepthAnythingReassembleStage / PreActResidualLayer / FeatureFusionLayer /
+        DepthEstimationHead; the module graphs are otherwise reproduced verbatim): _ConvRouter (where each convolution runs, per mode), _FusionStage, the head (_DaHead,
+        or DPT's in _patch_dpt_vit_reassemble_head) and the reassemble stage (_patch_da_reassemble, or DPT's).  The align_corners=True bilinear up-samplings run on
+        vd3d_upsample_bilinear_nhwc.  Same function as the module graph up to float32 association (tests/test_hip_depth_e2e.py: 1e-4 of the range on the prediction,
+        identical uint8 planes up to the stated bar).  VD3D_NECK_GLUE is read here, once: "0" is the A/B switch back to the module graph's own passes."""
+        cr = _ConvRouter(self, self.dtype == torch.float32 and _switch("VD3D_NECK_GLUE"))
+        if self.dpt_vit:
+            _FusionStage(self, cr)
+            return self._patch_dpt_vit_reassemble_head(cr)
+        _FusionStage(self, cr, _DaHead(self, cr).upconv)
+        self._patch_da_reassemble(cr)
 
-        def up(x, size):
-            if x.dtype in (torch.bfloat16, torch.float32) and x.shape[1] % 8 == 0 and x.is_contiguous(memory_format=CL):
-                return R.upsample_bilinear(x, size)
-            return F.interpolate(x, size=size, mode="bilinear", align_corners=True)
-
-        conv_img = {}   # fp16x2 mode: packed weights per convolution module (None = shape not built: the library convolution stays)
-
-        def conv_x2(m, x):
-            if self.gemm != "fp16x2" or self.conv is not None or not f32 or not _is_conv(m, 3, 1, 1) or x.dtype != torch.float32:
-                return None
-            key = id(m)
-            if key not in conv_img:
-                conv_img[key] = R.conv3x3_x2_pack(m.weight)
-            if conv_img[key] is None:
-                return None
-            # one workgroup per 16 x 32 output tile: below one tile per CU the library's split-K kernels win (19 x 33 maps with 768 input channels: measured 0.43 vs 0.17 ms)
-            if x.shape[0] * ((x.shape[2] + 15) // 16) * ((x.shape[3] + 31) // 32) < 256:
-                return None
-            return R.conv3x3_x2(x.contiguous(memory_format=CL), conv_img[key], m.out_channels)
-
-        conv3_img = {}   # conv="bf16x3" / "fp16x2": packed weights per convolution module (None = shape not built)
-        names = {id(m): n for n, m in self.model.named_modules()}
-        cm = self.conv   # the tile convolution of the mode (Renderer.TILE_CONVS: vd3d_conv3x3_x3 | vd3d_conv3x3_s1_x2), one kernel for every routed convolution
-        min_tiles = CONV_X2_MIN_TILES if cm == "fp16x2" else CONV_X3_MIN_TILES
-
-        def conv_x3(m, x):
-            if cm is None or not f32 or not _is_conv(m, 3, 1, 1) or x.dtype != torch.float32:
-                return None
-            key = id(m)
-            if key not in conv3_img:
-                conv3_img[key] = R.conv3x3_tile_pack(m.weight, cm, 1)
-            if conv3_img[key] is None:
-                if sc:
-                    raise NotImplementedError(f"self_contained=True: {names[key]}: vd3d_conv3x3_{R.TILE_CONVS[cm, 1]} does not build {m.in_channels} -> {m.out_channels} channels")
-                self.conv_routes[names[key]] = ("library", f"shape not built: {m.in_channels} -> {m.out_channels} channels")
-                return None
-            if sc:   # no size rule: every map, the 19 x 33 ones included
-                self.conv_routes[names[key]] = (cm, "self-contained")
-                return R.conv3x3_tile(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels, cm, 1)
-            if cm == "fp16x2":   # the rule of this mode reads the map alone, never the batch: a frame's route and bits do not depend on what it is batched with
-                tiles = ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)
-            else:
-                tiles = x.shape[0] * ((x.shape[2] + 7) // 8) * ((x.shape[3] + 31) // 32)   # one workgroup per 8 x 32 output tile
-            if tiles < min_tiles:
-                self.conv_routes[names[key]] = ("library", f"size rule: {tiles} tiles < {min_tiles}")
-                return None
-            self.conv_routes[names[key]] = (cm, f"{tiles} tiles")
-            return R.conv3x3_tile(x.contiguous(memory_format=CL), conv3_img[key], m.out_channels, cm, 1)
-
-        if cm is not None and f32:   # neck.convs (3 x 3, no bias) are plain module calls in the stock neck: route them too (their forward hooks still count)
-            for m in self.model.neck.convs:
-                if sc and m.bias is not None:
-                    raise NotImplementedError(f"self_contained=True: {names[id(m)]} has a bias (the stock neck convolutions have none) -- not built")
-                if m.bias is None:
-                    def neck_conv_fwd(x, m=m):
-                        y = conv_x3(m, x)
-                        if y is None and sc:
-                            raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 3 x 3 / stride 1 / padding 1 convolution -- not built")
-                        return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups) if y is None else y
-                    m.forward = neck_conv_fwd
-
-        def conv_nb(m, x):   # the module's convolution without its bias
-            y = conv_x2(m, x)
-            if y is None:
-                y = conv_x3(m, x)
-            if y is None and sc:
-                raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 3 x 3 / stride 1 / padding 1 convolution -- not built")
-            if y is None:
-                y = F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups).contiguous(memory_format=CL)
-            self._count_conv(m, y)   # these calls bypass the modules' forward hooks
-            return y
-
-        gemm_img = {}   # self-contained: packed weights of the 1 x 1 projections / transposed convolutions per module
-
-        def conv1x1_x3(m, x):
-            """Self-contained: a 1 x 1 convolution WITHOUT its bias as vd3d_gemm_x3 over the pixel rows of a channels_last map (its NHWC storage is the row matrix)."""
-            if not _is_conv(m, 1, 1, 0) or m.in_channels % 16 or x.dtype != torch.float32:
-                raise NotImplementedError(f"self_contained=True: {names[id(m)]} is not a float32 1 x 1 convolution with C_in a multiple of 16 -- not built")
-            if id(m) not in gemm_img:
-                gemm_img[id(m)] = R.gemm_x3_pack(m.weight.reshape(m.out_channels, m.in_channels), self.gemm)
-            rows = x.contiguous(memory_format=CL).permute(0, 2, 3, 1)   # [B, h, w, C] contiguous
-            y = R.linear_x3(rows, gemm_img[id(m)], m.out_channels, None, mode=self.gemm).permute(0, 3, 1, 2)
-            self.conv_routes[names[id(m)]] = (self.gemm, "self-contained: vd3d_gemm_x3 over the pixel rows")
-            self._count_conv(m, y)   # what conv_nb adds for the same module
-            return y
-
-        def res_unit(unit, x, x_relu=None, extra=None, want_relu=False):
-            """PreActResidualLayer: conv2(relu(conv1(relu(x)))) + x [then extra + that]; optionally also relu(result)."""
-            x = x.contiguous(memory_format=CL)
-            h = torch.relu(x) if x_relu is None else x_relu
-            y = R.bias_act(conv_nb(unit.convolution1, h), unit.convolution1.bias, relu=True)
-            y = conv_nb(unit.convolution2, y)
-            return R.bias_act(y, unit.convolution2.bias, r1=x, r2=extra, want_relu_copy=want_relu)
-
-        # float32 mode: the LAST fusion layer's projection, its up-sampling and head.conv1 as coarse GEMM + fine gather (head_upconv_compose).  "route": set below
-        # where the route exists; "armed": inside the model's own forward, where the head consumes the neck's output (the neck called alone materialises the
-        # up-sampled projection as ever); "pending": what the last fusion layer hands to head_fwd in this forward.
-        upconv = {"route": None, "armed": False, "pending": None}
-        last_fusion = self.model.neck.fusion_stage.layers[-1]
-
-        for layer in self.model.neck.fusion_stage.layers:
-            def fusion_fwd(hidden_state, residual=None, size=None, layer=layer):
-                fused = f32 and hidden_state.dtype == torch.float32 and hidden_state.shape[1] % 4 == 0
-                if residual is not None:
-                    if hidden_state.shape != residual.shape:
-                        residual = F.interpolate(residual, size=(hidden_state.shape[2], hidden_state.shape[3]), mode="bilinear",
-                                                 align_corners=False)
-                    if fused:
-                        hidden_state, hr = res_unit(layer.residual_layer1, residual, extra=hidden_state.contiguous(memory_format=CL), want_relu=True)
-                        hidden_state = res_unit(layer.residual_layer2, hidden_state, x_relu=hr)
-                    else:
-                        hidden_state = layer.residual_layer2(hidden_state + layer.residual_layer1(residual))
-                else:
-                    hidden_state = res_unit(layer.residual_layer2, hidden_state) if fused else layer.residual_layer2(hidden_state)
-                tgt = (2 * hidden_state.shape[2], 2 * hidden_state.shape[3]) if size is None else tuple(size)
-                if sc and not (fused and layer.projection.bias is not None):
-                    raise NotImplementedError(f"self_contained=True: {names[id(layer)]}: a float32 map with channels in multiples of 4 and a projection with a bias expected")
-                if fused and layer is last_fusion and upconv["route"] is not None and upconv["armed"]:
-                    wb, why = upconv["route"](layer, tgt)
-                    self.conv_routes[names[id(layer.projection)]] = self.conv_routes[names[id(self.model.head.conv1)]] = ("f32-upconv" if wb is not None else "library", why)
-                    if wb is not None:
-                        upconv["pending"] = (hidden_state, tgt, wb)
-                        return hidden_state   # the residual output on the coarse map: head_fwd runs the composed GEMM and the gather on it
-                if fused and layer.projection.bias is not None:
-                    return R.upsample_bilinear_bias((conv1x1_x3 if sc else conv_nb)(layer.projection, hidden_state), tgt, layer.projection.bias)
-                return layer.projection(up(hidden_state, tgt))
-            layer.forward = fusion_fwd
-        if getattr(self, "dpt_vit", False):
-            self._patch_dpt_vit_reassemble_head(conv_nb, f32)
+    def _patch_da_reassemble(self, cr):
+        """Depth-Anything's reassemble stage: the token tensor goes to the 1x1 projection as a channels_last VIEW ([B,T,C] minus CLS is NHWC storage) instead of a NCHW copy
+        that MIOpen converts back; the up-scaling stages 0 / 1 hand their coarse map to neck.convs[i] where _PolyRoute runs.  self_contained=True: _self_contained_reassemble."""
+        neck, stage = self.model.neck, self.model.neck.reassemble_stage
+        if self.self_contained:
+            stage.forward = self._self_contained_reassemble()
             return
-        head = self.model.head
-        tail_operands = None
-        # the metric heads (Sigmoid() * max_depth) take the tail kernel under self_contained=True only: without the keyword they route as they always did
-        tail_act = "relu" if isinstance(head.activation2, torch.nn.ReLU) else "sigmoid" if sc and isinstance(head.activation2, torch.nn.Sigmoid) else None
-        if (f32 and tail_act is not None and head.conv2.out_channels in (16, 32, 64) and head.conv3.kernel_size == (1, 1)
-                and head.conv2.bias is not None and head.conv3.bias is not None and head.conv1.bias is not None):
-            tail_operands = _head_tail_operands(head.conv3)
-        if sc and tail_operands is None:
-            raise NotImplementedError(f"self_contained=True: {self.name!r}: a depth head other than [conv 3 x 3, up-sampling, conv 3 x 3 -> 16 / 32 / 64, ReLU, conv 1 x 1, "
-                                      f"ReLU | Sigmoid] with biases (its last activation is {type(head.activation2).__name__}) -- not built")
-
-        # float32 mode: up-sampling + conv2 + tail as ONE exact-float32 MFMA launch (vd3d_dpt_head_conv_f32); VD3D_HEAD_FUSED=0: A/B switch back to the three launches
-        head_fused = self.gemm == "f32" and self.conv != "bf16x3" and self.device.type == "cuda"   # (the kernel reads device memory: a pipe on the CPU keeps its graph)
-        head_img = {}   # the packed conv2 weights per parameter version (None = shape not built)
-
-        def head_conv2_image():
-            m = head.conv2
-            if os.environ.get("VD3D_HEAD_FUSED", "1") == "0":
-                return None, "VD3D_HEAD_FUSED=0"
-            if not _is_conv(m, 3, 1, 1):
-                return None, "not a 3 x 3 / stride 1 / padding 1 convolution"
-            try:
-                key = (m.weight.data_ptr(), m.weight._version)
-            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
-                key = (m.weight.data_ptr(),)
-            if head_img.get("key") != key:
-                head_img["key"], head_img["img"] = key, (R.dpt_head_conv_pack(m.weight) if m.out_channels == 32 else None)
-            if head_img["img"] is None:
-                return None, f"shape not built: {m.in_channels} -> {m.out_channels} channels"
-            if head.conv1.bias.data_ptr() % 16 or m.bias.data_ptr() % 16 or tail_operands()[0].data_ptr() % 16:
-                return None, "a bias or the 1x1 weight is not 16-byte aligned"
-            return head_img["img"], f"{m.in_channels} -> {m.out_channels} channels"
-
-        # ... the same launch in "coarse GEMM + fine gather" form (vd3d_head_conv_gather_f32: a third of conv2's flops), where the channel count is routed
-        # (HEAD_CONV2_GATHER_ROUTED: a rule on the shape alone; VD3D_HEAD_CONV2_GATHER=1 routes every built count, =0 none) and the launch is not refused
-        gather_img = {}   # (parameter versions, (image, bc, C_in) or None)
-
-        def head_conv2_gather(in_size, size):
-            m = head.conv2
-            sw = os.environ.get("VD3D_HEAD_CONV2_GATHER", "")
-            if sw == "0" or m.out_channels != 32 or m.in_channels not in (HEAD_CONV2_GATHER_BUILT if sw == "1" else HEAD_CONV2_GATHER_ROUTED) or m.padding_mode != "zeros":
-                return None
-            if R.head_conv_gather_tile(in_size, size, m.in_channels) is None:   # a ratio no tile serves
-                return None
-            ts = (m.weight, head.conv1.bias)
-            try:
-                key = tuple((t.data_ptr(), t._version) for t in ts)
-            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
-                key = tuple((t.data_ptr(),) for t in ts)
-            if gather_img.get("key") != key:
-                gather_img["key"], gather_img["img"] = key, R.head_conv_gather_pack(*head_conv2_compose(m.weight, head.conv1.bias))
-            return gather_img["img"]
-
-        # float32 mode (where the polyphase neck is on): the last fusion layer's biased 1 x 1 projection, its up-sampling and head.conv1 (3 x 3, zero padding) are one
-        # linear map; all channel mixing runs as ONE library GEMM on the coarse map (C -> 9 C_out channels, composed per parameter version by head_upconv_compose), and
-        # vd3d_head_upconv_gather_f32 sums the 9 taps' bilinear samples per fine pixel: a quarter of conv1's flops, and neither the projected nor the up-sampled map is
-        # written.  VD3D_HEAD_UPCONV=0: A/B switch back.
-        n_fusion = len(self.model.neck.fusion_stage.layers)
-        upconv_on = (self.gemm == "f32" and cm is None and not sc and f32 and self.device.type == "cuda" and tail_operands is not None
-                     and head.head_in_index in (-1, n_fusion - 1))
-        upconv_w = {}   # (parameter versions, (Wc, bc) on the device)
-
-        def upconv_route(layer, tgt):
-            pj, c1 = layer.projection, head.conv1
-            if os.environ.get("VD3D_HEAD_UPCONV", "1") == "0":
-                return None, "VD3D_HEAD_UPCONV=0"
-            if not (_is_conv(pj, 1, 1, 0) and pj.bias is not None and _is_conv(c1, 3, 1, 1) and c1.padding_mode == "zeros" and c1.in_channels == pj.out_channels):
-                return None, "not a biased 1 x 1 projection in front of a 3 x 3 / stride 1 / padding 1 / zeros convolution"
-            if (c1.in_channels, c1.out_channels) not in HEAD_UPCONV_BUILT:
-                return None, f"shape not built: {c1.in_channels} -> {c1.out_channels} channels"
-            if tgt[0] < 2 or tgt[1] < 2:
-                return None, f"output {tgt[0]} x {tgt[1]} below 2 x 2"
-            ts = (pj.weight, pj.bias, c1.weight)
-            try:
-                key = tuple((t.data_ptr(), t._version) for t in ts)
-            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
-                key = tuple((t.data_ptr(),) for t in ts)
-            if upconv_w.get("key") != key:
-                upconv_w["key"], upconv_w["wb"] = key, head_upconv_compose(pj.weight, pj.bias, c1.weight)
-            return upconv_w["wb"], f"{pj.in_channels} -> 9 x {c1.out_channels} channels on the coarse map"
-
-        def upconv_run(hc, tgt, wb):
-            hc = hc.contiguous(memory_format=CL)
-            B, Cc, hh, ww = hc.shape
-            z = F.linear(hc.permute(0, 2, 3, 1).reshape(B * hh * ww, Cc), wb[0], wb[1])   # the NHWC storage is the row matrix
-            y1 = R.head_upconv_gather(z.view(B, hh, ww, -1), tgt, head.conv1.out_channels)
-            if self._flop_count is not None:   # the module graph's count: what conv_nb adds for the projection (on the coarse map) and for conv1
-                self._flop_count[0] += 2.0 * last_fusion.projection.out_channels * hh * ww * Cc
-                self._count_conv(head.conv1, y1)
-            return y1
-
-        if upconv_on:
-            upconv["route"] = upconv_route
-            model_fwd = self.model.forward
-
-            def armed_fwd(*args, **kwargs):   # the head follows the neck in here and nowhere else
-                upconv["armed"], upconv["pending"] = True, None
-                try:
-                    return model_fwd(*args, **kwargs)
-                finally:
-                    upconv["armed"], upconv["pending"] = False, None
-            self.model.forward = armed_fwd
-
-        def head_fwd(hidden_states, patch_height, patch_width):
-            x = hidden_states[head.head_in_index]
-            size = (int(patch_height * head.patch_size), int(patch_width * head.patch_size))
-            pend, upconv["pending"] = upconv["pending"], None
-            if pend is not None and pend[0] is not x:
-                raise RuntimeError("head_upconv: the head did not receive the last fusion layer's output")
-
-            def conv1_nb():   # head.conv1 without its bias: the composed pair on the coarse map the last fusion layer handed through (a float32 map), or the convolution
-                return upconv_run(*pend) if pend is not None else conv_nb(head.conv1, x.contiguous(memory_format=CL))
-            if tail_operands is not None and x.dtype == torch.float32:
-                img = None
-                if head_fused:
-                    img, why = head_conv2_image()
-                    if img is not None and (size[0] < 2 or size[1] < 2):
-                        img, why = None, f"output {size[0]} x {size[1]} below 2 x 2"
-                    gimg = None
-                    if img is not None:
-                        gimg = head_conv2_gather((int(x.shape[2]), int(x.shape[3])) if pend is None else pend[1], size)
-                        why += ", form gather (coarse GEMM + fine gather)" if gimg is not None else ", form conv"
-                    self.conv_routes[names[id(head.conv2)]] = ("f32-fused" if img is not None else "library", why)
-                if img is not None:
-                    y1 = conv1_nb()
-                    if self._flop_count is not None:   # exactly what conv_nb(head.conv2, .) and the tail line below add
-                        n_out = float(head.conv2.out_channels) * size[0] * size[1]
-                        self._flop_count[0] += 2.0 * n_out * head.conv2.in_channels * 9 + 2.0 * n_out
-                    w3, b3 = tail_operands()
-                    if gimg is not None:
-                        return R.dpt_head_conv(y1, head.conv1.bias, size, gimg, head.conv2.bias, w3, b3, float(head.max_depth), form="gather")
-                    return R.dpt_head_conv(y1, head.conv1.bias, size, img, head.conv2.bias, w3, b3, float(head.max_depth))
-                h = R.upsample_bilinear_bias(conv1_nb(), size, head.conv1.bias)
-                y = conv_nb(head.conv2, h)
-                if self._flop_count is not None:
-                    self._flop_count[0] += 2.0 * y.numel() / y.shape[0]   # the 1x1 convolution to one channel inside the tail kernel
-                w3, b3 = tail_operands()
-                if tail_act == "sigmoid":   # vd3d_dpt_head_tail_act_f32
-                    return R.dpt_head_tail(y, head.conv2.bias, w3, b3, float(head.max_depth), act="sigmoid")
-                return R.dpt_head_tail(y, head.conv2.bias, w3, b3, float(head.max_depth))
-            h = up(head.conv1(x), size)
-            h = head.conv3(head.activation1(head.conv2(h)))
-            return (head.activation2(h) * head.max_depth).squeeze(dim=1)
-        head.forward = head_fwd
-        stage = self.model.neck.reassemble_stage
-
-        # float32 mode: the up-scaling stages' ConvTranspose2d (kernel == stride == f, bias) and the bias-free 3 x 3 neck convolution behind it are one linear map;
-        # composed per parameter version on the coarse grid (neck_poly_compose) they run as ONE exact-float32 MFMA launch (vd3d_neck_poly_conv_f32) with 2.25 (f = 4) /
-        # 4 (f = 2) coarse taps per output pixel instead of 9 fine ones, and the fine map between them is never written.  VD3D_NECK_POLY=0: A/B switch back.
-        neck = self.model.neck
-        poly_on = self.gemm == "f32" and cm is None and not sc and f32 and self.device.type == "cuda"
-        poly_stages = [i for i in (0, 1) if poly_on and i < len(stage.layers) and i < len(neck.convs) and isinstance(stage.layers[i].resize, torch.nn.ConvTranspose2d)]
-        poly_img, poly_pending = {}, {}   # per stage: (parameter versions, packed blocks or None); the blocks the reassemble stage hands to neck.convs[i] in this forward
-
-        def poly_route(i):
-            rz, cv = stage.layers[i].resize, neck.convs[i]
-            if os.environ.get("VD3D_NECK_POLY", "1") == "0":
-                return None, "VD3D_NECK_POLY=0"
-            f = rz.kernel_size[0]
-            if not (rz.kernel_size == rz.stride == (f, f) and f >= 2 and rz.padding == (0, 0) and rz.output_padding == (0, 0) and rz.dilation == (1, 1) and rz.groups == 1
-                    and _is_conv(cv, 3, 1, 1) and cv.bias is None and cv.in_channels == rz.out_channels and cv.padding_mode == "zeros"):
-                return None, "not a ConvTranspose2d with kernel == stride in front of a bias-free 3 x 3 / stride 1 / padding 1 convolution"
-            ts = [t for t in (rz.weight, rz.bias, cv.weight) if t is not None]
-            try:
-                key = tuple((t.data_ptr(), t._version) for t in ts)
-            except RuntimeError:   # inference tensors track no version counter (see _head_tail_operands)
-                key = tuple((t.data_ptr(),) for t in ts)
-            if poly_img.get(i, (None, None))[0] != key:
-                poly_img[i] = (key, R.neck_poly_pack(*neck_poly_compose(rz.weight, rz.bias, cv.weight, f), f))   # None: shape not built
-            if poly_img[i][1] is None:
-                return None, f"shape not built: {rz.in_channels} -> {cv.out_channels} channels, factor {f}"
-            return poly_img[i][1], f"{rz.in_channels} -> {cv.out_channels} channels, factor {f}: {len(neck_poly_offsets(f))} composed blocks"
-
-        for i in poly_stages:
-            def poly_conv_fwd(x, i=i, m=neck.convs[i], rz=stage.layers[i].resize):
-                packed = poly_pending.pop(i, None)
-                if packed is None:   # the reassemble stage ran the transposed convolution itself
-                    return F.conv2d(x, m.weight, None, m.stride, m.padding, m.dilation, m.groups)
-                f = rz.kernel_size[0]
-                if self._flop_count is not None:   # what the bypassed transposed convolution's hook adds (the module graph's count; this module's own hook still runs)
-                    self._flop_count[0] += 2.0 * rz.out_channels * (f * x.shape[2]) * (f * x.shape[3]) * rz.in_channels * f * f
-                return R.neck_poly_conv(x.contiguous(memory_format=CL), packed)
-            neck.convs[i].forward = poly_conv_fwd
+        on = self.gemm == "f32" and cr.f32 and self.device.type == "cuda"
+        poly = {i: _PolyRoute(cr, stage.layers[i].resize, neck.convs[i]) for i in (0, 1)
+                if on and i < len(stage.layers) and i < len(neck.convs) and isinstance(stage.layers[i].resize, torch.nn.ConvTranspose2d)}
 
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
-            poly_pending.clear()
+            for route in poly.values():
+                route.pending = None
             for i, hs in enumerate(hidden_states):
                 B, _, Cn = hs.shape
                 x = hs[:, 1:].reshape(B, patch_height, patch_width, Cn).permute(0, 3, 1, 2)   # NHWC storage, NCHW view: channels_last
-                if i in poly_stages:
-                    packed, why = poly_route(i) if x.dtype == torch.float32 else (None, f"{x.dtype} map")
-                    route = ("f32-poly" if packed is not None else "library", why)
-                    self.conv_routes[names[id(stage.layers[i].resize)]] = self.conv_routes[names[id(neck.convs[i])]] = route
-                    if packed is not None:
-                        poly_pending[i] = packed
+                if i in poly:
+                    poly[i].pending = poly[i].route(x)[0]
+                    if poly[i].pending is not None:
                         out.append(stage.layers[i].projection(x))   # the coarse map; neck.convs[i] is the composed launch
                         continue
                 out.append(stage.layers[i](x))
             return out
-        stage.forward = self._self_contained_reassemble(names) if sc else reassemble_fwd
+        stage.forward = reassemble_fwd
 
     def _self_contained_resize(self, rz, name):
         """The resize module ``rz`` (``name``) of a reassemble layer under self_contained=True -> (kind, operand): ("ct", _ConvTransposeGemm) for a ConvTranspose2d with a
@@ -1136,7 +1148,7 @@ class DepthPipe:
             self.conv_routes[name] = (gm, "self-contained: vd3d_conv3x3_" + R.TILE_CONVS[gm, 2])
         return x
 
-    def _self_contained_reassemble(self, names):
+    def _self_contained_reassemble(self):
         """The DINOv2 reassemble stage without a library call (self_contained=True): per hook, the tokens minus CLS are the rows of the 1 x 1 projection (linear_x3
         with its bias; [B, T-1, C_i] is NHWC storage); ConvTranspose2d (kernel == stride, no padding) is a _ConvTransposeGemm, as on DPT-Large's route
         (_patch_dpt_vit_reassemble_head); Identity stays; the 3 x 3 / stride 2 / padding 1 convolution runs on the stride-2 tile convolution of the mode
@@ -1147,8 +1159,8 @@ class DepthPipe:
         for lay in stage.layers:
             pm, rz = lay.projection, lay.resize
             if not _is_conv(pm, 1, 1, 0) or pm.in_channels % 16:
-                raise NotImplementedError(f"self_contained=True: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
-            kind, img = self._self_contained_resize(rz, names[id(rz)])
+                raise NotImplementedError(f"self_contained=True: {self._names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
+            kind, img = self._self_contained_resize(rz, self._names[id(rz)])
             hooks.append(dict(pm=pm, rz=rz, proj=R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm), kind=kind, img=img))
 
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
@@ -1163,9 +1175,9 @@ class DepthPipe:
                 pm, rz = hk["pm"], hk["rz"]
                 n = pm.out_channels
                 x = R.linear_x3(hs[:, 1:].contiguous(), hk["proj"], n, pm.bias, mode=gm)         # [B, T-1, C_i]: NHWC storage
-                self.conv_routes[names[id(pm)]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
+                self.conv_routes[self._names[id(pm)]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
                 self._count_conv(pm, x.view(B, gh, gw, n).permute(0, 3, 1, 2))   # the routed modules bypass the counting hooks: the figure equals the library mode's
-                x = self._self_contained_resize_run(hk["kind"], hk["img"], rz, names[id(rz)], x, B, gh, gw)
+                x = self._self_contained_resize_run(hk["kind"], hk["img"], rz, self._names[id(rz)], x, B, gh, gw)
                 if hk["kind"] != "identity":
                     self._count_conv(rz, x)   # the hook's formula, as the library mode counts these modules
                 out.append(x)
@@ -1179,7 +1191,7 @@ class DepthPipe:
         element-wise / native kernels."""
         R = self.renderer
         m = pe.projection
-        name = next(n for n, mod in self.model.named_modules() if mod is m)
+        name = self._names[id(m)]
         p = m.kernel_size[0]
         if not (isinstance(m, torch.nn.Conv2d) and m.kernel_size == (p, p) and m.stride == (p, p) and m.padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1
                 and m.in_channels == 3 and p <= 64):
@@ -1196,21 +1208,19 @@ class DepthPipe:
             return y
         pe.forward = patch_fwd
 
-    def _patch_dpt_vit_reassemble_head(self, conv_nb, f32):
+    def _patch_dpt_vit_reassemble_head(self, cr):
         """DPT-Large's reassemble stage and head on the library path (split modes; called by _patch_dpt_upsampling, whose fusion-stage rewrite DPT shares):
           * per hook, GELU(Linear_2C->C(cat(tokens, CLS))) as one linear_x3 with the GELU epilogue over the [B, T-1, 2C] rows, then the 1x1 projection
             (C -> C_i) as a linear_x3 with its bias on the same rows -- [B, T-1, C_i] is NHWC storage, handed on as a channels_last view;
           * resize: hooks 0 / 1 (ConvTranspose2d, kernel == stride s) as a linear_x3 with the weight permuted to [(i, j, co)][ci] + the scatter / bias
             launch vd3d_depth_to_space_bias_nhwc_f32; hook 2 identity; hook 3 (3 x 3 stride 2) the library convolution -- under self_contained=True the
             stride-2 tile convolution of the mode + bias_act, by the rule of _self_contained_resize, and every module's route goes into conv_routes;
-          * head: conv1 bias-free with its bias inside the align_corners up-sampling, conv2 bias-free (vd3d_conv3x3_x2 in fp16x2 where its size rule allows),
-            vd3d_dpt_head_tail_f32 (scale 1) for the rest.
+          * head: _ConvRouter.head_tail3 with scale 1 and the head's nn.Upsample(x 2) size (conv2 on vd3d_conv3x3_x2 in fp16x2 where its size rule allows).
         neck.convs (3 x 3, no bias, C_i -> 256) and the fusion stage's 256 -> 256 convolutions have 256 output channels, which vd3d_conv3x3_x2 does not
         build: they stay library float32 convolutions, as for DA-V2-Large -- unless the pipe was built with conv="bf16x3", whose vd3d_conv3x3_x3 builds
-        256 output channels and takes them and the head's two 3 x 3 convolutions (conv_nb / the neck.convs routing of _patch_dpt_upsampling)."""
-        R, gm, CL, sc = self.renderer, self.gemm, torch.channels_last, self.self_contained
+        256 output channels and takes them and the head's two 3 x 3 convolutions (the _ConvRouter ``cr``: conv_nb / its neck.convs routing)."""
+        R, gm, sc = self.renderer, self.gemm, self.self_contained
         stage, head = self.model.neck.reassemble_stage, self.model.head
-        names = {id(m): n for n, m in self.model.named_modules()}
         hooks = []
         for i, lay in enumerate(stage.layers):
             if i in stage.neck_ignore_stages:   # DPT-Hybrid's hooks 0 / 1: maps of the BiT prefix, handed to neck.convs as they are
@@ -1223,12 +1233,11 @@ class DepthPipe:
                       proj=(R.gemm_x3_pack(pw.reshape(pw.shape[0], -1), gm), pw.shape[0], lay.projection.bias), resize=lay.resize,
                       ct=_ConvTransposeGemm(R, lay.resize, gm) if isinstance(lay.resize, torch.nn.ConvTranspose2d) and not sc else None)
             if sc:   # no library call: the resize module by the rule of the DINOv2 stage (refused by name here, at construction, if it is not built)
-                hk["sc"], hk["pname"] = self._self_contained_resize(lay.resize, names[id(lay.resize)]), names[id(lay.projection)]
+                hk["sc"], hk["pname"] = self._self_contained_resize(lay.resize, self._names[id(lay.resize)]), self._names[id(lay.projection)]
             hooks.append(hk)
 
         def count_rows(t, n):   # flops_per_frame: the 1x1 projections and transposed convolutions (EXECUTED: P x C_out x C_in) bypass the module hooks;
-            if self._flop_count is not None:   # the readout Linear is not a convolution (not counted, as in the stock graph)
-                self._flop_count[0] += 2.0 * t.numel() / t.shape[0] * n
+            self._count_flops(2.0 * t.numel() / t.shape[0] * n)   # the readout Linear is not a convolution (not counted, as in the stock graph)
 
         def reassemble_fwd(hidden_states, patch_height=None, patch_width=None):
             out = []
@@ -1254,7 +1263,7 @@ class DepthPipe:
                     self.conv_routes[hk["pname"]] = (gm, "self-contained: vd3d_gemm_x3 over the token rows")
                     if kind == "ct":
                         count_rows(x, operand.n)
-                    x = self._self_contained_resize_run(kind, operand, rz, names[id(rz)], x, B, gh, gw)
+                    x = self._self_contained_resize_run(kind, operand, rz, self._names[id(rz)], x, B, gh, gw)
                     if kind == "s2":
                         self._count_conv(rz, x)   # what the module's hook adds without the keyword
                 elif hk["ct"] is not None:
@@ -1267,23 +1276,17 @@ class DepthPipe:
             return out
         stage.forward = reassemble_fwd
 
-        if not f32:   # VD3D_NECK_GLUE=0: the head's own module graph
+        if not cr.f32:   # VD3D_NECK_GLUE=0: the head's own module graph
             return
         conv1, _, conv2, _, conv3, _ = list(head.head)
         tail_operands = _head_tail_operands(conv3)
         in_index = self.model.config.head_in_index
 
         def head_fwd(hidden_states):
-            x = hidden_states[in_index].contiguous(memory_format=CL)
+            x = hidden_states[in_index].contiguous(memory_format=_CL)
             size = (2 * x.shape[2], 2 * x.shape[3])   # nn.Upsample(scale_factor=2, align_corners=True)
-            h = R.upsample_bilinear_bias(conv_nb(conv1, x), size, conv1.bias)
-            y = conv_nb(conv2, h)
-            if self._flop_count is not None:
-                self._flop_count[0] += 2.0 * y.numel() / y.shape[0]   # the 1x1 convolution to one channel inside the tail kernel
-            w3, b3 = tail_operands()
-            return R.dpt_head_tail(y, conv2.bias, w3, b3, 1.0)
+            return cr.head_tail3(cr.conv_nb(conv1, x), conv1, conv2, size, tail_operands, 1.0)
         head.forward = head_fwd
-
 
     @torch.no_grad()
     def _fuse_backbone_layers(self):
@@ -1483,12 +1486,11 @@ class DepthPipe:
         R, gm, sc = self.renderer, self.gemm, self.self_contained
         emb = self.model.dpt.embeddings
         pm, bb = emb.projection, emb.backbone
-        names = {id(m): n for n, m in self.model.named_modules()}
         if not _is_conv(pm, 1, 1, 0) or pm.in_channels % 16:
-            raise NotImplementedError(f"gemm={gm!r}: {names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
+            raise NotImplementedError(f"gemm={gm!r}: {self._names[id(pm)]} is not a 1 x 1 convolution with C_in a multiple of 16 -- not built")
         img = R.gemm_x3_pack(pm.weight.reshape(pm.out_channels, pm.in_channels), gm)
-        prefix = _BitPrefix(self, bb, bit_prefix_plan(bb, names), names) if sc else None
-        lib_names = [names[id(m)] for m in bb.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.GroupNorm))]
+        prefix = _BitPrefix(self, bb, bit_prefix_plan(bb, self._names), self._names) if sc else None
+        lib_names = [self._names[id(m)] for m in bb.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.GroupNorm))]
 
         def emb_fwd(pixel_values, interpolate_pos_encoding=False):
             B, C, H, W = pixel_values.shape
@@ -1506,7 +1508,7 @@ class DepthPipe:
                     self.conv_routes[n] = ("library", "the BiT prefix stays the module graph without self_contained=True")
                 hooks, f3 = [maps[i] for i in emb.residual_feature_map_index], maps[-1].permute(0, 2, 3, 1).contiguous()
             tok = R.linear_x3(f3.reshape(B, f3.shape[1] * f3.shape[2], f3.shape[3]), img, pm.out_channels, pm.bias, mode=gm)
-            self.conv_routes[names[id(pm)]] = (gm, ("self-contained: " if sc else "") + "vd3d_gemm_x3 over the pixel rows")
+            self.conv_routes[self._names[id(pm)]] = (gm, ("self-contained: " if sc else "") + "vd3d_gemm_x3 over the pixel rows")
             self._count_conv(pm, tok)   # the bypassed Conv2d
             x = torch.cat((emb.cls_token.expand(B, -1, -1), tok), dim=1) + pos
             return Out(last_hidden_states=x, intermediate_activations=hooks)
@@ -1785,10 +1787,8 @@ class DepthPipe:
         backbone = 2.0 * lin * T + 4.0 * T * T * d * L
         total = [0.0]
 
-        def hook(mod, inp, out):   # registered on the convolution modules only; total is self._flop_count while they run
-            self._count_conv(mod, out)
-
-        hs = [m.register_forward_hook(hook) for m in self.model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d))]
+        # the hook is registered on the convolution modules only; total is self._flop_count while they run
+        hs = [m.register_forward_hook(lambda mod, inp, out: self._count_conv(mod, out)) for m in self.model.modules() if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d))]
         self._flop_count = total   # the bias-free convolution calls of the rewritten neck / head count themselves (EXECUTED flops: the
         try:                       # fusion layers' projections run before their up-samplings, at a quarter of the pixels)
             with torch.no_grad():
