@@ -341,10 +341,12 @@ VD3D_EXPORT void* vd3d_ctx_pixel_stream_k(vd3d_ctx* c, int k) {
 
 // ---- state ------------------------------------------------------------------------------------
 VD3D_EXPORT int vd3d_state_export(vd3d_ctx* c, vd3d_state* out) {
+  HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipMemcpyAsync(out, &c->work->st, sizeof(vd3d_state), hipMemcpyDeviceToHost, c->stream));
   return vd3d_sync(c);
 }
 VD3D_EXPORT int vd3d_state_import(vd3d_ctx* c, const vd3d_state* in) {
+  HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipMemcpyAsync(&c->work->st, in, sizeof(vd3d_state), hipMemcpyHostToDevice, c->stream));
   return vd3d_sync(c);
 }
@@ -368,6 +370,7 @@ VD3D_EXPORT int vd3d_state_planes(vd3d_ctx* c, float** tdf_prev, float** norm_pr
   return 0;
 }
 VD3D_EXPORT int vd3d_last_scalars(vd3d_ctx* c, vd3d_frame_scalars* out) {
+  HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipMemcpyAsync(out, &c->work->fs, sizeof(vd3d_frame_scalars), hipMemcpyDeviceToHost, c->stream));
   return vd3d_sync(c);
 }
@@ -1704,6 +1707,7 @@ VD3D_EXPORT int vd3d_add_layernorm(vd3d_ctx* c, int dtype, const void* x, const 
                                    float eps, int64_t rows, int cols, void* out_sum, void* out_norm) {
   if (dtype != VD3D_DT_BF16 && dtype != VD3D_DT_F32) return set_err(VD3D_E_INVALID, "bad dtype %d", dtype);
   if (!c || !x || !gamma || !beta || !out_norm || rows < 1 || (y_or_null && !out_sum)) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_add_layernorm(c->stream, dtype, x, y_or_null, gamma, beta, eps, (long long)rows, cols, out_sum, out_norm))
     return set_err(VD3D_E_UNSUPPORTED, "add_layernorm: cols %d not in {384,768,1024}", cols);
   HIPCHK(hipGetLastError());
@@ -1934,6 +1938,7 @@ VD3D_EXPORT int vd3d_gemm_x3(vd3d_ctx* c, const float* X, int64_t M, int K, cons
 VD3D_EXPORT int vd3d_upsample_bilinear_nhwc(vd3d_ctx* c, int dtype, const void* in, void* out, int B, int ih, int iw, int oh, int ow, int C) {
   if (dtype != VD3D_DT_BF16 && dtype != VD3D_DT_F32) return set_err(VD3D_E_INVALID, "bad dtype %d", dtype);
   if (!c || !in || !out || B < 1 || ih < 1 || iw < 1) return set_err(VD3D_E_INVALID, "bad argument");
+  HIPCHK(hipSetDevice(c->device));
   if (!vd_launch_upsample_bilinear_nhwc(c->stream, dtype, in, out, B, ih, iw, oh, ow, C))
     return set_err(VD3D_E_UNSUPPORTED, "upsample_bilinear_nhwc: C not a multiple of 8 (bf16) / 4 (f32) or output smaller than 2x2");
   HIPCHK(hipGetLastError());
