@@ -44,7 +44,8 @@ extern "C" {
  *    vd3d_neck_poly_conv_f32 (the float32 neck's transposed convolution + 3 x 3 convolution in polyphase form), vd3d_depthpro_preprocess_u8
  *    and vd3d_depthpro_post_f32 (DepthPro's image-processor front end and post-process), vd3d_head_upconv_gather_f32 (the fine half of the float32 head's
  *    first convolution as coarse GEMM + fine gather), vd3d_head_conv_gather_weight_bytes, vd3d_head_conv_gather_tile, vd3d_head_conv_gather_pack_weights and
- *    vd3d_head_conv_gather_f32 (the float32 head's up-sampling + second convolution + tail as coarse GEMM + fine gather in one launch). */
+ *    vd3d_head_conv_gather_f32 (the float32 head's up-sampling + second convolution + tail as coarse GEMM + fine gather in one launch),
+ *    vd3d_depthpro_patches_count, vd3d_depthpro_patches_f32 and vd3d_depthpro_merge_f32 (DepthPro's patch pyramid and patch merge: DepthPipe(encoders=...)). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -803,6 +804,23 @@ int vd3d_depthpro_preprocess_u8(vd3d_ctx* ctx, const uint8_t* frames_bgr, int B,
  * focal = 0.5 oW / tan(0.5 deg2rad(fov[b])) -- fov_or_null: the model's field of view in degrees, float32 [B] in DEVICE memory (no host synchronisation), NULL:
  * no scaling -- resize = ATen's bilinear, skipped for oH == oW == S.  tan is evaluated in float64 and narrowed to float32 (within 1 ulp; the narrowing is a second rounding).  NaN stays NaN. */
 int vd3d_depthpro_post_f32(vd3d_ctx* ctx, const float* pred, const float* fov_or_null, int B, int S, int oH, int oW, float* out);
+/* The two gathers around DepthPro's three ViT encoders under DepthPipe(encoders=...); visiondepth3d_amd/depth_pro.py states both in NumPy (patches_statement,
+ * merge_statement) and the kernels give those values bit for bit.
+ *
+ * DepthProPatchEncoder's patch pyramid in one launch: pixel_values float32 planar [B][3][S][S] -> patches [(n1^2 + n2^2 + n4^2) B][p][p][3] (pixel-interleaved: the
+ * memory vd3d_patchify_f32 reads; the logical tensor is [N][3][p][p]).  Levels in the order full resolution, half, quarter; inside a level patch-major, batch-minor
+ * (index l B + b, l the row-major patch position); a level whose image has side s holds (s - p) / stride + 1 patches per side, one where s == p (its stride is then
+ * not read).  Half level: 0.25 ((a + b) + (c + d)) over every 2 x 2 cell; quarter level: the same over the 2 x 2 centre of every 4 x 4 cell --
+ * F.interpolate(scale_factor=0.5 / 0.25, mode="bilinear") on such sides.  vd3d_depthpro_patches_count (host only): patches per frame, < 0 where a level holds no
+ * patch.  S a multiple of 4 up to 2^20, S / 4 >= p >= 1, 4-byte aligned pointers; 16-byte loads and stores where p and the strides in use are multiples of 4 and
+ * both pointers 16-byte aligned, 4-byte ones otherwise. */
+int64_t vd3d_depthpro_patches_count(int S, int p, int stride_full, int stride_half, int stride_quarter);
+int vd3d_depthpro_patches_f32(vd3d_ctx* ctx, const float* pixel_values, int B, int S, int p, int stride_full, int stride_half, int stride_quarter, float* patches);
+/* reconstruct_feature_maps in NHWC: rows float32 [n B][T][C] (sequence index l B + b) -> out [B][oh][ow][C].  The leading T - g^2 tokens are dropped; side =
+ * int(sqrt(n)) patches per side (1 for n == 1; sequences past side^2 are never read); pad = min(g / 4, padding), 0 for n < 4, trimmed on the edges that meet
+ * another patch: merged size M = side g - 2 pad (side - 1); then ATen's bilinear from M x M to oh x ow, skipped (exact copies) for oh == ow == M.  T >= g^2,
+ * g <= 4096, sides up to 2^20, 4-byte aligned pointers; 16-byte loads and stores where C is a multiple of 4 and both pointers are 16-byte aligned. */
+int vd3d_depthpro_merge_f32(vd3d_ctx* ctx, const float* rows, int n, int B, int T, int C, int g, int padding, int oh, int ow, float* out);
 
 /* ---- preview visualisers: generate_preview_image, core/preview_utils.py:23-84, the exactly defined types.
  * left / right: uint8 BGR [h][w][3] eyes (outputs of vd3d_pixel_shift).  out: [h][w][3], except HSBS: [h][2*(w/2)][3].

@@ -4,6 +4,14 @@ same module) in the same process, runs alternating.  Medians of ROUNDS rounds, t
 
     python tools/probe_depth_pro.py kernels
     python tools/probe_depth_pro.py forward [--frames 1 4]
+
+and behind profiles/r28_depth_pro_encoders.md (DepthPipe(encoders=...)): the pyramid and merge kernels alone at the published shapes beside the stream copy of the
+same bytes and the ATen operations they replace; the 1536 x 1536 forward with encoders=None / "bf16x3" / "fp16x2" (one synthetic model, copied per pipe), its three
+own parts timed apart, and the two hand-over layouts of the merge in front of the library neck; the time from process start to the end of the first forward.
+
+    python tools/probe_depth_pro.py pyramid [--frames 1 4]
+    python tools/probe_depth_pro.py encoders [--frames 1 4]
+    python tools/probe_depth_pro.py first --mode bf16x3
 """
 import argparse
 import json
@@ -102,9 +110,130 @@ def forward(frames):
     R.close()
 
 
+def pyramid(frames):
+    """The two encoder-side kernels alone at the published shapes (S = 1536, p = 384, a 24 x 24 grid of 1024 channels)."""
+    import torch.nn.functional as F
+    from transformers.models.depth_pro.modeling_depth_pro import reconstruct_feature_maps, split_to_patches
+    from visiondepth3d_amd import _lib
+    from visiondepth3d_amd.render_3d import Renderer, _ptr
+    R = Renderer(0)
+    n = 512 << 20
+    src, dst = torch.empty(n, dtype=torch.uint8, device="cuda"), torch.empty(n, dtype=torch.uint8, device="cuda")
+
+    def copy_of(nbytes):   # the stream copy of nbytes / 2 in, nbytes / 2 out
+        return lambda: _lib.check(R._L.vd3d_stream_copy(R._ctx, _ptr(src), _ptr(dst), nbytes // 2))
+
+    def aten_patches(x):
+        imgs = [split_to_patches(F.interpolate(x, scale_factor=r, mode="bilinear", align_corners=False), 384, o) for r, o in ((0.25, 0.0), (0.5, 0.5), (1, 0.25))]
+        return torch.cat(imgs[::-1], dim=0)
+    for B in frames:
+        x = torch.randn(B, 3, 1536, 1536, device="cuda")
+        nbytes = x.numel() * 4 + 35 * B * 3 * 384 * 384 * 4
+        r = rounds({"kernel": lambda: R.depthpro_patches(x, 384, [288, 192, 384]), "stream_copy": copy_of(nbytes), "aten": lambda: aten_patches(x)}, 20)
+        print(json.dumps(dict(what=f"patches_1536_p384_B{B}", ms=r, bytes=nbytes, bytes_per_s=nbytes / (r["kernel"][0] * 1e-3), of_stream_copy=r["stream_copy"][0] / r["kernel"][0])))
+        for name, nseq, pad, out in (("level_full", 25, 3, 96), ("level_half", 9, 6, 48), ("level_quarter", 1, 12, 24), ("hook", 35, 3, 96)):
+            rows = torch.randn(nseq * B, 577, 1024, device="cuda")
+            nbytes = 2 * B * out * out * 1024 * 4
+            r = rounds({"kernel": lambda: R.depthpro_merge(rows, B, 24, pad, out, out), "stream_copy": copy_of(nbytes),
+                        "aten": lambda: reconstruct_feature_maps(rows, B, pad, (out, out))}, 20)
+            print(json.dumps(dict(what=f"merge_{name}_B{B}", ms=r, bytes=nbytes, bytes_per_s=nbytes / (r["kernel"][0] * 1e-3), of_stream_copy=r["stream_copy"][0] / r["kernel"][0])))
+    R.close()
+
+
+def _full_model():
+    from transformers import DepthProForDepthEstimation
+    from visiondepth3d_amd import depth_pro
+    from visiondepth3d_amd.depth import synthetic_weights_
+    m = DepthProForDepthEstimation(depth_pro.config()).eval()
+    synthetic_weights_(m, 0)
+    return m
+
+
+def encoders(frames):
+    import copy
+    from visiondepth3d_amd.depth import DepthPipe, patch_embedding_gemm_weight
+    from visiondepth3d_amd.render_3d import Renderer
+    R = Renderer(0)
+    model = _full_model()
+    pipes = {str(mode): DepthPipe("depth-pro", renderer=R, model=copy.deepcopy(model), encoders=mode) for mode in (None, "bf16x3", "fp16x2")}
+    del model
+    fr = torch.randint(0, 256, (max(frames), 1080, 1920, 3), dtype=torch.uint8, device="cuda")
+    half = (0.5, 0.5, 0.5)
+    for B in frames:
+        f = fr[:B]
+        r = rounds({k: (lambda p=p: p.infer_bgr_u8(f)) for k, p in pipes.items()}, 2, warm=1)
+        print(json.dumps(dict(what=f"forward_1536_encoders_B{B}", ms=r, resize={k: p.encoders_resize for k, p in pipes.items()})))
+    # the three own parts apart (random activations of the published shapes; the blocks on freshly packed copies of the same weights)
+    for mode in ("bf16x3", "fp16x2"):
+        pipe = pipes[mode]
+        net = pipe.model
+        vits = [net.depth_pro.encoder.patch_encoder.model, net.depth_pro.encoder.image_encoder.model, net.fov_model.fov_encoder.model]
+        packed = [R.gemm_x3_pack(patch_embedding_gemm_weight(v.embeddings.patch_embeddings.projection.weight), mode) for v in vits]
+        blocks = [pipe._split_layers(v.encoder.layer, mode) for v in vits]
+        for B in frames:
+            x = R.depthpro_preprocess(fr[:B], 1536, half, half)
+
+            @torch.no_grad()
+            def embed():
+                patches = R.depthpro_patches(x, 384, [288, 192, 384])
+                for v, img, inp in zip(vits, packed, (patches, patches[-B:], patches[-B:])):
+                    pe = v.embeddings.patch_embeddings.projection
+                    tok = R.linear_x3(R.patchify(inp, 16), img, 1024, pe.bias, mode=mode)
+                    torch.cat((v.embeddings.cls_token.expand(tok.shape[0], -1, -1), tok), dim=1) + v.embeddings.position_embeddings
+            seqs = [torch.randn(n, 577, 1024, device="cuda") * 0.5 for n in (35 * B, B, B)]
+
+            @torch.no_grad()
+            def run_blocks():
+                for v, bl, t in zip(vits, blocks, seqs):
+                    for b in bl:
+                        t = b(t)
+                    R.add_layernorm(t, None, v.layernorm)
+
+            def merges():
+                t = seqs[0]
+                R.depthpro_merge(t[:25 * B], B, 24, 3, 96, 96), R.depthpro_merge(t[25 * B:34 * B], B, 24, 6, 48, 48), R.depthpro_merge(t[34 * B:], B, 24, 12, 24, 24)
+                R.depthpro_merge(t, B, 24, 3, 96, 96), R.depthpro_merge(t, B, 24, 3, 96, 96), R.depthpro_merge(seqs[1], B, 24, 0, 24, 24)
+            r = rounds({"pyramid_and_embeddings": embed, "encoder_blocks": run_blocks, "merges": merges}, 2, warm=1)
+            print(json.dumps(dict(what=f"parts_{mode}_B{B}", ms=r)))
+        del blocks, packed
+    # the two hand-over layouts of the merge in front of the library neck, fusion stage and head: the [B, C, oh, ow] view of the NHWC storage, or a contiguous copy
+    pipe = pipes["bf16x3"]
+    for B in frames:
+        got = {}
+        h = pipe.model.depth_pro.neck.register_forward_pre_hook(lambda mod, args: got.__setitem__("f", [t.clone(memory_format=torch.preserve_format) for t in args[0]]))
+        pipe.infer_bgr_u8(fr[:B])
+        h.remove()
+        feats = got["f"]
+        assert all(t.is_contiguous(memory_format=torch.channels_last) for t in feats)
+
+        @torch.no_grad()
+        def decoder(fs):
+            return pipe.model.head(pipe.model.fusion_stage(pipe.model.depth_pro.neck(fs))[-1])
+        r = rounds({"view": lambda: decoder(list(feats)), "contiguous_copy": lambda: decoder([t.contiguous() for t in feats])}, 2, warm=1)
+        print(json.dumps(dict(what=f"handover_layout_B{B}", ms=r)))
+    R.close()
+
+
+def first(mode):
+    from visiondepth3d_amd.depth import DepthPipe
+    from visiondepth3d_amd.render_3d import Renderer
+    R = Renderer(0)
+    t = time.time()
+    pipe = DepthPipe("depth-pro", renderer=R, encoders=None if mode == "none" else mode)
+    built = time.time()
+    fr = torch.randint(0, 256, (1, 1080, 1920, 3), dtype=torch.uint8, device="cuda")
+    pipe.infer_bgr_u8(fr)
+    torch.cuda.synchronize()
+    print(json.dumps(dict(what="start_to_first_forward", encoders=pipe.encoders, import_s=t - T0, construct_s=built - t, first_forward_s=time.time() - built,
+                          total_s=time.time() - T0)))
+    R.close()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernels", "forward"])
+    ap.add_argument("what", choices=["kernels", "forward", "pyramid", "encoders", "first"])
     ap.add_argument("--frames", type=int, nargs="+", default=[1, 4])
+    ap.add_argument("--mode", choices=["none", "bf16x3", "fp16x2"], default="none")
     a = ap.parse_args()
-    kernels() if a.what == "kernels" else forward(a.frames)
+    {"kernels": kernels, "forward": lambda: forward(a.frames), "pyramid": lambda: pyramid(a.frames), "encoders": lambda: encoders(a.frames),
+     "first": lambda: first(a.mode)}[a.what]()

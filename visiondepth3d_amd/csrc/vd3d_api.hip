@@ -2158,6 +2158,36 @@ VD3D_EXPORT int vd3d_depthpro_post_f32(vd3d_ctx* c, const float* pred, const flo
   HIPCHK(hipGetLastError());
   return 0;
 }
+// ---- DepthPro's patch pyramid and patch merge (vd3d_depthpro_pyramid.hip)
+VD3D_EXPORT int64_t vd3d_depthpro_patches_count(int S, int p, int stride_full, int stride_half, int stride_quarter) {
+  return (int64_t)vd_depthpro_patches_count(S, p, stride_full, stride_half, stride_quarter);
+}
+VD3D_EXPORT int vd3d_depthpro_patches_f32(vd3d_ctx* c, const float* pixel_values, int B, int S, int p, int stride_full, int stride_half, int stride_quarter, float* patches) {
+  if (!c || !pixel_values || !patches) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || S > (1 << 20) || vd_depthpro_patches_count(S, p, stride_full, stride_half, stride_quarter) < 1)
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_patches: batch %d, side %d (a multiple of 4, up to 2^20), patch %d, strides %d / %d / %d: every level must hold a patch "
+                   "and a level of several patches needs a stride of at least 1", B, S, p, stride_full, stride_half, stride_quarter);
+  if ((reinterpret_cast<uintptr_t>(pixel_values) & 3) || (reinterpret_cast<uintptr_t>(patches) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_patches: the pixel values and the patches must be 4-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depthpro_patches_f32(c->stream, pixel_values, B, S, p, stride_full, stride_half, stride_quarter, patches))
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_patches: too many pixels for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_depthpro_merge_f32(vd3d_ctx* c, const float* rows, int n, int B, int T, int C, int g, int padding, int oh, int ow, float* out) {
+  if (!c || !rows || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (n < 1 || B < 1 || C < 1 || g < 1 || g > 4096 || padding < 0 || oh < 1 || ow < 1 || oh > (1 << 20) || ow > (1 << 20) || (long long)T < (long long)g * g || n > (1 << 20))
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_merge: %d sequences per frame, batch %d, %d tokens of %d channels on a %d x %d grid, padding %d, output %d x %d: every "
+                   "count at least 1, the tokens at least the grid, the grid side up to 4096, an output side up to 2^20", n, B, T, C, g, g, padding, oh, ow);
+  int side, pad;
+  if ((long long)vd_depthpro_merge_geometry(n, g, padding, &side, &pad) > (1 << 20)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_merge: a merged side past 2^20");
+  if ((reinterpret_cast<uintptr_t>(rows) & 3) || (reinterpret_cast<uintptr_t>(out) & 3)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_merge: the rows and the output must be 4-byte aligned");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depthpro_merge_f32(c->stream, rows, n, B, T, C, g, padding, oh, ow, out)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_merge: too many elements for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 VD3D_EXPORT int vd3d_preview_image(vd3d_ctx* c, int type, const uint8_t* left_bgr, const uint8_t* right_bgr, int h, int w, uint8_t* out_bgr) {
   if (!c || !left_bgr || !right_bgr || !out_bgr || h < 1 || w < 1) return set_err(VD3D_E_INVALID, "bad argument");

@@ -324,6 +324,11 @@ bool vd_launch_groupnorm_nhwc_f32(hipStream_t s, const float* x, const float* re
 // ---- vd3d_depthpro.hip: DepthPro's front end and post-process (the C entry points check shapes and alignment; false = a grid too large)
 bool vd_launch_depthpro_preprocess_u8(hipStream_t s, const uint8_t* frames, int B, int H, int W, int S, const float mean[3], const float std[3], float* out);
 bool vd_launch_depthpro_post_f32(hipStream_t s, const float* pred, const float* fov, int B, int S, int oH, int oW, float* out);
+// ---- vd3d_depthpro_pyramid.hip: DepthPro's patch pyramid and patch merge (the C entry points check shapes and alignment; false = a grid too large)
+long long vd_depthpro_patches_count(int S, int p, int stride_full, int stride_half, int stride_quarter);   // patches per frame over the three levels; < 0: no such pyramid
+bool vd_launch_depthpro_patches_f32(hipStream_t s, const float* x, int B, int S, int p, int stride_full, int stride_half, int stride_quarter, float* out);
+int vd_depthpro_merge_geometry(int n, int g, int padding, int* side, int* pad);   // the merged size
+bool vd_launch_depthpro_merge_f32(hipStream_t s, const float* rows, int n, int B, int T, int C, int g, int padding, int oh, int ow, float* out);
 // ---- vd3d_handoff.hip
 // form: 0 = the library's choice (the separable kernel for up-scaling), 1 = the general kernel, 2 = the separable kernel (false where it does not apply)
 bool vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,

@@ -827,7 +827,7 @@ class DepthPipe:
     def __init__(self, name: str = "depth-anything-v2-small", device="cuda", dtype=torch.float32, seed: int = 0,
                  channels_last: bool = True, renderer=None, fuse_backbone: bool = True, model=None, processor: dict | None = None,
                  tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None, self_contained: bool = False,
-                 front_end: str = "float"):
+                 front_end: str = "float", encoders: str | None = None):
         """``dtype``: float32 (the reference's precision, default) or bfloat16.
         ``front_end``: ``"float"`` (default) -- the network input is the float32 statement of the image processor's antialiased bicubic resize, never
         rounded (``vd3d_depth_preprocess`` with a renderer, ATen otherwise).  ``"pil"`` -- OPT-IN: the input the reference process builds, bit for bit.
@@ -846,6 +846,14 @@ class DepthPipe:
         no resize) -- a deviation: the pipeline resizes before the reciprocal.  A model without the field-of-view branch is not scaled.  The network itself runs its
         stock float32 graph: ``gemm="bf16x3"`` / ``"fp16x2"`` and ``self_contained=True`` refuse DepthPro by name (the rewrite is not built), and so does tiled depth
         (its blend evaluates a bicubic post-process); ``bars=`` consumes the uint8 planes and works unchanged.
+        ``encoders`` (DepthPro only; float32 + ``renderer``): ``None`` (default) -- the stock graph, as above.  ``"bf16x3"`` / ``"fp16x2"`` -- OPT-IN: from ``pixel_values``
+        to the inputs of ``DepthProNeck`` (and to the input of the field-of-view model's convolution) no vendor-library call is made: the patch pyramid is one launch
+        (``vd3d_depthpro_patches_f32``), the patch embeddings are ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, every ``Dinov2Layer`` of the patch, image and
+        field-of-view encoders is a ``_split_block`` in the named arithmetic, the final LayerNorms are ``vd3d_add_layernorm``, the field-of-view ``neck`` Linear is
+        ``vd3d_gemm_x3`` and every ``reconstruct_feature_maps`` is ``vd3d_depthpro_merge_f32`` (``_route_depth_pro_encoders``).  The neck, the fusion stage, the head
+        and the field-of-view convolutions stay the stock module graph on the float32 library, which is why ``gemm=`` / ``self_contained=True`` keep refusing DepthPro.
+        ``pipe.encoders`` records the mode (or None), ``pipe.encoders_resize`` whether the image / field-of-view encoders read the pyramid's quarter level
+        ("pyramid") or resized for themselves ("aten").  Any other model, value or geometry is refused by name at construction.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
         GEMMs and the attention (64-wide heads) is the library's exact-float32 kernel (``vd3d_attention_f32``: both products on the float32-input
         matrix cores, float32 online softmax); ``"bf16x3"`` -- OPT-IN: the library's own split-bf16 GEMM (``vd3d_gemm_x3``: every float32 operand exactly split into three bf16
@@ -908,6 +916,11 @@ class DepthPipe:
             raise ValueError("gemm='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
         if front_end not in ("float", "pil"):
             raise ValueError("front_end must be 'float' or 'pil'")
+        if encoders not in (None, "bf16x3", "fp16x2"):
+            raise ValueError("encoders must be None, 'bf16x3' or 'fp16x2'")
+        if encoders is not None and (dtype != torch.float32 or renderer is None or torch.device(device).type != "cuda"):
+            raise ValueError("encoders='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
+        self.encoders, self.encoders_resize = None, {}
         self.front_end, self.front_end_route = front_end, None
         self.gemm, self.conv, self.self_contained = gemm, conv, bool(self_contained)
         self.conv_routes = {}
@@ -938,6 +951,9 @@ class DepthPipe:
                 self._split_scope(fuse_backbone)
             if processor is None:
                 processor = PROCESSORS["depth_pro"]
+        if encoders is not None:   # refused by name on the module graph as it was handed in: nothing moved to a device yet
+            self.model = model
+            enc_plan = self._depth_pro_encoders_scope(encoders, processor)
         if self.self_contained:   # refused here, by name, on the module graph as it was handed in: no renderer call, nothing moved to a device yet
             self.model = model
             scope = self._split_scope(fuse_backbone)
@@ -982,6 +998,8 @@ class DepthPipe:
                 self._patch_dpt_upsampling()
             if self.self_contained:
                 self._patch_patch_embedding(self.model.backbone.embeddings.patch_embeddings)
+        if encoders is not None:
+            self._route_depth_pro_encoders(encoders, enc_plan)
 
     def _library_selection(self, tuned_gemm: bool, miopen_find):
         if miopen_find is not None:
@@ -1316,17 +1334,7 @@ class DepthPipe:
             bb.layernorm.forward = lambda x: final_ln(x if pad_state["T"] is None else x[:, :pad_state["T"]])
         stash = {"x": None, "h": None}   # LayerNorm1(x) computed by the PREVIOUS layer's fused add+LayerNorm launch
         for li, layer in enumerate(layers):
-            att, out = layer.attention.attention, layer.attention.output.dense
-            wqkv = torch.cat([att.query.weight, att.key.weight, att.value.weight], 0).contiguous()
-            bqkv = torch.cat([att.query.bias, att.key.bias, att.value.bias], 0).contiguous()
-            l1, l2 = layer.layer_scale1.lambda1.float(), layer.layer_scale2.lambda1.float()
-            wo = (out.weight.float() * l1[:, None]).to(out.weight.dtype).contiguous()
-            bo = (out.bias.float() * l1).to(out.bias.dtype).contiguous()
-            fc1, fc2 = layer.mlp.fc1, layer.mlp.fc2
-            w2 = (fc2.weight.float() * l2[:, None]).to(fc2.weight.dtype).contiguous()
-            b2 = (fc2.bias.float() * l2).to(fc2.bias.dtype).contiguous()
-            nh, hd, scaling = att.num_attention_heads, att.attention_head_size, att.scaling
-            n1, n2, act = layer.norm1, layer.norm2, layer.mlp.activation
+            wqkv, bqkv, wo, bo, fc1, w2, b2, nh, hd, scaling, n1, n2, act = self._dinov2_layer_operands(layer)
             nxt = layers[li + 1].norm1 if li + 1 < len(layers) else None
             x3 = None
             if self.gemm != "f32":
@@ -1365,12 +1373,207 @@ class DepthPipe:
 
             layer.forward = fwd
 
-    def _split_block(self, stash, pad_state, wqkv, bqkv, wo, bo, w1, b1, w2, b2, nh, hd, scaling, n1, n2, act, nxt):
+    @staticmethod
+    def _dinov2_layer_operands(layer):
+        """One Dinov2Layer as the operands of the fused block: q / k / v weights and biases concatenated for ONE GEMM, LayerScale folded into the output projection
+        and fc2 (lambda * (xW^T + b) == x(lambda*W)^T + lambda*b) -> (wqkv, bqkv, wo, bo, fc1 module, w2, b2, heads, head size, scaling, norm1, norm2, activation)."""
+        att, out = layer.attention.attention, layer.attention.output.dense
+        wqkv = torch.cat([att.query.weight, att.key.weight, att.value.weight], 0).contiguous()
+        bqkv = torch.cat([att.query.bias, att.key.bias, att.value.bias], 0).contiguous()
+        l1, l2 = layer.layer_scale1.lambda1.float(), layer.layer_scale2.lambda1.float()
+        wo = (out.weight.float() * l1[:, None]).to(out.weight.dtype).contiguous()
+        bo = (out.bias.float() * l1).to(out.bias.dtype).contiguous()
+        fc1, fc2 = layer.mlp.fc1, layer.mlp.fc2
+        w2 = (fc2.weight.float() * l2[:, None]).to(fc2.weight.dtype).contiguous()
+        b2 = (fc2.bias.float() * l2).to(fc2.bias.dtype).contiguous()
+        return wqkv, bqkv, wo, bo, fc1, w2, b2, att.num_attention_heads, att.attention_head_size, att.scaling, layer.norm1, layer.norm2, layer.mlp.activation
+
+    @torch.no_grad()
+    def _split_layers(self, layers, mode):
+        """Every Dinov2Layer of ``layers`` (one encoder) as a ``_split_block`` in ``mode``: the weights are folded (_dinov2_layer_operands), split and packed once,
+        here; the blocks share one ``stash`` of their own and there is no query padding.  Returns the block functions in order; the modules are left as they are."""
+        layers = list(layers)
+        stash, pad_state = {"x": None, "h": None}, {"T": None}
+        fwds = []
+        for li, layer in enumerate(layers):
+            wqkv, bqkv, wo, bo, fc1, w2, b2, nh, hd, scaling, n1, n2, act = self._dinov2_layer_operands(layer)
+            nxt = layers[li + 1].norm1 if li + 1 < len(layers) else None
+            fwds.append(self._split_block(stash, pad_state, wqkv, bqkv, wo, bo, fc1.weight, fc1.bias, w2, b2, nh, hd, scaling, n1, n2, act, nxt, mode=mode))
+        return fwds
+
+    def _depth_pro_encoders_scope(self, mode, processor):
+        """``encoders=``: what the routing needs of the model and its processor, read from the module graph and the configuration only (nothing is moved or
+        launched); everything it does not cover is refused by name.  Returns the plan ``_route_depth_pro_encoders`` executes: the processor side, DepthPro's patch
+        size, the pyramid levels and the names of the encoders present."""
+        from . import depth_pro
+        m, tag = self.model, f"encoders={mode!r}"
+        what = f"{self.name!r} ({type(m).__name__})"
+        if type(m).__name__ != "DepthProForDepthEstimation":
+            raise NotImplementedError(f"{tag}: {what} -- the keyword routes the three ViT encoders of DepthProForDepthEstimation; every other model takes gemm= / conv= / "
+                                      "self_contained=")
+        cfg = m.config
+        found = [("patch", m.depth_pro.encoder.patch_encoder), ("image", m.depth_pro.encoder.image_encoder)]
+        if m.fov_model is not None:
+            found.append(("fov", m.fov_model.fov_encoder))
+        for which, enc in found:
+            vit = enc.model
+            if type(vit).__name__ != "Dinov2Model":
+                raise NotImplementedError(f"{tag}: {what}: the {which} encoder is a {type(vit).__name__} -- _split_block is built for Dinov2Model encoders")
+            d, nh = int(vit.config.hidden_size), int(vit.config.num_attention_heads)
+            if d not in (384, 768, 1024) or d != 64 * nh:
+                raise NotImplementedError(f"{tag}: {what}: the {which} encoder has hidden size {d} with {nh} heads -- vd3d_attention_x3 and vd3d_add_layernorm are "
+                                          "built for 384 / 768 / 1024 with 64-wide heads")
+            if getattr(vit.config, "use_swiglu_ffn", False):
+                raise NotImplementedError(f"{tag}: {what}: the {which} encoder has a SwiGLU feed-forward -- _split_block is built for fc1 / activation / fc2")
+            pe = vit.embeddings.patch_embeddings.projection
+            k = pe.kernel_size[0]
+            if not (isinstance(pe, torch.nn.Conv2d) and pe.kernel_size == (k, k) and pe.stride == (k, k) and pe.padding == (0, 0) and pe.dilation == (1, 1)
+                    and pe.groups == 1 and pe.in_channels == 3 and k <= 64):
+                raise NotImplementedError(f"{tag}: {what}: the {which} encoder's patch embedding is not Conv2d(3, C, kernel_size=p, stride=p), p <= 64 -- "
+                                          "vd3d_patchify_f32 does not take it")
+        ratios = [float(r) for r in cfg.scaled_images_ratios]
+        if ratios != [0.25, 0.5, 1.0]:
+            raise NotImplementedError(f"{tag}: {what}: scaled_images_ratios={list(cfg.scaled_images_ratios)} -- vd3d_depthpro_patches_f32 builds the pyramid of [0.25, 0.5, 1]")
+        size = tuple(int(v) for v in (PROCESSORS["depth_pro"] if processor is None else processor)["size"])
+        if size[0] != size[1] or size[0] % 4:
+            raise NotImplementedError(f"{tag}: {what}: a processor size of {size} -- the pyramid kernel takes a square side that is a multiple of 4")
+        p = int(cfg.patch_size)
+        try:
+            levels = depth_pro.pyramid_levels(size[0], p, ratios, [float(o) for o in cfg.scaled_images_overlap_ratios])
+        except ValueError as e:
+            raise NotImplementedError(f"{tag}: {what}: a pyramid vd3d_depthpro_patches_f32 is not built for -- {e}") from None
+        if any(stride < 1 for _, _, stride, _ in levels):
+            raise NotImplementedError(f"{tag}: {what}: a pyramid vd3d_depthpro_patches_f32 is not built for -- scaled_images_overlap_ratios="
+                                      f"{list(cfg.scaled_images_overlap_ratios)} leave a stride below 1")
+        return dict(size=size[0], patch=p, ratios=ratios, overlaps=[float(o) for o in cfg.scaled_images_overlap_ratios], which=[w for w, _ in found])
+
+    @torch.no_grad()
+    def _route_depth_pro_encoders(self, mode, plan):
+        """``encoders=``: the forwards of DepthProPatchEncoder, DepthProImageEncoder and DepthProFovEncoder replaced (``_depth_pro_encoders_scope`` has accepted the
+        model), so that between ``pixel_values`` and the inputs of DepthProNeck / ``fov_model.conv`` every launch is one of this project's kernels or an ATen
+        element-wise one (the class-token concatenation, the position-embedding add, the last block's residual add) -- no hipBLASLt, MIOpen or AOTriton call:
+          * the patch pyramid: one launch of vd3d_depthpro_patches_f32, written in the memory patchify reads;
+          * per encoder: vd3d_patchify_f32 + vd3d_gemm_x3 for the patch embedding, the class token and the (memoised) position embedding added, every Dinov2Layer a
+            _split_block in ``mode`` (_split_layers: one weight split / pack per encoder, here), the hook layers' residual streams kept, the final LayerNorm as
+            add_layernorm(x, None, ln);
+          * every reconstruct_feature_maps: vd3d_depthpro_merge_f32, handed on as the [B, C, oh, ow] view of its NHWC storage (channels_last, what the library
+            convolutions behind it read);
+          * the field-of-view encoder's ``neck`` Linear: vd3d_gemm_x3.
+        Where floor(S / 4) is DepthPro's patch size and the image / field-of-view encoder's image_size, that encoder reads the pyramid's quarter level (the last
+        patch of the stack: F.interpolate(size=) and F.interpolate(scale_factor=0.25) give the same bits there); otherwise its resize stays an ATen call.
+        ``encoders_resize`` says which, per encoder."""
+        import math
+        from transformers.models.depth_pro.modeling_depth_pro import DepthProOutput
+        from . import depth_pro
+        R, m = self.renderer, self.model
+        cfg = m.config
+        p, ratios, overlaps = plan["patch"], plan["ratios"], plan["overlaps"]
+        state = {"pixel_values": None, "quarter": None}   # the pyramid's quarter level of the forward in flight, for the image / field-of-view encoders
+
+        def make_encoder(vit):
+            emb, pe = vit.embeddings, vit.embeddings.patch_embeddings.projection
+            k, C = pe.kernel_size[0], pe.out_channels
+            img = R.gemm_x3_pack(patch_embedding_gemm_weight(pe.weight), mode)
+            blocks = self._split_layers(vit.encoder.layer, mode)
+            pos = {}
+
+            def run(x, hooks=()):
+                """[N, 3, h, w] in channels_last memory -> (LayerNorm(last hidden state), {hook: that layer's residual stream})."""
+                N, _, h, w = x.shape
+                tok = R.linear_x3(R.patchify(x, k), img, C, pe.bias, mode=mode)
+                t = torch.cat((emb.cls_token.expand(N, -1, -1), tok), dim=1)
+                if (h, w) not in pos:   # a constant of the input size (the parameter itself where the grid is the trained one)
+                    pos[(h, w)] = emb.interpolate_pos_encoding(t, h, w).detach()
+                t = t + pos[(h, w)]
+                kept = {}
+                for li, blk in enumerate(blocks):
+                    t = blk(t)
+                    if li in hooks:
+                        kept[li] = t
+                return R.add_layernorm(t, None, vit.layernorm)[1], kept
+            return run
+
+        def base_size(enc, height, width):   # the lowest-resolution feature size, as the stock forwards compute it
+            e = int(math.log2(width / enc.out_size))
+            return height // 2 ** e, width // 2 ** e
+
+        def merge(rows, B, padding, oh, ow):
+            T = rows.shape[1]
+            return R.depthpro_merge(rows.contiguous(), B, int(T ** 0.5), padding, oh, ow).permute(0, 3, 1, 2)
+
+        def own_input(which, enc_cfg, pixel_values):
+            """The [B, 3, size, size] input of the image / field-of-view encoder in channels_last memory."""
+            size = int(enc_cfg.image_size)
+            q = state["quarter"] if state["pixel_values"] is pixel_values else None
+            if q is not None and pixel_values.shape[-1] // 4 == size == p and tuple(q.shape[-2:]) == (size, size):
+                self.encoders_resize[which] = "pyramid"
+                return q
+            self.encoders_resize[which] = "aten"
+            return F.interpolate(pixel_values, size=(size, size), mode="bilinear", align_corners=False).contiguous(memory_format=torch.channels_last)
+
+        def check(pixel_values):
+            if pixel_values.dtype != torch.float32 or pixel_values.dim() != 4 or pixel_values.shape[1] != 3:
+                raise NotImplementedError(f"encoders={mode!r}: float32 [B, 3, S, S] pixel values expected -- refusing to fall back silently")
+
+        pe_mod = m.depth_pro.encoder.patch_encoder
+        run_patch = make_encoder(pe_mod.model)
+        hook_ids = [int(i) for i in pe_mod.intermediate_hook_ids]
+
+        def patch_fwd(pixel_values):
+            check(pixel_values)
+            B, _, H, W = pixel_values.shape
+            if H != W or H % 4:
+                raise NotImplementedError(f"encoders={mode!r}: a {H} x {W} input -- the pyramid kernel takes a square side that is a multiple of 4")
+            lv = depth_pro.pyramid_levels(H, p, ratios, overlaps)   # low resolution first
+            patches = R.depthpro_patches(pixel_values.contiguous(), p, [lv[2][2], lv[1][2], lv[0][2]])
+            state["pixel_values"], state["quarter"] = pixel_values, (patches[-B:] if lv[0][3] == 1 else None)
+            last, kept = run_patch(patches, set(hook_ids))
+            bh, bw = base_size(pe_mod, H, W)
+            feats, start = [None] * 3, 0
+            for i in (2, 1, 0):   # the stack holds the high-resolution patches first, the features are listed low resolution first
+                cnt = lv[i][3] ** 2 * B
+                feats[i] = merge(last[start:start + cnt], B, int(pe_mod.merge_padding_value * (1 / ratios[i])), bh * 2 ** i, bw * 2 ** i)
+                start += cnt
+            for i in hook_ids:
+                feats.append(merge(kept[i], B, int(pe_mod.merge_padding_value * (1 / ratios[-1])), bh * 4, bw * 4))
+            return feats
+        pe_mod.forward = patch_fwd
+
+        ie_mod = m.depth_pro.encoder.image_encoder
+        run_image = make_encoder(ie_mod.model)
+
+        def image_fwd(pixel_values, output_attentions=False, output_hidden_states=False, return_dict=True):
+            check(pixel_values)
+            if output_attentions or output_hidden_states:
+                raise NotImplementedError(f"encoders={mode!r}: the routed image encoder keeps no attentions or hidden states")
+            B, _, H, W = pixel_values.shape
+            last, _ = run_image(own_input("image", cfg.image_model_config, pixel_values))
+            feats = merge(last, B, 0, *base_size(ie_mod, H, W))
+            return DepthProOutput(last_hidden_state=last, features=feats) if return_dict else (last, feats)
+        ie_mod.forward = image_fwd
+
+        if m.fov_model is not None:
+            fe_mod = m.fov_model.fov_encoder
+            run_fov = make_encoder(fe_mod.model)
+            neck = fe_mod.neck
+            neck_img = R.gemm_x3_pack(neck.weight, mode)
+
+            def fov_fwd(pixel_values):
+                check(pixel_values)
+                B, _, H, W = pixel_values.shape
+                last, _ = run_fov(own_input("fov", cfg.fov_model_config, pixel_values))
+                state["pixel_values"] = state["quarter"] = None   # the last reader of the forward in flight
+                return merge(R.linear_x3(last, neck_img, neck.out_features, neck.bias, mode=mode), B, 0, *base_size(fe_mod, H, W))
+            fe_mod.forward = fov_fwd
+        self.encoders = mode
+
+    def _split_block(self, stash, pad_state, wqkv, bqkv, wo, bo, w1, b1, w2, b2, nh, hd, scaling, n1, n2, act, nxt, mode=None):
         """``x -> block(x)`` for one pre-LayerNorm transformer block (Dinov2Layer, DPTViTLayer) in the split arithmetic of ``self.gemm``: the weights are split and
         packed once; q / k / v as one GEMM, vd3d_attention_x3 on its output, the output projection, fc1 with the exact GELU in its epilogue (any other
         activation runs behind it), fc2; both residual-add + LayerNorm pairs as vd3d_add_layernorm, the NEXT block's first LayerNorm (``nxt``) computed with
-        this block's second residual add and handed over through ``stash``.  Returns the residual stream, as the stock block does."""
-        R, gm = self.renderer, self.gemm
+        this block's second residual add and handed over through ``stash``.  Returns the residual stream, as the stock block does.  ``mode``: the split arithmetic
+        where it is not the pipe's ``gemm`` (DepthPro's ``encoders=``)."""
+        R, gm = self.renderer, mode or self.gemm
         gelu_ok = isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none" or type(act).__name__ == "GELUActivation"
         x3 = dict(qkv=(R.gemm_x3_pack(wqkv, gm), wqkv.shape[0]), wo=(R.gemm_x3_pack(wo, gm), wo.shape[0]),
                   fc1=(R.gemm_x3_pack(w1, gm), w1.shape[0]), w2=(R.gemm_x3_pack(w2, gm), w2.shape[0]), gelu=bool(gelu_ok), mode=gm)
@@ -1381,7 +1584,7 @@ class DepthPipe:
         def fwd(x):
             B, T, d = x.shape
             if not (x.dtype == torch.float32 and x.is_contiguous() and d in (384, 768, 1024)):
-                raise NotImplementedError(f"gemm={gm!r}: hidden size {d} / dtype {x.dtype} not built (float32, 384 / 768 / 1024) -- refusing to fall back silently")
+                raise NotImplementedError(f"{'encoders' if mode else 'gemm'}={gm!r}: hidden size {d} / dtype {x.dtype} not built (float32, 384 / 768 / 1024) -- refusing to fall back silently")
             h = stash["h"] if stash["x"] is x else R.add_layernorm(x, None, n1)[1]
             stash["x"] = stash["h"] = None
             qkv = lin(h, "qkv", bqkv)

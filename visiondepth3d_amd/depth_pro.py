@@ -1,6 +1,8 @@
 """DepthPro (``apple/DepthPro-hf``, ``DepthProForDepthEstimation``) behind DepthPipe: the published geometry; the image processor and its post-process stated
 in torch (what the two kernels of csrc/vd3d_depthpro.hip are held to, and what runs where there is no renderer); and the model's patch order and merge geometry
-stated in NumPy (no kernel runs them: the network is the stock module graph; they pin down split_to_patches / merge_patches for whoever routes it).
+stated in NumPy: ``patches_statement`` and ``merge_statement`` are what the two kernels of csrc/vd3d_depthpro_pyramid.hip (``vd3d_depthpro_patches_f32``,
+``vd3d_depthpro_merge_f32``) give bit for bit (tests/test_hip_depth_pro_pyramid.py).  Those kernels run under ``DepthPipe(encoders="bf16x3" | "fp16x2")``, which
+routes the three encoders (``DepthPipe._route_depth_pro_encoders``); by default the network is the stock module graph and no kernel runs them.
 
 Line numbers are those of the installed transformers: ``models/depth_pro/modeling_depth_pro.py`` (M), ``models/depth_pro/image_processing_depth_pro.py`` (P)
 and ``image_processing_backends.py`` (B).

@@ -1391,6 +1391,36 @@ class Renderer:
         _lib.check(self._L.vd3d_depthpro_post_f32(self._ctx, _ptr(pred), _ptr(fov) if fov is not None else None, B, S, int(oH), int(oW), _ptr(out)))
         return out
 
+    def depthpro_patches(self, pixel_values: torch.Tensor, p: int, strides) -> torch.Tensor:
+        """DepthProPatchEncoder's patch pyramid in one launch: contiguous float32 pixel_values [B, 3, S, S] (S a multiple of 4) -> the stack its ViT sees,
+        logical shape [(n1 + n2 + n4) B, 3, p, p] in channels_last memory (what ``patchify`` takes): full-resolution patches first, then the half level, then the
+        quarter level, patch-major and batch-minor inside a level.  ``strides``: (full, half, quarter), each int(p (1 - overlap))
+        (include/vd3d.h vd3d_depthpro_patches_f32; ``depth_pro.patches_statement``)."""
+        x = pixel_values
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or not x.is_contiguous():
+            raise ValueError("depthpro_patches: contiguous float32 [B, 3, S, S] pixel values expected")
+        B, _, S, _ = x.shape
+        p, st = int(p), [int(v) for v in strides]
+        n = int(self._L.vd3d_depthpro_patches_count(S, p, *st))
+        if n < 1:
+            raise ValueError(f"depthpro_patches: a {S} x {S} image (a multiple of 4 expected) holds no {p} x {p} patch at a quarter of its size, or a stride of {st} is below 1")
+        out = torch.empty((n * B, p, p, 3), dtype=torch.float32, device=x.device)
+        self._enter(x, out)
+        _lib.check(self._L.vd3d_depthpro_patches_f32(self._ctx, _ptr(x), B, S, p, *st, _ptr(out)))
+        return out.permute(0, 3, 1, 2)   # NCHW view of NHWC storage == torch.channels_last
+
+    def depthpro_merge(self, rows: torch.Tensor, B: int, g: int, padding: int, oh: int, ow: int) -> torch.Tensor:
+        """reconstruct_feature_maps in one launch: contiguous float32 token rows [n B, T, C] (T >= g^2: the leading tokens are dropped) -> contiguous NHWC
+        [B, oh, ow, C]: the patches merged with ``min(g // 4, padding)`` tokens trimmed on every edge that meets another patch, then ATen's bilinear resize, skipped
+        where the merged size is the output size (include/vd3d.h vd3d_depthpro_merge_f32; ``depth_pro.merge_statement``)."""
+        if rows.dtype != torch.float32 or rows.dim() != 3 or not rows.is_contiguous() or rows.shape[0] % int(B):
+            raise ValueError("depthpro_merge: contiguous float32 token rows [n B, T, C] expected")
+        nB, T, Cc = rows.shape
+        out = torch.empty((int(B), int(oh), int(ow), Cc), dtype=torch.float32, device=rows.device)
+        self._enter(rows, out)
+        _lib.check(self._L.vd3d_depthpro_merge_f32(self._ctx, _ptr(rows), nB // int(B), int(B), T, Cc, int(g), int(padding), int(oh), int(ow), _ptr(out)))
+        return out
+
     def detect_black_bars(self, frame_bgr: torch.Tensor):
         """detect_black_bars(frame_to_tensor(frame)) (core/render_3d.py:293-316) on a uint8 BGR frame -> (top, bottom)."""
         f = frame_bgr.to(self.device, torch.uint8).contiguous()
