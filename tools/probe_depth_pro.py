@@ -151,8 +151,9 @@ def _full_model():
 
 def encoders(frames):
     import copy
-    from visiondepth3d_amd.depth import DepthPipe, patch_embedding_gemm_weight
+    from visiondepth3d_amd.depth import DepthPipe, patch_embedding_rows
     from visiondepth3d_amd.render_3d import Renderer
+    from visiondepth3d_amd.vit_blocks import dinov2_operands, encoder_blocks
     R = Renderer(0)
     model = _full_model()
     pipes = {str(mode): DepthPipe("depth-pro", renderer=R, model=copy.deepcopy(model), encoders=mode) for mode in (None, "bf16x3", "fp16x2")}
@@ -168,17 +169,16 @@ def encoders(frames):
         pipe = pipes[mode]
         net = pipe.model
         vits = [net.depth_pro.encoder.patch_encoder.model, net.depth_pro.encoder.image_encoder.model, net.fov_model.fov_encoder.model]
-        packed = [R.gemm_x3_pack(patch_embedding_gemm_weight(v.embeddings.patch_embeddings.projection.weight), mode) for v in vits]
-        blocks = [pipe._split_layers(v.encoder.layer, mode) for v in vits]
+        embeds = [patch_embedding_rows(R, v.embeddings.patch_embeddings.projection, mode) for v in vits]
+        blocks = [encoder_blocks(R, [dinov2_operands(lay) for lay in v.encoder.layer], mode, keyword="encoders") for v in vits]
         for B in frames:
             x = R.depthpro_preprocess(fr[:B], 1536, half, half)
 
             @torch.no_grad()
             def embed():
                 patches = R.depthpro_patches(x, 384, [288, 192, 384])
-                for v, img, inp in zip(vits, packed, (patches, patches[-B:], patches[-B:])):
-                    pe = v.embeddings.patch_embeddings.projection
-                    tok = R.linear_x3(R.patchify(inp, 16), img, 1024, pe.bias, mode=mode)
+                for v, rows, inp in zip(vits, embeds, (patches, patches[-B:], patches[-B:])):
+                    tok = rows(inp)
                     torch.cat((v.embeddings.cls_token.expand(tok.shape[0], -1, -1), tok), dim=1) + v.embeddings.position_embeddings
             seqs = [torch.randn(n, 577, 1024, device="cuda") * 0.5 for n in (35 * B, B, B)]
 
@@ -195,7 +195,7 @@ def encoders(frames):
                 R.depthpro_merge(t, B, 24, 3, 96, 96), R.depthpro_merge(t, B, 24, 3, 96, 96), R.depthpro_merge(seqs[1], B, 24, 0, 24, 24)
             r = rounds({"pyramid_and_embeddings": embed, "encoder_blocks": run_blocks, "merges": merges}, 2, warm=1)
             print(json.dumps(dict(what=f"parts_{mode}_B{B}", ms=r)))
-        del blocks, packed
+        del blocks, embeds
     # the two hand-over layouts of the merge in front of the library neck, fusion stage and head: the [B, C, oh, ow] view of the NHWC storage, or a contiguous copy
     pipe = pipes["bf16x3"]
     for B in frames:

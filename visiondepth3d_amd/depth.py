@@ -30,6 +30,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .vit_blocks import dinov2_operands, dpt_vit_operands, encoder_blocks, head_geometry_ok, query_padding
+
 # Architectures of the reference's model list (core/render_depth.py:686-712) that go through its Hugging Face branch
 # (AutoModelForDepthEstimation, :756-760,823-824).  "da" = DepthAnythingForDepthEstimation on a DINOv2 backbone: Depth-Anything V1
 # (LiheYoung/depth-anything-*-hf), V2 (depth-anything/Depth-Anything-V2-*-hf) and Distill-Any-Depth
@@ -252,6 +254,31 @@ def patch_embedding_gemm_weight(w: torch.Tensor) -> torch.Tensor:
     to the next multiple of 16 (vd3d_gemm_x3's K unit; p = 14: 588 -> 592).  vd3d_patchify_f32 writes the matching rows, zero tail included."""
     C, k = w.shape[0], w[0].numel()
     return F.pad(w.detach().reshape(C, k), (0, (k + 15) // 16 * 16 - k)).contiguous()
+
+
+def patch_embedding_conv_ok(conv) -> bool:
+    """Conv2d(3, C, kernel_size=p, stride=p), p <= 64: the patch embeddings vd3d_patchify_f32 takes."""
+    p = conv.kernel_size[0] if isinstance(conv, torch.nn.Conv2d) else 0
+    return 0 < p <= 64 and conv.kernel_size == (p, p) and conv.stride == (p, p) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels == 3
+
+
+def patch_embedding_rows(R, conv, mode: str):
+    """A patch-embedding convolution (``patch_embedding_conv_ok``) as vd3d_patchify_f32 + vd3d_gemm_x3 in ``mode``, its weight packed once, here: returns
+    ``x -> [B, T - 1, C]`` for a float32 [B, 3, th, tw] image in channels_last memory, bias included."""
+    img = R.gemm_x3_pack(patch_embedding_gemm_weight(conv.weight), mode)
+    return lambda x: R.linear_x3(R.patchify(x, conv.kernel_size[0]), img, conv.out_channels, conv.bias, mode=mode)
+
+
+def _memoise(obj, attr: str, key):
+    """``obj.attr(t, *args)`` -- a position-embedding interpolation, a constant of the input size -- memoised per ``key(t, *args)``."""
+    orig, cache = getattr(obj, attr), {}
+
+    def cached(t, *args):   # (positional, as the embeddings modules call it)
+        k = key(t, *args)
+        if k not in cache:
+            cache[k] = orig(t, *args).detach()
+        return cache[k]
+    setattr(obj, attr, cached)
 
 
 def im2col_gemm_weight(w: torch.Tensor) -> torch.Tensor:
@@ -849,7 +876,7 @@ class DepthPipe:
         ``encoders`` (DepthPro only; float32 + ``renderer``): ``None`` (default) -- the stock graph, as above.  ``"bf16x3"`` / ``"fp16x2"`` -- OPT-IN: from ``pixel_values``
         to the inputs of ``DepthProNeck`` (and to the input of the field-of-view model's convolution) no vendor-library call is made: the patch pyramid is one launch
         (``vd3d_depthpro_patches_f32``), the patch embeddings are ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, every ``Dinov2Layer`` of the patch, image and
-        field-of-view encoders is a ``_split_block`` in the named arithmetic, the final LayerNorms are ``vd3d_add_layernorm``, the field-of-view ``neck`` Linear is
+        field-of-view encoders is a ``vit_blocks._split_block`` in the named arithmetic, the final LayerNorms are ``vd3d_add_layernorm``, the field-of-view ``neck`` Linear is
         ``vd3d_gemm_x3`` and every ``reconstruct_feature_maps`` is ``vd3d_depthpro_merge_f32`` (``_route_depth_pro_encoders``).  The neck, the fusion stage, the head
         and the field-of-view convolutions stay the stock module graph on the float32 library, which is why ``gemm=`` / ``self_contained=True`` keep refusing DepthPro.
         ``pipe.encoders`` records the mode (or None), ``pipe.encoders_resize`` whether the image / field-of-view encoders read the pyramid's quarter level
@@ -961,7 +988,7 @@ class DepthPipe:
                 bit_prefix_plan(model.dpt.embeddings.backbone, {id(m): n for n, m in model.named_modules()})
             if scope == "dinov2":
                 bc = model.config.backbone_config
-                if int(bc.hidden_size) not in (384, 768, 1024) or int(bc.hidden_size) != 64 * int(bc.num_attention_heads):
+                if not head_geometry_ok(bc.hidden_size, bc.num_attention_heads):
                     raise NotImplementedError(f"self_contained=True: {name!r}: hidden size {bc.hidden_size} with {bc.num_attention_heads} heads -- vd3d_attention_x3 and "
                                               "vd3d_add_layernorm are built for 384 / 768 / 1024 with 64-wide heads; anything else would run library attention")
                 act2 = getattr(model.head, "activation2", None)
@@ -1069,17 +1096,7 @@ class DepthPipe:
         """DINOv2 re-interpolates its position embedding (bicubic 37x37 -> patch grid) on EVERY forward; for a fixed
         frame size the result is a constant, and ATen's bicubic kernel loops the 384-1024 channels serially per output
         pixel (measured 2.9 ms per forward on MI355X, 14 % of the step).  Memoise it per (height, width)."""
-        emb = self.model.backbone.embeddings
-        orig = emb.interpolate_pos_encoding
-        cache = {}
-
-        def cached(embeddings, height, width):
-            key = (int(height), int(width), embeddings.dtype, embeddings.shape[1])
-            if key not in cache:
-                cache[key] = orig(embeddings, height, width).detach()
-            return cache[key]
-
-        emb.interpolate_pos_encoding = cached
+        _memoise(self.model.backbone.embeddings, "interpolate_pos_encoding", lambda t, height, width: (int(height), int(width), t.dtype, t.shape[1]))
 
     def _count_conv(self, m, y):
         """flops_per_frame: a convolution module m that a rewrite runs without calling it adds, for its output y, what the counting hook would have added."""
@@ -1207,21 +1224,17 @@ class DepthPipe:
         map the module flattens and transposes) as vd3d_patchify_f32 + vd3d_gemm_x3 on the weight reshaped to [C, 3 p^2] and zero-padded to the GEMM's K unit
         (p = 14: 588 -> 592; p = 16: 768, no padding), with its bias: [B, T-1, C] directly.  CLS, the cached position embedding and the final LayerNorm stay ATen
         element-wise / native kernels."""
-        R = self.renderer
         m = pe.projection
         name = self._names[id(m)]
-        p = m.kernel_size[0]
-        if not (isinstance(m, torch.nn.Conv2d) and m.kernel_size == (p, p) and m.stride == (p, p) and m.padding == (0, 0) and m.dilation == (1, 1) and m.groups == 1
-                and m.in_channels == 3 and p <= 64):
+        if not patch_embedding_conv_ok(m):
             raise NotImplementedError(f"self_contained=True: {name}: a patch embedding other than Conv2d(3, C, kernel_size=p, stride=p), p <= 64 -- not built")
-        img = R.gemm_x3_pack(patch_embedding_gemm_weight(m.weight), self.gemm)
+        rows = patch_embedding_rows(self.renderer, m, self.gemm)
 
         def patch_fwd(pixel_values):
             if pixel_values.dtype != torch.float32 or pixel_values.shape[1] != 3:
                 raise NotImplementedError("self_contained=True: the patch embedding takes a float32 [B, 3, th, tw] image")
-            rows = R.patchify(pixel_values.contiguous(memory_format=torch.channels_last), p)   # what depth_preprocess hands over is taken as it is
+            y = rows(pixel_values.contiguous(memory_format=torch.channels_last))   # what depth_preprocess hands over is taken as it is
             self.conv_routes[name] = (self.gemm, "self-contained: vd3d_patchify_f32 + vd3d_gemm_x3")
-            y = R.linear_x3(rows, img, m.out_channels, m.bias, mode=self.gemm)
             self._count_conv(m, y)   # the bypassed Conv2d: 2 (T - 1) C 3 p^2
             return y
         pe.forward = patch_fwd
@@ -1311,95 +1324,13 @@ class DepthPipe:
         """Inference-only rewrite of every Dinov2Layer (same math, fewer launches): q/k/v projections as ONE GEMM
         (N = 3*hidden), LayerScale folded into the output-projection / fc2 weights (lambda * (xW^T + b) == x(lambda*W)^T +
         lambda*b), the attention called directly (float32 with a renderer: vd3d_attention_f32; otherwise SDPA).  Per layer: 4 GEMMs + attention + 2 LN + GELU + 2 adds instead of 6 GEMMs + 13
-        smaller kernels."""
-        layers = list(self.model.backbone.encoder.layer)
-        R = self.renderer
-        # Query-length padding: AOTriton's flash kernel takes a ~1.5x slower path when the QUERY length is not a multiple of
-        # 256 (measured on MI355X: Tq=2443 446 us, Tq=2560 302 us per layer, keys unpadded).  DINOv2 always has an odd token
-        # count (patches + CLS), so the token sequence is padded ONCE after the embeddings with dummy tokens that are never
-        # used as keys/values (k, v are sliced to the real length) and are dropped before the final layer norm: exact.
-        pad_state = {"T": None}
+        smaller kernels.  The block itself is ``vit_blocks``: ``dinov2_operands`` per layer, ``encoder_blocks`` in the pipe's ``gemm``."""
         bb = self.model.backbone
-        if self.device.type == "cuda":
-            def pad_tokens(_mod, _inp, out):
-                T = out.shape[1]
-                Tp = -(-T // 256) * 256
-                pad_state["T"] = None
-                if out.dtype == torch.bfloat16 and Tp != T and Tp <= T * 1.1:
-                    pad_state["T"] = T
-                    return F.pad(out, (0, 0, 0, Tp - T))
-                return out
-            bb.embeddings.register_forward_hook(pad_tokens)
-            final_ln = bb.layernorm.forward
-            bb.layernorm.forward = lambda x: final_ln(x if pad_state["T"] is None else x[:, :pad_state["T"]])
-        stash = {"x": None, "h": None}   # LayerNorm1(x) computed by the PREVIOUS layer's fused add+LayerNorm launch
-        for li, layer in enumerate(layers):
-            wqkv, bqkv, wo, bo, fc1, w2, b2, nh, hd, scaling, n1, n2, act = self._dinov2_layer_operands(layer)
-            nxt = layers[li + 1].norm1 if li + 1 < len(layers) else None
-            x3 = None
-            if self.gemm != "f32":
-                x3 = self._split_block(stash, pad_state, wqkv, bqkv, wo, bo, fc1.weight, fc1.bias, w2, b2, nh, hd, scaling, n1, n2, act, nxt)
-
-            def fwd(x, wqkv=wqkv, bqkv=bqkv, wo=wo, bo=bo, fc1=fc1, w2=w2, b2=b2, nh=nh, hd=hd, scaling=scaling, n1=n1, n2=n2,
-                    act=act, nxt=nxt, x3=x3):
-                if x3 is not None:
-                    return x3(x)
-                B, T, d = x.shape
-                hip = R is not None and x.dtype in (torch.bfloat16, torch.float32) and x.is_contiguous() and d in (384, 768, 1024)
-                if hip:   # residual add + LayerNorm pairs as single HIP launches (vd3d_add_layernorm)
-                    h = stash["h"] if stash["x"] is x else R.add_layernorm(x, None, n1)[1]
-                    stash["x"] = stash["h"] = None
-                else:
-                    h = n1(x)
-                qkv = F.linear(h, wqkv, bqkv)
-                if R is not None and x.dtype == torch.float32 and hd == 64 and not pad_state["T"]:   # the library's exact-float32 attention
-                    o = R.attention_f32(qkv, nh, scaling)
-                else:
-                    qkv = qkv.view(B, T, 3, nh, hd)
-                    Tk = pad_state["T"] or T   # real tokens only on the key/value side
-                    q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :Tk, 1].transpose(1, 2), qkv[:, :Tk, 2].transpose(1, 2)
-                    o = F.scaled_dot_product_attention(q, k, v, scale=scaling).transpose(1, 2).reshape(B, T, d)
-                a = F.linear(o, wo, bo)
-                if not hip:
-                    x = x + a
-                    return x + F.linear(act(fc1(n2(x))), w2, b2)
-                x, h = R.add_layernorm(x, a, n2)
-                m = F.linear(act(fc1(h)), w2, b2)
-                if nxt is None:
-                    return x + m
-                x, hn = R.add_layernorm(x, m, nxt)
-                stash["x"], stash["h"] = x, hn
-                return x
-
-            layer.forward = fwd
-
-    @staticmethod
-    def _dinov2_layer_operands(layer):
-        """One Dinov2Layer as the operands of the fused block: q / k / v weights and biases concatenated for ONE GEMM, LayerScale folded into the output projection
-        and fc2 (lambda * (xW^T + b) == x(lambda*W)^T + lambda*b) -> (wqkv, bqkv, wo, bo, fc1 module, w2, b2, heads, head size, scaling, norm1, norm2, activation)."""
-        att, out = layer.attention.attention, layer.attention.output.dense
-        wqkv = torch.cat([att.query.weight, att.key.weight, att.value.weight], 0).contiguous()
-        bqkv = torch.cat([att.query.bias, att.key.bias, att.value.bias], 0).contiguous()
-        l1, l2 = layer.layer_scale1.lambda1.float(), layer.layer_scale2.lambda1.float()
-        wo = (out.weight.float() * l1[:, None]).to(out.weight.dtype).contiguous()
-        bo = (out.bias.float() * l1).to(out.bias.dtype).contiguous()
-        fc1, fc2 = layer.mlp.fc1, layer.mlp.fc2
-        w2 = (fc2.weight.float() * l2[:, None]).to(fc2.weight.dtype).contiguous()
-        b2 = (fc2.bias.float() * l2).to(fc2.bias.dtype).contiguous()
-        return wqkv, bqkv, wo, bo, fc1, w2, b2, att.num_attention_heads, att.attention_head_size, att.scaling, layer.norm1, layer.norm2, layer.mlp.activation
-
-    @torch.no_grad()
-    def _split_layers(self, layers, mode):
-        """Every Dinov2Layer of ``layers`` (one encoder) as a ``_split_block`` in ``mode``: the weights are folded (_dinov2_layer_operands), split and packed once,
-        here; the blocks share one ``stash`` of their own and there is no query padding.  Returns the block functions in order; the modules are left as they are."""
-        layers = list(layers)
-        stash, pad_state = {"x": None, "h": None}, {"T": None}
-        fwds = []
-        for li, layer in enumerate(layers):
-            wqkv, bqkv, wo, bo, fc1, w2, b2, nh, hd, scaling, n1, n2, act = self._dinov2_layer_operands(layer)
-            nxt = layers[li + 1].norm1 if li + 1 < len(layers) else None
-            fwds.append(self._split_block(stash, pad_state, wqkv, bqkv, wo, bo, fc1.weight, fc1.bias, w2, b2, nh, hd, scaling, n1, n2, act, nxt, mode=mode))
-        return fwds
+        # query padding is the library back-end's: the split modes are float32 only (the constructor refuses anything else) and the hook pads bf16 alone
+        pad_state = query_padding(bb.embeddings, bb.layernorm) if self.device.type == "cuda" and self.gemm == "f32" else None
+        layers = list(bb.encoder.layer)
+        for layer, blk in zip(layers, encoder_blocks(self.renderer, [dinov2_operands(lay) for lay in layers], self.gemm, pad_state=pad_state)):
+            layer.forward = blk
 
     def _depth_pro_encoders_scope(self, mode, processor):
         """``encoders=``: what the routing needs of the model and its processor, read from the module graph and the configuration only (nothing is moved or
@@ -1420,15 +1351,12 @@ class DepthPipe:
             if type(vit).__name__ != "Dinov2Model":
                 raise NotImplementedError(f"{tag}: {what}: the {which} encoder is a {type(vit).__name__} -- _split_block is built for Dinov2Model encoders")
             d, nh = int(vit.config.hidden_size), int(vit.config.num_attention_heads)
-            if d not in (384, 768, 1024) or d != 64 * nh:
+            if not head_geometry_ok(d, nh):
                 raise NotImplementedError(f"{tag}: {what}: the {which} encoder has hidden size {d} with {nh} heads -- vd3d_attention_x3 and vd3d_add_layernorm are "
                                           "built for 384 / 768 / 1024 with 64-wide heads")
             if getattr(vit.config, "use_swiglu_ffn", False):
                 raise NotImplementedError(f"{tag}: {what}: the {which} encoder has a SwiGLU feed-forward -- _split_block is built for fc1 / activation / fc2")
-            pe = vit.embeddings.patch_embeddings.projection
-            k = pe.kernel_size[0]
-            if not (isinstance(pe, torch.nn.Conv2d) and pe.kernel_size == (k, k) and pe.stride == (k, k) and pe.padding == (0, 0) and pe.dilation == (1, 1)
-                    and pe.groups == 1 and pe.in_channels == 3 and k <= 64):
+            if not patch_embedding_conv_ok(vit.embeddings.patch_embeddings.projection):
                 raise NotImplementedError(f"{tag}: {what}: the {which} encoder's patch embedding is not Conv2d(3, C, kernel_size=p, stride=p), p <= 64 -- "
                                           "vd3d_patchify_f32 does not take it")
         ratios = [float(r) for r in cfg.scaled_images_ratios]
@@ -1454,7 +1382,7 @@ class DepthPipe:
         element-wise one (the class-token concatenation, the position-embedding add, the last block's residual add) -- no hipBLASLt, MIOpen or AOTriton call:
           * the patch pyramid: one launch of vd3d_depthpro_patches_f32, written in the memory patchify reads;
           * per encoder: vd3d_patchify_f32 + vd3d_gemm_x3 for the patch embedding, the class token and the (memoised) position embedding added, every Dinov2Layer a
-            _split_block in ``mode`` (_split_layers: one weight split / pack per encoder, here), the hook layers' residual streams kept, the final LayerNorm as
+            _split_block in ``mode`` (vit_blocks.encoder_blocks: one weight split / pack per encoder, here), the hook layers' residual streams kept, the final LayerNorm as
             add_layernorm(x, None, ln);
           * every reconstruct_feature_maps: vd3d_depthpro_merge_f32, handed on as the [B, C, oh, ow] view of its NHWC storage (channels_last, what the library
             convolutions behind it read);
@@ -1471,17 +1399,15 @@ class DepthPipe:
         state = {"pixel_values": None, "quarter": None}   # the pyramid's quarter level of the forward in flight, for the image / field-of-view encoders
 
         def make_encoder(vit):
-            emb, pe = vit.embeddings, vit.embeddings.patch_embeddings.projection
-            k, C = pe.kernel_size[0], pe.out_channels
-            img = R.gemm_x3_pack(patch_embedding_gemm_weight(pe.weight), mode)
-            blocks = self._split_layers(vit.encoder.layer, mode)
+            emb = vit.embeddings
+            rows = patch_embedding_rows(R, emb.patch_embeddings.projection, mode)
+            blocks = encoder_blocks(R, [dinov2_operands(lay) for lay in vit.encoder.layer], mode, keyword="encoders")
             pos = {}
 
             def run(x, hooks=()):
                 """[N, 3, h, w] in channels_last memory -> (LayerNorm(last hidden state), {hook: that layer's residual stream})."""
                 N, _, h, w = x.shape
-                tok = R.linear_x3(R.patchify(x, k), img, C, pe.bias, mode=mode)
-                t = torch.cat((emb.cls_token.expand(N, -1, -1), tok), dim=1)
+                t = torch.cat((emb.cls_token.expand(N, -1, -1), rows(x)), dim=1)
                 if (h, w) not in pos:   # a constant of the input size (the parameter itself where the grid is the trained one)
                     pos[(h, w)] = emb.interpolate_pos_encoding(t, h, w).detach()
                 t = t + pos[(h, w)]
@@ -1567,46 +1493,6 @@ class DepthPipe:
             fe_mod.forward = fov_fwd
         self.encoders = mode
 
-    def _split_block(self, stash, pad_state, wqkv, bqkv, wo, bo, w1, b1, w2, b2, nh, hd, scaling, n1, n2, act, nxt, mode=None):
-        """``x -> block(x)`` for one pre-LayerNorm transformer block (Dinov2Layer, DPTViTLayer) in the split arithmetic of ``self.gemm``: the weights are split and
-        packed once; q / k / v as one GEMM, vd3d_attention_x3 on its output, the output projection, fc1 with the exact GELU in its epilogue (any other
-        activation runs behind it), fc2; both residual-add + LayerNorm pairs as vd3d_add_layernorm, the NEXT block's first LayerNorm (``nxt``) computed with
-        this block's second residual add and handed over through ``stash``.  Returns the residual stream, as the stock block does.  ``mode``: the split arithmetic
-        where it is not the pipe's ``gemm`` (DepthPro's ``encoders=``)."""
-        R, gm = self.renderer, mode or self.gemm
-        gelu_ok = isinstance(act, torch.nn.GELU) and getattr(act, "approximate", "none") == "none" or type(act).__name__ == "GELUActivation"
-        x3 = dict(qkv=(R.gemm_x3_pack(wqkv, gm), wqkv.shape[0]), wo=(R.gemm_x3_pack(wo, gm), wo.shape[0]),
-                  fc1=(R.gemm_x3_pack(w1, gm), w1.shape[0]), w2=(R.gemm_x3_pack(w2, gm), w2.shape[0]), gelu=bool(gelu_ok), mode=gm)
-
-        def lin(t, key, bias, gelu=False):
-            return R.linear_x3(t if t.is_contiguous() else t.contiguous(), x3[key][0], x3[key][1], bias, gelu=gelu, mode=gm)
-
-        def fwd(x):
-            B, T, d = x.shape
-            if not (x.dtype == torch.float32 and x.is_contiguous() and d in (384, 768, 1024)):
-                raise NotImplementedError(f"{'encoders' if mode else 'gemm'}={gm!r}: hidden size {d} / dtype {x.dtype} not built (float32, 384 / 768 / 1024) -- refusing to fall back silently")
-            h = stash["h"] if stash["x"] is x else R.add_layernorm(x, None, n1)[1]
-            stash["x"] = stash["h"] = None
-            qkv = lin(h, "qkv", bqkv)
-            if hd == 64 and not pad_state["T"]:   # the library's split-bf16 attention (every DINOv2 size and ViT-L/16 have 64-wide heads)
-                o = R.attention_x3(qkv, nh, scaling, mode=gm)
-            else:
-                qkv = qkv.view(B, T, 3, nh, hd)
-                Tk = pad_state["T"] or T
-                q, k, v = qkv[:, :, 0].transpose(1, 2), qkv[:, :Tk, 1].transpose(1, 2), qkv[:, :Tk, 2].transpose(1, 2)
-                o = F.scaled_dot_product_attention(q, k, v, scale=scaling).transpose(1, 2).reshape(B, T, d)
-            a = lin(o, "wo", bo)
-            x, h = R.add_layernorm(x, a, n2)
-            hid = lin(h, "fc1", b1, gelu=True) if x3["gelu"] else act(lin(h, "fc1", b1))
-            m = lin(hid, "w2", b2)
-            if nxt is None:
-                return x + m
-            x, hn = R.add_layernorm(x, m, nxt)
-            stash["x"], stash["h"] = x, hn
-            return x
-
-        return fwd
-
     def _split_scope(self, fuse_backbone: bool = True) -> str:
         """Which rewrite ``gemm="bf16x3" / "fp16x2"`` applies to this model: "dinov2" (DepthAnythingForDepthEstimation on Dinov2Backbone), "dpt-vit"
         (DPTForDepthEstimation on its plain ViT encoder with readout_type="project": DPT-Large) or "dpt-hybrid" (DPTForDepthEstimation with is_hybrid in the
@@ -1658,7 +1544,7 @@ class DepthPipe:
         if cfg.use_batch_norm_in_fusion_residual:
             refuse("batch norm in the fusion residual units")
         d, nh = int(cfg.hidden_size), int(cfg.num_attention_heads)
-        if d not in (384, 768, 1024) or d // nh != 64 or d % nh:
+        if not head_geometry_ok(d, nh):
             refuse(f"hidden size {d} with {nh} heads (built: 384 / 768 / 1024, 64-wide heads)")
         for lay in m.neck.reassemble_stage.layers:
             r = getattr(lay, "resize", None)   # (DPT-Hybrid's hooks 0 / 1 are nn.Identity layers)
@@ -1720,35 +1606,15 @@ class DepthPipe:
     def _cache_vit_position_embeddings(self):
         """DPTViTEmbeddings re-interpolates its position embedding (bilinear, 24 x 24 -> patch grid) on every forward; for a fixed input size the result is a
         constant.  Memoised per (grid height, grid width, dtype), like _cache_position_embeddings for DINOv2."""
-        emb = self.model.dpt.embeddings
-        orig = emb._resize_pos_embed
-        cache = {}
-
-        def cached(posemb, grid_size_height, grid_size_width, start_index=1):
-            key = (int(grid_size_height), int(grid_size_width), posemb.dtype, int(start_index))
-            if key not in cache:
-                cache[key] = orig(posemb, grid_size_height, grid_size_width, start_index).detach()
-            return cache[key]
-
-        emb._resize_pos_embed = cached
+        _memoise(self.model.dpt.embeddings, "_resize_pos_embed", lambda t, gh, gw, start_index=1: (int(gh), int(gw), t.dtype, int(start_index)))
 
     @torch.no_grad()
     def _fuse_vit_layers(self):
-        """Every DPTViTLayer (ViT-L/16 of DPT-Large) through _split_block -- the same rewrite as _fuse_backbone_layers' split mode: layernorm_before /
-        layernorm_after are its two LayerNorms (eps 1e-12), attention.output.dense the output projection, intermediate.dense fc1 (hidden_act "gelu": exact,
-        in the epilogue), output.dense fc2; there is no LayerScale to fold.  The encoder collects each layer's return value at backbone_out_indices:
-        the residual stream, as in the stock graph."""
+        """Every DPTViTLayer (ViT-L/16 of DPT-Large) as a ``vit_blocks._split_block`` -- the same rewrite as _fuse_backbone_layers' split mode, on
+        ``dpt_vit_operands``.  The encoder collects each layer's return value at backbone_out_indices: the residual stream, as in the stock graph."""
         layers = list(self.model.dpt.encoder.layer)
-        stash, pad_state = {"x": None, "h": None}, {"T": None}
-        for li, layer in enumerate(layers):
-            att, ffn = layer.attention.attention, layer.intermediate
-            wqkv = torch.cat([att.query.weight, att.key.weight, att.value.weight], 0).contiguous()
-            bqkv = None if att.query.bias is None else torch.cat([att.query.bias, att.key.bias, att.value.bias], 0).contiguous()
-            out, fc2 = layer.attention.output.dense, layer.output.dense
-            nxt = layers[li + 1].layernorm_before if li + 1 < len(layers) else None
-            layer.forward = self._split_block(stash, pad_state, wqkv, bqkv, out.weight, out.bias, ffn.dense.weight, ffn.dense.bias, fc2.weight, fc2.bias,
-                                              att.num_attention_heads, att.attention_head_size, att.scaling, layer.layernorm_before, layer.layernorm_after,
-                                              ffn.intermediate_act_fn, nxt)
+        for layer, blk in zip(layers, encoder_blocks(self.renderer, [dpt_vit_operands(lay) for lay in layers], self.gemm)):
+            layer.forward = blk
 
     def _pil_pixel_values(self, frames_bgr: torch.Tensor, inference_size=None) -> torch.Tensor:
         """``front_end="pil"``: the pixel_values the reference's image processor makes of these frames as PIL images (pre-resized to
