@@ -1,7 +1,8 @@
 """GPU test (-m gpu) of the fused depth-net input preparation (vd3d_depth_preprocess, boundary B3 / SURVEY a25) against
 the plain PyTorch float32 statement of the same operator chain (antialiased bicubic resize -> 1/255 -> ImageNet
 normalise).  Floating-point kernel: tolerance = bf16 rounding of the result (1/2 ulp = 2^-9 relative) plus the float32
-association noise of the 2-D filter sums."""
+association noise of the 2-D filter sums.  These are the loose checks on smooth frames; the kernel's bits are pinned on random bytes
+against its NumPy statement in tests/test_hip_depthprep_bits.py, and the statement against float64 in tests/test_depthprep_host.py."""
 import numpy as np
 import pytest
 

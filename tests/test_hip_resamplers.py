@@ -3,7 +3,8 @@
   depth hand-off   vd3d_depth_handoff_form: 1 = k_handoff (sixteen taps from memory per output pixel), 2 = k_handoff_sep (one wave walks a band of output rows with
                    the four horizontally interpolated prediction rows in registers) -- bit for bit against the C oracle and against each other
   input prep       vd3d_depth_preprocess_form: 1 = k_depth_prep (32 x 8 tiles), 2 = k_depth_prep_strip (32-column strips of 32-row bands, dword loads) -- torch.equal
-  up-sampling      k_upsample_bilinear[_bias]_nhwc_f32 -- torch.equal against the expression of include/vd3d.h stated with element-wise float32 torch operations
+  up-sampling      k_upsample_bilinear[_bias]_nhwc_f32 -- torch.equal against the expression of include/vd3d.h stated with element-wise float32 torch operations;
+                   k_upsample_bilinear_nhwc (bf16) -- the same expression on the widened bf16 inputs, rounded once with the kernel's f2bf, on bits
 
 Every kernel is a fixed sequence of IEEE float32 operations (the library is built with -ffp-contract=off), so every comparison here is an equality."""
 import numpy as np
@@ -212,3 +213,27 @@ def test_upsample_f32_bit_exact(R, B, C, src, dst):
     assert torch.equal(got.permute(0, 2, 3, 1), _upsample_ref(x, oh, ow, None))
     got = R.upsample_bilinear_bias(x_cl, (oh, ow), bias)
     assert torch.equal(got.permute(0, 2, 3, 1), _upsample_ref(x, oh, ow, bias))
+
+
+def _f2bf_bits(f):
+    """The kernel's f2bf on a float32 tensor -> bf16 bits as int16: (b + 0x7fff + ((b >> 16) & 1)) >> 16 in 32-bit arithmetic that wraps, as the device's does."""
+    b = f.contiguous().view(torch.int32)
+    return (((b + 0x7fff + ((b >> 16) & 1)) >> 16) & 0xffff).to(torch.int16)
+
+
+@pytest.mark.parametrize("B,C,src,dst", UPSAMPLE_SHAPES, ids=lambda v: "%dx%d" % v if isinstance(v, tuple) else str(v))
+def test_upsample_bf16_bit_exact(R, B, C, src, dst):
+    """One thread = 8 channels: C doubled where it is no multiple of 8 (12 -> 24 keeps a c8 = 3 that is no power of two).  float32 blend of the widened inputs
+    in the float32 kernel's association, one rounding to bf16."""
+    (ih, iw), (oh, ow) = src, dst
+    C = C if C % 8 == 0 else 2 * C
+    assert C % 8 == 0
+    g = torch.Generator(device="cuda").manual_seed(C + ih)
+    buf = (torch.randn(B + 1, ih, iw, C, device="cuda", generator=g) * 3).to(torch.bfloat16)
+    buf[B] = float("nan")                                  # behind the last image: an unclamped x1 or y1 tap of weight 0 poisons the result
+    x = buf[:B]
+    got = R.upsample_bilinear(x.permute(0, 3, 1, 2), (oh, ow))
+    assert got.dtype == torch.bfloat16 and got.shape == (B, C, oh, ow) and got.is_contiguous(memory_format=torch.channels_last)
+    want = _f2bf_bits(_upsample_ref(x.float(), oh, ow, None))
+    assert not bool(torch.isnan(got.float()).any())
+    assert torch.equal(got.permute(0, 2, 3, 1).contiguous().view(torch.int16), want)

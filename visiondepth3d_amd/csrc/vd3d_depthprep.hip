@@ -6,8 +6,10 @@
 // (flip, float cast, upsample_gen2d_aa, div, sub, div, bf16 cast, channels_last copy) and their HBM round trips.
 //
 // Arithmetic follows ATen's upsample_gen2d_aa (float32): weights w_j = cubic((j + xmin - center + 0.5)/scale) normalised
-// by their sum, horizontal sums per input row first, then the vertical sum.  Floating-point kernel: tested against the
-// torch float32 path on the GPU (tests/test_hip_depthprep.py, bf16-ulp tolerance), no CPU oracle.
+// by their sum, horizontal sums per input row first, then the vertical sum.  Floating-point kernel: a fixed sequence of
+// float32 operations, stated in NumPy and held to the float64 operator on the host (tests/test_depthprep_host.py, which
+// also walks the launcher's capacities below over every admitted geometry); both kernels are held to that statement bit
+// for bit (tests/test_hip_depthprep_bits.py) and to the torch float32 path within a tolerance (tests/test_hip_depthprep.py).
 #include "vd3d_dev.h"
 #include "vd3d_kernels.h"
 
