@@ -45,7 +45,9 @@ extern "C" {
  *    and vd3d_depthpro_post_f32 (DepthPro's image-processor front end and post-process), vd3d_head_upconv_gather_f32 (the fine half of the float32 head's
  *    first convolution as coarse GEMM + fine gather), vd3d_head_conv_gather_weight_bytes, vd3d_head_conv_gather_tile, vd3d_head_conv_gather_pack_weights and
  *    vd3d_head_conv_gather_f32 (the float32 head's up-sampling + second convolution + tail as coarse GEMM + fine gather in one launch),
- *    vd3d_depthpro_patches_count, vd3d_depthpro_patches_f32 and vd3d_depthpro_merge_f32 (DepthPro's patch pyramid and patch merge: DepthPipe(encoders=...)). */
+ *    vd3d_depthpro_patches_count, vd3d_depthpro_patches_f32 and vd3d_depthpro_merge_f32 (DepthPro's patch pyramid and patch merge: DepthPipe(encoders=...)),
+ *    vd3d_conv3x3_epi (the stride-1 tile convolution with a residual unit's glue in its epilogue), vd3d_depthpro_head_weight_bytes,
+ *    vd3d_depthpro_head_pack_weights and vd3d_depthpro_head (DepthPro's head behind its first convolution in one launch: DepthPipe(decoder=...)). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -622,6 +624,45 @@ int vd3d_conv3x3_s1_x2(vd3d_ctx* ctx, const float* X, int B, int H, int W, int C
 int64_t vd3d_conv3x3_s2_x2_weight_bytes(int Cin, int Cout);
 int vd3d_conv3x3_s2_x2_pack_weights(vd3d_ctx* ctx, const float* W, int Cin, int Cout, void* image);
 int vd3d_conv3x3_s2_x2(vd3d_ctx* ctx, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, float* Y);
+/* The stride-1 tile convolution with the glue of a pre-activation residual unit in its epilogue -- the residual units and head.layers.0 of
+ * DepthPipe("depth-pro", decoder=...): 3 x 3, stride 1, zero padding 1, float32 NHWC, X [B][H][W][Cin] -> Y (and Yrelu) [B][H][W][Cout], in the arithmetic of
+ * `mode`: VD3D_X3_BF16X3 reads the image of vd3d_conv3x3_x3_pack_weights, VD3D_X3_FP16X2 the image of vd3d_conv3x3_s1_x2_pack_weights (no image format of its
+ * own).  In this order, every step one float32 operation (the library is built without contraction):
+ *   u = the bare sum exactly as vd3d_conv3x3_x3 / vd3d_conv3x3_s1_x2 forms it (same tile, K order and accumulators: acc + lo, times colscale in fp16x2) over X --
+ *       with VD3D_EPI_RELU_IN over (x != x ? x : max(x, 0)), applied to the staged pixels in front of the split: a NaN stays a NaN;
+ *   v = u;  bias != NULL: v = v + bias[oc];  r1 != NULL: v = v + r1[p][oc];  r2 != NULL: v = r2[p][oc] + v;  VD3D_EPI_RELU: v = max(v, 0);
+ *   Y[p][oc] = v;  Yrelu != NULL: Yrelu[p][oc] = max(v, 0).
+ * That is vd3d_nhwc_bias_act_f32's chain: Y and Yrelu EQUAL, bit for bit, what [relu ->] the bias-free convolution -> vd3d_nhwc_bias_act_f32 writes
+ * (tests/test_hip_conv_epi_bits.py), without the bare sum and the ReLU'd input ever reaching memory.  max(NaN, 0) is 0 there and here.  The range and NaN
+ * contract of each mode is the bias-free entry point's; bit for bit repeatable and independent of B.
+ * Rules (VD3D_E_UNSUPPORTED with a message that names the broken one, nothing launched, nothing written): Cin a positive multiple of 16 (fp16x2: at most
+ * 65 536), Cout 32, 64, 128 or 256; H, W >= 1; 1 <= B <= 65 535; X and the image 16-byte aligned, bias / r1 / r2 / Y / Yrelu 4-byte; r1 and r2 are dense
+ * [B][H][W][Cout] maps; Y and Yrelu overlap neither X, r1, r2, the bias, the image nor each other (a workgroup reads the halo its neighbours' tiles would
+ * write).  A mode or a flag bit outside the above is VD3D_E_INVALID. */
+/* Everything behind head.layers.0 of DepthProDepthEstimationHead as ONE launch on the coarse map (DepthPipe("depth-pro", decoder=...)), in the arithmetic of
+ * `mode` (VD3D_X3_BF16X3 | VD3D_X3_FP16X2, the contracts of the tile convolutions above):
+ *   ConvTranspose2d(Cin, Cin, 2, 2) + bt -> Conv2d(Cin, 32, 3, padding 1) + b2 -> ReLU -> Conv2d(32, 1, 1) + b3 -> ReLU:  x [B][h][w][Cin] -> out [B][2h][2w]
+ * The transposed convolution and the 3 x 3 convolution are one linear map: per output phase (p_y, p_x) four taps on the coarse grid (offsets p - 1 and p per
+ * axis), the tap geometry of VD3D_IFN_T4S2.  Wc [16][32][Cin] holds the composed blocks, block (2 p_y + p_x) * 4 + 2 t_y + t_x for tap offset
+ * (p_y + t_y - 1, p_x + t_x - 1): Wc[k] = sum of W3[:, :, dy, dx] @ Wt[:, :, (p_y + dy) & 1, (p_x + dx) & 1]^T over the fine taps that land in the offset
+ * (visiondepth3d_amd.depth.neck_poly_compose(wt, None, w3, 2): float64, rounded once).  The 3 x 3 convolution pads the FINE map with zeros, not with bt, so
+ * the constant term is a table T [3][3][32] indexed by (first / interior / last fine row, likewise the column):
+ * T = b2 + sum of W3[:, :, dy, dx] @ bt over the taps whose fine pixel is inside the map (float64 on the host, rounded once).  Per output pixel, in float32:
+ *   v[oc] = acc + lo (times colscale[oc] in fp16x2) over the taps, 16-channel chunk then tap;  u[oc] = max(v[oc] + T[row class][column class][oc], 0);
+ *   d = sum over oc of w3[oc] * u[oc] as a butterfly over the 32 channels (partner distance 16, 8, 4, 2, 1, in that order);  out = max(d + b3, 0).
+ * max(NaN, 0) is 0, as in vd3d_dpt_head_tail_f32.  No split-K, no atomics: bit for bit repeatable and independent of B.  Neither 2h x 2w x Cin map exists.
+ * The blocks are split and packed once into vd3d_depthpro_head_weight_bytes(mode, Cin) bytes (host-only; < 0: not built): [phase 4][chunk Cin / 16][tap 4] K
+ * steps of [term][k-half 2][oc 32][8] (bf16x3: three exact terms; fp16x2: two terms of 2^e W with e per output channel over all 16 blocks, then colscale[32]),
+ * then a 64-byte zero page; the image belongs to its mode and is only valid for this library version.
+ * Rules (VD3D_E_UNSUPPORTED with a message that names the broken one, nothing launched, nothing written): Cin a positive multiple of 16 (at most 65 536);
+ * 1 <= B <= 65 535; 1 <= h, w <= 16 384; x and the image 16-byte aligned, Wc / T / w3 / out 4-byte; out does not overlap x.  Any other mode: VD3D_E_INVALID. */
+int64_t vd3d_depthpro_head_weight_bytes(int mode, int Cin);
+int vd3d_depthpro_head_pack_weights(vd3d_ctx* ctx, int mode, const float* Wc, int Cin, void* image);
+int vd3d_depthpro_head(vd3d_ctx* ctx, int mode, const float* x, int B, int h, int w, int Cin, const void* w_image, const float* T, const float* w3, float b3,
+                       float* out);
+enum { VD3D_EPI_RELU_IN = 1, VD3D_EPI_RELU = 2 };
+int vd3d_conv3x3_epi(vd3d_ctx* ctx, int mode, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, int flags,
+                     const float* bias_or_null, const float* r1_or_null, const float* r2_or_null, float* Y, float* Yrelu_or_null);
 
 /* The convolutions of the RIFE interpolation network (IFNet HDv3; RifeSession(conv="bf16x3")) in the same bf16x3 arithmetic: exact three-term truncation
  * split of every float32 operand, the products x1 w3, x3 w1, x2 w2, x1 w2, x2 w1 into one float32 accumulator and x1 w1 into another, summed in the epilogue

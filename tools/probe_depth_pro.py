@@ -12,6 +12,15 @@ own parts timed apart, and the two hand-over layouts of the merge in front of th
     python tools/probe_depth_pro.py pyramid [--frames 1 4]
     python tools/probe_depth_pro.py encoders [--frames 1 4]
     python tools/probe_depth_pro.py first --mode bf16x3
+
+and behind profiles/r29_depth_pro_decoder.md (DepthPipe(encoders=..., decoder=...)): vd3d_conv3x3_epi beside the pair of launches it replaces, per argument set
+the decoder uses, at 256 -> 256 channels; vd3d_depthpro_head beside the four launches it replaces, with the peak device memory of both forms; the 1536 x 1536
+forward with encoders=m alone and with decoder=m on top, the decoder apart on the pipe's own features; the cold start with the keyword.
+
+    python tools/probe_depth_pro.py epi [--frames 1 4]
+    python tools/probe_depth_pro.py head [--frames 1 4]
+    python tools/probe_depth_pro.py decoder [--frames 1 4]
+    python tools/probe_depth_pro.py first --mode bf16x3 --decoder
 """
 import argparse
 import json
@@ -214,26 +223,138 @@ def encoders(frames):
     R.close()
 
 
-def first(mode):
+def epi(frames):
+    """vd3d_conv3x3_epi against bias-free convolution + vd3d_nhwc_bias_act_f32 on the same buffers: 256 -> 256 channels on the fusion stage's maps."""
+    from visiondepth3d_amd.render_3d import Renderer
+    CL = torch.channels_last
+    R = Renderer(0)
+    w = torch.randn(256, 256, 3, 3, device="cuda") * 0.02
+    bias = torch.randn(256, device="cuda")
+    sets = {"relu_in+bias+relu": dict(relu_in=True, relu=True), "bias+r1": dict(r1=True), "bias+r1+r2": dict(r1=True, r2=True), "bias": dict()}
+    for mode in ("bf16x3", "fp16x2"):
+        img = R.conv3x3_tile_pack(w, mode, 1)
+        for side in (96, 384, 768):
+            for B in frames:
+                x, r1, r2 = (torch.randn(B, 256, side, side, device="cuda").contiguous(memory_format=CL) for _ in range(3))
+                for name, s in sets.items():
+                    kw = dict(bias=bias, r1=r1 if s.get("r1") else None, r2=r2 if s.get("r2") else None, relu=bool(s.get("relu")))
+
+                    def fused():
+                        return R.conv3x3_epi(x, img, 256, mode, relu_in=bool(s.get("relu_in")), **kw)
+
+                    def pair():
+                        return R.bias_act(R.conv3x3_tile(torch.relu(x) if s.get("relu_in") else x, img, 256, mode, 1), **kw)
+
+                    def bare():
+                        return R.conv3x3_tile(x, img, 256, mode, 1)
+                    assert torch.equal(fused(), pair())
+                    r = rounds({"fused": fused, "pair": pair, "bare_convolution": bare}, 3 if side == 768 else 10, warm=1)
+                    print(json.dumps(dict(what=f"epi_{mode}_{side}_B{B}_{name}", ms=r, fused_over_pair=r["fused"][0] / r["pair"][0])))
+                del x, r1, r2
+    R.close()
+
+
+def head(frames):
+    """vd3d_depthpro_head against the four launches it replaces (GEMM, depth-to-space, bias-free tile convolution, vd3d_dpt_head_tail_f32): 768 x 768 -> 1536 x 1536,
+    128 channels, with the peak device memory of both forms above the operands."""
+    from visiondepth3d_amd import depth_pro
+    from visiondepth3d_amd.depth import conv_transpose_gemm_weight, neck_poly_compose
+    from visiondepth3d_amd.render_3d import Renderer
+    R = Renderer(0)
+    C = 128
+    wt, bt = torch.randn(C, C, 2, 2, device="cuda") / C ** 0.5, torch.randn(C, device="cuda")
+    w3, b2 = torch.randn(32, C, 3, 3, device="cuda") / (3.0 * C ** 0.5), torch.randn(32, device="cuda")
+    w1, b3 = torch.randn(32, device="cuda") / 32 ** 0.5, 0.25
+    T = depth_pro.head_poly_table(bt, w3, b2)
+    for mode in ("bf16x3", "fp16x2"):
+        poly = R.depthpro_head_pack(neck_poly_compose(wt, None, w3, 2)[0], mode)
+        gimg, cimg = R.gemm_x3_pack(conv_transpose_gemm_weight(wt), mode), R.conv3x3_tile_pack(w3, mode, 1)
+        for B in frames:
+            x = torch.randn(B, C, 768, 768, device="cuda").contiguous(memory_format=torch.channels_last)
+
+            def fused():
+                return R.depthpro_head(x, poly, T, w1, b3, mode)
+
+            def four():
+                y = R.linear_x3(x.permute(0, 2, 3, 1), gimg, 4 * C, None, mode=mode)
+                fine = R.depth_to_space_bias(y.view(-1, 4 * C), B, 768, 768, 2, bt)
+                return R.dpt_head_tail(R.conv3x3_tile(fine, cimg, 32, mode, 1), b2, w1, b3, 1.0)
+            peak = {}
+            for k, f in (("fused", fused), ("four_launches", four)):
+                torch.cuda.synchronize()
+                torch.cuda.empty_cache()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                out = f()
+                torch.cuda.synchronize()
+                peak[k] = torch.cuda.max_memory_allocated() - base
+                del out
+            d = (fused() - four()).abs().max().item()
+            r = rounds({"fused": fused, "four_launches": four}, 3, warm=1)
+            print(json.dumps(dict(what=f"head_{mode}_768_C{C}_B{B}", ms=r, fused_over_four=r["fused"][0] / r["four_launches"][0], peak_bytes=peak, max_abs_difference=d)))
+            del x
+    R.close()
+
+
+def decoder(frames):
+    """The 1536 x 1536 forward with encoders=m alone (the parent's pipe) and with decoder=m on top, one synthetic model copied per pipe; and the decoder apart
+    -- neck, fusion stage and head on the features the pipe's own encoders hand over -- in the stock and the routed form."""
+    import copy
+    from visiondepth3d_amd.depth import DepthPipe
+    from visiondepth3d_amd.render_3d import Renderer
+    R = Renderer(0)
+    model = _full_model()
+    pipes = {}
+    for mode in ("bf16x3", "fp16x2"):
+        pipes[f"encoders={mode}"] = DepthPipe("depth-pro", renderer=R, model=copy.deepcopy(model), encoders=mode)
+        pipes[f"encoders={mode},decoder={mode}"] = DepthPipe("depth-pro", renderer=R, model=copy.deepcopy(model), encoders=mode, decoder=mode)
+    del model
+    fr = torch.randint(0, 256, (max(frames), 1080, 1920, 3), dtype=torch.uint8, device="cuda")
+    for B in frames:
+        f = fr[:B]
+        r = rounds({k: (lambda p=p: p.infer_bgr_u8(f)) for k, p in pipes.items()}, 2, warm=1)
+        print(json.dumps(dict(what=f"forward_1536_decoder_B{B}", ms=r)))
+    routed = pipes["encoders=bf16x3,decoder=bf16x3"]
+    print(json.dumps(dict(what="decoder_routes_full_size", routes=routed.decoder_routes)))
+    for B in frames:
+        got = {}
+        src = pipes["encoders=bf16x3"]
+        h = src.model.depth_pro.neck.register_forward_pre_hook(lambda mod, args: got.__setitem__("f", [t.clone(memory_format=torch.preserve_format) for t in args[0]]))
+        src.infer_bgr_u8(fr[:B])
+        h.remove()
+        feats = got["f"]
+
+        def apart(p):
+            @torch.no_grad()
+            def run():
+                return p.model.head(p.model.fusion_stage(p.model.depth_pro.neck(list(feats)))[-1])
+            return run
+        r = rounds({k: apart(p) for k, p in pipes.items()}, 2, warm=1)
+        print(json.dumps(dict(what=f"decoder_apart_B{B}", ms=r)))
+    R.close()
+
+
+def first(mode, with_decoder=False):
     from visiondepth3d_amd.depth import DepthPipe
     from visiondepth3d_amd.render_3d import Renderer
     R = Renderer(0)
     t = time.time()
-    pipe = DepthPipe("depth-pro", renderer=R, encoders=None if mode == "none" else mode)
+    pipe = DepthPipe("depth-pro", renderer=R, encoders=None if mode == "none" else mode, decoder=mode if with_decoder else None)
     built = time.time()
     fr = torch.randint(0, 256, (1, 1080, 1920, 3), dtype=torch.uint8, device="cuda")
     pipe.infer_bgr_u8(fr)
     torch.cuda.synchronize()
-    print(json.dumps(dict(what="start_to_first_forward", encoders=pipe.encoders, import_s=t - T0, construct_s=built - t, first_forward_s=time.time() - built,
+    print(json.dumps(dict(what="start_to_first_forward", encoders=pipe.encoders, decoder=pipe.decoder, import_s=t - T0, construct_s=built - t, first_forward_s=time.time() - built,
                           total_s=time.time() - T0)))
     R.close()
 
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=["kernels", "forward", "pyramid", "encoders", "first"])
+    ap.add_argument("what", choices=["kernels", "forward", "pyramid", "encoders", "first", "epi", "head", "decoder"])
     ap.add_argument("--frames", type=int, nargs="+", default=[1, 4])
     ap.add_argument("--mode", choices=["none", "bf16x3", "fp16x2"], default="none")
+    ap.add_argument("--decoder", action="store_true")
     a = ap.parse_args()
     {"kernels": kernels, "forward": lambda: forward(a.frames), "pyramid": lambda: pyramid(a.frames), "encoders": lambda: encoders(a.frames),
-     "first": lambda: first(a.mode)}[a.what]()
+     "first": lambda: first(a.mode, a.decoder), "epi": lambda: epi(a.frames), "head": lambda: head(a.frames), "decoder": lambda: decoder(a.frames)}[a.what]()

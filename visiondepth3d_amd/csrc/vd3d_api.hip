@@ -1797,6 +1797,61 @@ VD3D_EXPORT int vd3d_conv3x3_s2_x2(vd3d_ctx* c, const float* X, int B, int H, in
   return tile_conv_run(tc_s2_x2, c, X, B, H, W, Cin, w_image, Cout, Y);
 }
 
+// the stride-1 tile convolution with a residual unit's glue in its epilogue (vd3d_conv_epi.hip), on the weight image of the mode's bias-free entry point
+VD3D_EXPORT int vd3d_conv3x3_epi(vd3d_ctx* c, int mode, const float* X, int B, int H, int W, int Cin, const void* w_image, int Cout, int flags,
+                                 const float* bias_or_null, const float* r1_or_null, const float* r2_or_null, float* Y, float* Yrelu_or_null) {
+  if (!c || !X || !w_image || !Y) return set_err(VD3D_E_INVALID, "conv3x3_epi: null argument");
+  if (mode != VD3D_X3_BF16X3 && mode != VD3D_X3_FP16X2) return set_err(VD3D_E_INVALID, "conv3x3_epi: mode %d must be VD3D_X3_BF16X3 (0) or VD3D_X3_FP16X2 (1)", mode);
+  if (flags & ~(VD3D_EPI_RELU_IN | VD3D_EPI_RELU)) return set_err(VD3D_E_INVALID, "conv3x3_epi: flags %d hold a bit that is neither VD3D_EPI_RELU_IN nor VD3D_EPI_RELU", flags);
+  const tile_conv_desc& d = mode == VD3D_X3_BF16X3 ? tc_x3 : tc_s1_x2;
+  if (d.weight_bytes(Cin, Cout) < 0)
+    return set_err(VD3D_E_UNSUPPORTED, "conv3x3_epi: shape not built: C_in %d must be a positive multiple of 16%s and C_out %d %s", Cin, d.cin_cap, Cout, d.cout_rule);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_epi: batch %d must be 1 .. 65535 (one grid row per frame)", B);
+  if (H < 1 || W < 1) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_epi: map %d x %d must be at least 1 x 1", H, W);
+  HIPCHK(hipSetDevice(c->device));
+  const int rc = vd_launch_conv3x3_epi(c->stream, mode == VD3D_X3_BF16X3 ? 0 : 1, X, B, H, W, Cin, w_image, Cout, flags, bias_or_null, r1_or_null, r2_or_null, Y, Yrelu_or_null);
+  if (rc == 1 || rc == 2) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_epi: the input and the weight image must be 16-byte aligned (bias, r1, r2 and the outputs 4-byte)");
+  if (rc == 3) return set_err(VD3D_E_UNSUPPORTED, "conv3x3_epi: an output overlaps X, r1, r2, the bias, the weight image or the other output (a workgroup reads the halo of its neighbours' tiles)");
+  if (rc) return set_err(VD3D_E_HIP, "conv3x3_epi: the dynamic LDS opt-in or the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// DepthPro's head behind head.layers.0 (vd3d_depthpro_head.hip): every rule of include/vd3d.h is checked here, before anything is launched
+static int depthpro_head_shape_err(int mode, int Cin) {
+  if (mode != VD3D_X3_BF16X3 && mode != VD3D_X3_FP16X2) return set_err(VD3D_E_INVALID, "depthpro_head: mode %d must be VD3D_X3_BF16X3 (0) or VD3D_X3_FP16X2 (1)", mode);
+  return set_err(VD3D_E_UNSUPPORTED, "depthpro_head: shape not built: C_in %d must be a positive multiple of 16 (at most 65536); C_out is 32", Cin);
+}
+VD3D_EXPORT int64_t vd3d_depthpro_head_weight_bytes(int mode, int Cin) { return (int64_t)vd_depthpro_head_weight_bytes(mode, Cin); }
+VD3D_EXPORT int vd3d_depthpro_head_pack_weights(vd3d_ctx* c, int mode, const float* Wc, int Cin, void* image) {
+  if (!c || !Wc || !image) return set_err(VD3D_E_INVALID, "depthpro_head: null argument");
+  if (vd_depthpro_head_weight_bytes(mode, Cin) < 0) return depthpro_head_shape_err(mode, Cin);
+  if ((reinterpret_cast<uintptr_t>(image) & 15) || (reinterpret_cast<uintptr_t>(Wc) & 3)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_head: the weight image must be 16-byte aligned (the blocks 4-byte)");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depthpro_head_pack(c->stream, mode, Wc, Cin, image)) return set_err(VD3D_E_HIP, "depthpro_head: the weight pack launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_depthpro_head(vd3d_ctx* c, int mode, const float* x, int B, int h, int w, int Cin, const void* w_image, const float* T, const float* w3, float b3,
+                                   float* out) {
+  if (!c || !x || !w_image || !T || !w3 || !out) return set_err(VD3D_E_INVALID, "depthpro_head: null argument");
+  if (vd_depthpro_head_weight_bytes(mode, Cin) < 0) return depthpro_head_shape_err(mode, Cin);
+  if (B < 1 || B > 65535) return set_err(VD3D_E_UNSUPPORTED, "depthpro_head: batch %d must be 1 .. 65535 (one grid row per frame)", B);
+  if (h < 1 || w < 1 || h > (1 << 14) || w > (1 << 14)) return set_err(VD3D_E_UNSUPPORTED, "depthpro_head: coarse map %d x %d must be 1 x 1 .. 16384 x 16384", h, w);
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w_image) & 15) || (reinterpret_cast<uintptr_t>(T) & 3) || (reinterpret_cast<uintptr_t>(w3) & 3) ||
+      (reinterpret_cast<uintptr_t>(out) & 3))
+    return set_err(VD3D_E_UNSUPPORTED, "depthpro_head: the input and the weight image must be 16-byte aligned (T, w3 and the output 4-byte)");
+  {
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x), oa = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t xn = (uintptr_t)B * h * w * Cin * 4, on = (uintptr_t)B * h * w * 16;
+    if (xa < oa + on && oa < xa + xn) return set_err(VD3D_E_UNSUPPORTED, "depthpro_head: the output overlaps the input (a workgroup reads the halo of its neighbours' tiles)");
+  }
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_depthpro_head(c->stream, mode, x, B, h, w, Cin, w_image, T, w3, b3, out)) return set_err(VD3D_E_HIP, "depthpro_head: the dynamic LDS opt-in or the launch failed");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // the convolutions of the interpolation network (vd3d_conv_ifn.hip): every rule of include/vd3d.h is checked here, before anything is launched
 VD3D_EXPORT int64_t vd3d_conv_ifn_weight_bytes(int kind, int Cin, int Cout) { return (int64_t)vd_conv_ifn_weight_bytes(kind, Cin, Cout); }
 

@@ -36,6 +36,7 @@ __host__ __device__ constexpr int cx_lds_m(int mode, int ck) { return cx_b_off(m
 static_assert(cx_a_buf(0) == CX_A_BUF && cx_b_off(0) == CX_B_OFF && cx_lds_m(0, 128) == cx_lds(128) && cx_lds_m(0, 32) == cx_lds(32), "MODE 0 is the plan above");
 
 enum { CX_K3S1 = 0, CX_K3S2 = 1, CX_T4S2 = 2 };   // include/vd3d.h VD3D_IFN_*
+VD_DEV float cx_relu_nan(float x) { return x != x ? x : fmaxf(x, 0.f); }   // torch.relu: a NaN stays a NaN (fmaxf alone would give 0)
 
 struct vd_cx_args {
   const float* X; const uint8_t* Wimg; const float* zero16; const float* bias; const float* slope; const float* R; float* Y;
@@ -45,23 +46,31 @@ struct vd_cx_args {
   int ntx;                  // tiles per row of the tile grid
   int nchunk;               // C_in / 16
   const float* colscale;    // MODE 1: 2^-e per output channel (the weight image holds 2^e W); MODE 0: not read
+  // EPI 2 only (vd3d_conv3x3_epi; behind everything the other forms read, so their argument offsets are what they were)
+  const float* R2; float* Y2; int relu_in, relu;
+  float b3;                 // EPI 3 only (vd3d_depthpro_head): the bias of the 1 x 1 convolution to one channel
 };
 
-// EPI: the entry points' thin variants of the one body.  true (vd3d_conv_ifn): + bias (never null there), optional slope and residual, at most 96 output
-// channels.  false (vd3d_conv3x3_x3: K3S1; vd3d_conv3x3_s2_x3: K3S2): the bare sum -- nothing is added, not even a zero -- and CK-channel slices of C_out on
-// the grid's z axis (K3S1: 256 as two slices of 128; K3S2: 128 n as n slices).
-template <int MODE, int KIND, int WM, int NWN, bool EPI>
+// EPI: the entry points' thin variants of the one body.  1 / true (vd3d_conv_ifn): + bias (never null there), optional slope and residual, at most 96 output
+// channels.  0 / false (vd3d_conv3x3_x3: K3S1; vd3d_conv3x3_s2_x3: K3S2): the bare sum -- nothing is added, not even a zero -- and CK-channel slices of C_out on
+// the grid's z axis (K3S1: 256 as two slices of 128; K3S2: 128 n as n slices).  2 (vd3d_conv3x3_epi, vd3d_conv_epi.hip: K3S1, both MODEs): the bare sum of
+// EPI 0, sliced the same way, over X or over relu(X) (relu_in: applied to the staged pixels in front of the split, a NaN stays a NaN), then
+// vd3d_nhwc_bias_act_f32's chain on the sum in registers: [+ bias[oc]] [+ R] [R2 + v] [max(v, 0)] -> Y, [max(v, 0) -> Y2]; every operand but X is optional.
+// 3 (vd3d_depthpro_head, vd3d_depthpro_head.hip: T4S2 with 32 output channels, both MODEs): the whole tail of DepthPro's head behind the sum -- a border-class
+// bias table, ReLU, the 1 x 1 convolution to ONE channel as a butterfly over the 32 lanes of a pixel, its bias, ReLU -- one float per output pixel.
+template <int MODE, int KIND, int WM, int NWN, int EPI>
 VD_DEV void cx_conv(const vd_cx_args a) {
   constexpr int NTM = cx_terms(MODE), A_BUF = cx_a_buf(MODE), B_OFF = cx_b_off(MODE);
   constexpr int NS = CX_NS, WN = 8 / WM, MR = CX_TH / WM, CK = 32 * WN * NWN, BST = cx_b_stage_m(MODE, CK), NBP = BST / (CX_NT * 16), B_ITEMS = 2 * NTM * CK;
-  static_assert(MODE == 0 || !EPI, "the fp16x2 form has the bare epilogue only");
+  static_assert(MODE == 0 || EPI != 1, "the fp16x2 form has no interpolation-network epilogue");
+  static_assert(EPI != 2 || KIND == CX_K3S1, "the residual-unit epilogue is built for the stride-1 geometry");
   constexpr int A_FLY = NS - 2;   // the taps of a chunk whose counted wait leaves the next chunk's pixel DMAs in flight
   constexpr int SUBS = KIND == CX_K3S2 ? 4 : 1, ST = KIND == CX_K3S2 ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) uint8_t cx_smem[];   // the only LDS object: [A buffer 0][A buffer 1][float32 staging][B ring]
   const int tile = blockIdx.x, b = blockIdx.y;
   // blockIdx.z is the weight slice of the workgroup: the output phase 2 p_y + p_x for T4S2, the CK-channel slice of C_out without EPI (K3S1: 0 or 1, C_out
   // 256; K3S2: C_out / 128 slices); otherwise the grid has one z plane and it is not read
-  constexpr bool SLICED = KIND == CX_T4S2 || !EPI;
+  constexpr bool SLICED = KIND == CX_T4S2 || EPI != 1;
   const unsigned slice = SLICED ? blockIdx.z : 0u;
   const int ph_y = KIND == CX_T4S2 ? (int)(slice >> 1) : 0, ph_x = KIND == CX_T4S2 ? (int)(slice & 1) : 0, oc0 = KIND == CX_T4S2 ? 0 : (int)slice * CK;
   const int tyi = tile / a.ntx, txi = tile - tyi * a.ntx;
@@ -99,7 +108,10 @@ VD_DEV void cx_conv(const vd_cx_args a) {
 #pragma unroll
     for (int it = 0; it < CX_A_ITERS; ++it) {
       const x3_s8 raw = *reinterpret_cast<const x3_s8*>(stg + it * (CX_NT * 16));   // a short vector, bit-cast: not ordered behind the DMAs in flight (vd3d_x3.h)
-      const float4 f = __builtin_bit_cast(float4, raw);
+      float4 f = __builtin_bit_cast(float4, raw);
+      if constexpr (EPI == 2) {
+        if (a.relu_in) { f.x = cx_relu_nan(f.x); f.y = cx_relu_nan(f.y); f.z = cx_relu_nan(f.z); f.w = cx_relu_nan(f.w); }   // uniform
+      }
       if constexpr (MODE == 1) {
         const float v[4] = {f.x, f.y, f.z, f.w};
         x3_h4 h1, h2;
@@ -198,7 +210,7 @@ VD_DEV void cx_conv(const vd_cx_args a) {
       // step that can do it, and the DPT stride-1 convolution does it there; the interpolation network's geometries have chunks shorter than that (K3S2) and do
       // it at the chunk's last step, all three alike, and so does K3S2 without EPI (its 1- and 2-step chunks never reach tap NS - 1).  Either position is safe;
       // each entry point keeps the one it was measured with.
-      if (more_a && tap == (EPI || KIND == CX_K3S2 ? T : NS) - 1) {
+      if (more_a && tap == (EPI == 1 || KIND == CX_K3S2 ? T : NS) - 1) {
         if (KIND == CX_K3S2 && T < NS - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // a 1- or 2-step chunk: the pixel DMAs have not been waited for yet
         write_a((chunk + 1) & 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -208,12 +220,40 @@ VD_DEV void cx_conv(const vd_cx_args a) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
+  if constexpr (EPI == 3) {
+    // ---- the DepthPro head's epilogue (vd3d_depthpro_head.hip; T4S2, 8 x 1 waves, CK = 32: a wave owns one tile row, lane (li, kh) holds output channel li of
+    // the 16 columns (r & 3) + 8 (r >> 2) + 4 kh).  Per pixel: u = max(v + T[row class][column class][oc], 0), d = sum over oc of w3[oc] u as a butterfly over
+    // the 32 lanes of the pixel (partner distance 16, 8, 4, 2, 1, in that order: every lane ends with the same bits), out = max(d + b3, 0); lane li < 16
+    // stores the pixel of register li.  All 64 lanes run the butterflies; only the store is masked.  a.bias = T [3][3][32], a.slope = w3 [32].
+    static_assert(KIND == CX_T4S2 && WM == 8 && NWN == 1, "the head epilogue reduces the 32 channels of one N tile");
+    const int oy = 2 * (y0 + wm) + ph_y;
+    const int ry = oy == 0 ? 0 : oy == a.Ho - 1 ? 2 : 1;   // first / interior / last fine row (a row past the map reads the interior class and stores nothing)
+    const float t0 = a.bias[(ry * 3 + 0) * 32 + li], t1 = a.bias[(ry * 3 + 1) * 32 + li], t2 = a.bias[(ry * 3 + 2) * 32 + li], w3 = a.slope[li];
+    float cs = 1.f;
+    if constexpr (MODE == 1) cs = a.colscale[li];
+    float mine = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int ox = 2 * (x0 + (r & 3) + 8 * (r >> 2) + 4 * kh) + ph_x;
+      float v = acc[0][0][r] + lo[0][0][r];
+      if constexpr (MODE == 1) v *= cs;
+      float d = w3 * fmaxf(v + (ox == 0 ? t0 : ox == a.Wo - 1 ? t2 : t1), 0.f);
+#pragma unroll
+      for (int off = 16; off > 0; off >>= 1) d = d + __shfl_xor(d, off, 64);
+      if (li == r) mine = d;
+    }
+    const int ox = 2 * (x0 + (li & 3) + 8 * ((li & 15) >> 2) + 4 * kh) + ph_x;
+    if (li < 16 && oy < a.Ho && ox < a.Wo) a.Y[((size_t)b * a.Ho + oy) * a.Wo + ox] = fmaxf(mine + a.b3, 0.f);
+    return;
+  }
+
   // ---- epilogue: accumulator register r of (m, n) = tile column (r & 3) + 8 (r >> 2) + 4 kh of tile row MR wm + m, output channel oc0 + (wn * NWN + n) * 32 + li
 #pragma unroll
   for (int n = 0; n < NWN; ++n) {
     const int oc = oc0 + (wn * NWN + n) * 32 + li;
     float bv = 0.f, sv = 1.f;
-    if constexpr (EPI) { bv = a.bias[oc]; sv = a.slope ? a.slope[oc] : 1.f; }
+    if constexpr (EPI == 1) { bv = a.bias[oc]; sv = a.slope ? a.slope[oc] : 1.f; }
+    if constexpr (EPI == 2) { if (a.bias) bv = a.bias[oc]; }
     float cs = 1.f;
     if constexpr (MODE == 1) { cs = a.colscale[oc]; asm volatile("" : "+v"(cs)); }   // consumed in front of the masked stores (vd3d_gemm.hip: else one s_waitcnt vmcnt(0) per store)
 #pragma unroll
@@ -227,10 +267,17 @@ VD_DEV void cx_conv(const vd_cx_args a) {
           const size_t pix = ((size_t)b * a.Ho + oy) * a.Wo + ox;
           float v = acc[m][n][r] + lo[m][n][r];
           if constexpr (MODE == 1) v *= cs;
-          if constexpr (EPI) {
+          if constexpr (EPI == 1) {
             v += bv;
             if (a.slope) v = v >= 0.f ? v : sv * v;
             if (a.R) v += a.R[pix * a.r_stride + oc];
+          }
+          if constexpr (EPI == 2) {   // k_bias_act's chain (vd3d_netops.hip), operation for operation
+            if (a.bias) v += bv;
+            if (a.R) v += a.R[pix * a.r_stride + oc];
+            if (a.R2) v = a.R2[pix * a.r_stride + oc] + v;
+            if (a.relu) v = fmaxf(v, 0.f);
+            if (a.Y2) a.Y2[pix * a.y_stride + oc] = fmaxf(v, 0.f);
           }
           a.Y[pix * a.y_stride + a.y_offset + oc] = v;
         }
@@ -241,9 +288,15 @@ VD_DEV void cx_conv(const vd_cx_args a) {
 
 // the bf16x3 kernel of vd3d_conv_x3.hip / vd3d_conv_s2.hip / vd3d_conv_ifn.hip and the fp16x2 kernel of vd3d_conv_x2t.hip
 template <int KIND, int WM, int NWN, bool EPI>
-__global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) { cx_conv<0, KIND, WM, NWN, EPI>(a); }
+__global__ __launch_bounds__(CX_NT) void k_conv_x3(const vd_cx_args a) { cx_conv<0, KIND, WM, NWN, EPI ? 1 : 0>(a); }
 template <int KIND, int WM, int NWN>
-__global__ __launch_bounds__(CX_NT) void k_conv_x2(const vd_cx_args a) { cx_conv<1, KIND, WM, NWN, false>(a); }
+__global__ __launch_bounds__(CX_NT) void k_conv_x2(const vd_cx_args a) { cx_conv<1, KIND, WM, NWN, 0>(a); }
+// the residual-unit form of either arithmetic (vd3d_conv_epi.hip): stride 1, EPI 2
+template <int MODE, int WM, int NWN>
+__global__ __launch_bounds__(CX_NT) void k_conv_epi(const vd_cx_args a) { cx_conv<MODE, CX_K3S1, WM, NWN, 2>(a); }
+// DepthPro's head behind head.layers.0 in either arithmetic (vd3d_depthpro_head.hip): T4S2, 32 output channels, EPI 3
+template <int MODE>
+__global__ __launch_bounds__(CX_NT) void k_depthpro_head(const vd_cx_args a) { cx_conv<MODE, CX_T4S2, 8, 1, 3>(a); }
 
 // ---- host: the dense, bias-free launch that vd3d_conv3x3_x3, vd3d_conv3x3_s2_x3, vd3d_conv3x3_s1_x2 and vd3d_conv3x3_s2_x2 share (kind K3S1 or K3S2; the tile
 // grid is the output in both).  Checks what they all check -- B 1 .. 65535 (one grid row per frame), a map of at least 1 x 1, X and the image 16-byte and Y
@@ -257,6 +310,7 @@ inline bool cx_dense_args(int kind, const float* X, int B, int H, int W, int Cin
   a.B = B; a.H = H; a.W = W;
   a.Ho = kind == CX_K3S2 ? (H + 1) / 2 : H; a.Wo = kind == CX_K3S2 ? (W + 1) / 2 : W;
   a.x_stride = Cin; a.y_stride = Cout; a.y_offset = 0; a.r_stride = 0; a.nchunk = Cin / 16; a.colscale = colscale;
+  a.R2 = nullptr; a.Y2 = nullptr; a.relu_in = 0; a.relu = 0; a.b3 = 0.f;
   a.ntx = (a.Wo + CX_TW - 1) / CX_TW;
   grid = dim3((unsigned)(a.ntx * ((a.Ho + CX_TH - 1) / CX_TH)), (unsigned)B, Cout > 128 ? (unsigned)(Cout / 128) : 1u);
   return true;

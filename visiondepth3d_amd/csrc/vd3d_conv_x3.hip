@@ -118,6 +118,7 @@ static bool cx_launch(hipStream_t s, int kind, const float* X, int B, int H, int
   a.Ho = kind == CX_K3S2 ? (H + 1) / 2 : kind == CX_T4S2 ? 2 * H : H;
   a.Wo = kind == CX_K3S2 ? (W + 1) / 2 : kind == CX_T4S2 ? 2 * W : W;
   a.x_stride = x_stride; a.y_stride = y_stride; a.y_offset = y_offset; a.r_stride = r_stride; a.nchunk = Cin / 16; a.colscale = nullptr;
+  a.R2 = nullptr; a.Y2 = nullptr; a.relu_in = 0; a.relu = 0; a.b3 = 0.f;
   const int gh = kind == CX_K3S2 ? a.Ho : H, gw = kind == CX_K3S2 ? a.Wo : W;   // the tile grid
   a.ntx = (gw + CX_TW - 1) / CX_TW;
   const dim3 grid((unsigned)(a.ntx * ((gh + CX_TH - 1) / CX_TH)), (unsigned)B, kind == CX_T4S2 ? 4u : 1u);

@@ -264,6 +264,15 @@ bool vd_launch_conv3x3_s2_x3(hipStream_t s, const float* X, int B, int H, int W,
 long long vd_conv3x3_s1_x2_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_s1_x2_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_s1_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);
+// vd3d_conv_epi.hip: the stride-1 tile convolution of mode 0 (bf16x3) / 1 (fp16x2) with vd3d_nhwc_bias_act_f32's chain in its epilogue.  0: launched; 1: shape
+// not built; 2: a pointer, batch or map rule; 3: an output overlaps an input or the other output; 4: the dynamic-LDS opt-in failed
+// vd3d_depthpro_head.hip: DepthPro's head behind head.layers.0 as one launch on the coarse map (mode 0 bf16x3 / 1 fp16x2); Wc = the 16 composed blocks [16][32][Cin]
+long long vd_depthpro_head_weight_bytes(int mode, int Cin);
+bool vd_launch_depthpro_head_pack(hipStream_t s, int mode, const float* Wc, int Cin, void* img);
+bool vd_launch_depthpro_head(hipStream_t s, int mode, const float* X, int B, int h, int w, int Cin, const void* wimg, const float* T, const float* w3, float b3,
+                             float* out);
+int vd_launch_conv3x3_epi(hipStream_t s, int mode, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, int flags, const float* bias,
+                          const float* r1, const float* r2, float* Y, float* Yrelu);
 long long vd_conv3x3_s2_x2_weight_bytes(int Cin, int Cout);
 bool vd_launch_conv3x3_s2_x2_pack(hipStream_t s, const float* W, int Cin, int Cout, void* img);
 bool vd_launch_conv3x3_s2_x2(hipStream_t s, const float* X, int B, int H, int W, int Cin, const void* wimg, int Cout, float* Y);

@@ -854,7 +854,7 @@ class DepthPipe:
     def __init__(self, name: str = "depth-anything-v2-small", device="cuda", dtype=torch.float32, seed: int = 0,
                  channels_last: bool = True, renderer=None, fuse_backbone: bool = True, model=None, processor: dict | None = None,
                  tuned_gemm: bool = True, miopen_find: bool | None = None, gemm: str = "f32", conv: str | None = None, self_contained: bool = False,
-                 front_end: str = "float", encoders: str | None = None):
+                 front_end: str = "float", encoders: str | None = None, decoder: str | None = None):
         """``dtype``: float32 (the reference's precision, default) or bfloat16.
         ``front_end``: ``"float"`` (default) -- the network input is the float32 statement of the image processor's antialiased bicubic resize, never
         rounded (``vd3d_depth_preprocess`` with a renderer, ATen otherwise).  ``"pil"`` -- OPT-IN: the input the reference process builds, bit for bit.
@@ -879,6 +879,11 @@ class DepthPipe:
         field-of-view encoders is a ``vit_blocks._split_block`` in the named arithmetic, the final LayerNorms are ``vd3d_add_layernorm``, the field-of-view ``neck`` Linear is
         ``vd3d_gemm_x3`` and every ``reconstruct_feature_maps`` is ``vd3d_depthpro_merge_f32`` (``_route_depth_pro_encoders``).  The neck, the fusion stage, the head
         and the field-of-view convolutions stay the stock module graph on the float32 library, which is why ``gemm=`` / ``self_contained=True`` keep refusing DepthPro.
+        ``decoder`` (DepthPro only; needs ``encoders``, whose mode it may differ from): ``None`` (default) -- the neck, fusion stage, head and field-of-view convolutions
+        stay the stock module graph, as above.  ``"bf16x3"`` / ``"fp16x2"`` -- OPT-IN: they run on this project's kernels in the named arithmetic
+        (``depth_pro.DecoderRoutes`` lists the route of every module; ``depth_pro.decoder_scope`` refuses, by name and before the module moves, what the routes do not
+        take), so that between ``pixel_values`` and ``predicted_depth`` / ``field_of_view`` no convolution, matrix-product or attention operator of ATen is dispatched.
+        ``pipe.decoder`` records the mode, ``pipe.decoder_routes`` (module name -> route) where every Conv2d / ConvTranspose2d of the decoder ran in the last forward.
         ``pipe.encoders`` records the mode (or None), ``pipe.encoders_resize`` whether the image / field-of-view encoders read the pyramid's quarter level
         ("pyramid") or resized for themselves ("aten").  Any other model, value or geometry is refused by name at construction.
         ``gemm`` (float32 + ``renderer`` only; round 6): ``"f32"`` (default) -- the four linears of every transformer block are hipBLASLt's float32
@@ -947,7 +952,13 @@ class DepthPipe:
             raise ValueError("encoders must be None, 'bf16x3' or 'fp16x2'")
         if encoders is not None and (dtype != torch.float32 or renderer is None or torch.device(device).type != "cuda"):
             raise ValueError("encoders='bf16x3' / 'fp16x2' are modes of the float32 pipe on the GPU and need a renderer (the kernels live in libvd3d_hip.so)")
+        if decoder not in (None, "bf16x3", "fp16x2"):
+            raise ValueError("decoder must be None, 'bf16x3' or 'fp16x2'")
+        if decoder is not None and encoders is None:
+            raise ValueError(f"decoder={decoder!r} needs encoders='bf16x3' | 'fp16x2': the patch merges of the routed encoders hand over the NHWC storage the decoder's "
+                             "routes read")
         self.encoders, self.encoders_resize = None, {}
+        self.decoder, self.decoder_routes = None, {}
         self.front_end, self.front_end_route = front_end, None
         self.gemm, self.conv, self.self_contained = gemm, conv, bool(self_contained)
         self.conv_routes = {}
@@ -981,6 +992,9 @@ class DepthPipe:
         if encoders is not None:   # refused by name on the module graph as it was handed in: nothing moved to a device yet
             self.model = model
             enc_plan = self._depth_pro_encoders_scope(encoders, processor)
+        if decoder is not None:    # likewise: refused by name before anything moves
+            from . import depth_pro
+            depth_pro.decoder_scope(model, name, decoder, enc_plan["size"])
         if self.self_contained:   # refused here, by name, on the module graph as it was handed in: no renderer call, nothing moved to a device yet
             self.model = model
             scope = self._split_scope(fuse_backbone)
@@ -1027,6 +1041,11 @@ class DepthPipe:
                 self._patch_patch_embedding(self.model.backbone.embeddings.patch_embeddings)
         if encoders is not None:
             self._route_depth_pro_encoders(encoders, enc_plan)
+        if decoder is not None:
+            from . import depth_pro
+            with torch.no_grad():
+                depth_pro.DecoderRoutes(self, decoder)
+            self.decoder = decoder
 
     def _library_selection(self, tuned_gemm: bool, miopen_find):
         if miopen_find is not None:

@@ -968,6 +968,55 @@ class Renderer:
         member's public method, looked up per call (a wrapper put on ``conv3x3_x3`` to count its calls sees DepthPipe's)."""
         return getattr(self, f"conv3x3_{self.TILE_CONVS[mode, stride]}")(x, w_image, Cout)
 
+    EPI_RELU_IN, EPI_RELU = 1, 2   # include/vd3d.h VD3D_EPI_*
+
+    def conv3x3_epi(self, x: torch.Tensor, w_image: torch.Tensor, Cout: int, mode: str = "bf16x3", bias=None, r1=None, r2=None, relu_in: bool = False,
+                    relu: bool = False, want_relu_copy: bool = False):
+        """``bias_act(conv3x3_tile([relu](x), w_image, Cout, mode), bias, r1, r2, relu, want_relu_copy)`` as ONE launch with the same bits
+        (``vd3d_conv3x3_epi``, include/vd3d.h): the stride-1 tile convolution of ``mode`` on the image of ``conv3x3_tile_pack(W, mode)`` with
+        ``vd3d_nhwc_bias_act_f32``'s chain in its epilogue.  ``relu_in``: the convolution reads relu(x) (a NaN stays a NaN).  Returns y, or (y, relu(y))."""
+        self._nhwc_f32(x, r1, r2)
+        B, Cin, H, W = x.shape
+        for r in (r1, r2):
+            if r is not None and tuple(r.shape) != (B, int(Cout), H, W):
+                raise ValueError("conv3x3_epi: r1 and r2 have the output's shape")
+        if bias is not None and (bias.dtype != torch.float32 or bias.numel() != int(Cout) or not bias.is_contiguous()):
+            raise ValueError("conv3x3_epi: bias is a contiguous float32 [Cout]")
+        out = torch.empty((B, int(Cout), H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        ro = torch.empty_like(out) if want_relu_copy else None
+        self._enter(x, w_image, bias, r1, r2, out, ro)
+        flags = (self.EPI_RELU_IN if relu_in else 0) | (self.EPI_RELU if relu else 0)
+        _lib.check(self._L.vd3d_conv3x3_epi(self._ctx, {"bf16x3": 0, "fp16x2": 1}[mode], _ptr(x), B, H, W, Cin, _ptr(w_image), int(Cout), flags,
+                                            _ptr(bias) if bias is not None else None, _ptr(r1) if r1 is not None else None,
+                                            _ptr(r2) if r2 is not None else None, _ptr(out), _ptr(ro) if ro is not None else None))
+        return (out, ro) if want_relu_copy else out
+
+    def depthpro_head_pack(self, blocks: torch.Tensor, mode: str = "bf16x3"):
+        """Split + pack the 16 composed blocks ``[16, 32, Cin]`` of ``neck_poly_compose(wt, None, w3, 2)`` for ``depthpro_head`` in ``mode``; ``None`` when the shape is
+        not built (Cin % 16, 32 output channels)."""
+        w = blocks.detach().to(self.device, torch.float32).contiguous()
+        if w.dim() != 3 or tuple(w.shape[:2]) != (16, 32):
+            return None
+        nb = int(self._L.vd3d_depthpro_head_weight_bytes(self.X3_MODES[mode], int(w.shape[2])))
+        if nb < 0:
+            return None
+        img = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._enter(w, img)
+        _lib.check(self._L.vd3d_depthpro_head_pack_weights(self._ctx, self.X3_MODES[mode], _ptr(w), int(w.shape[2]), _ptr(img)))
+        return img
+
+    def depthpro_head(self, x: torch.Tensor, w_image: torch.Tensor, table: torch.Tensor, w3: torch.Tensor, b3: float, mode: str = "bf16x3") -> torch.Tensor:
+        """DepthPro's head behind ``head.layers.0`` in one launch on the coarse map (``vd3d_depthpro_head``, include/vd3d.h; ``depth_pro.head_poly_statement``):
+        float32 channels_last ``x`` [B, Cin, h, w] -> [B, 2h, 2w].  ``table``: float32 [3, 3, 32] (``depth_pro.head_poly_table``), ``w3``: float32 [32]."""
+        self._nhwc_f32(x)
+        B, Cin, h, w = x.shape
+        if table.dtype != torch.float32 or tuple(table.shape) != (3, 3, 32) or not table.is_contiguous() or w3.dtype != torch.float32 or w3.numel() != 32 or not w3.is_contiguous():
+            raise ValueError("depthpro_head: table is contiguous float32 [3, 3, 32], w3 float32 [32]")
+        out = torch.empty((B, 2 * h, 2 * w), dtype=torch.float32, device=x.device)
+        self._enter(x, w_image, table, w3, out)
+        _lib.check(self._L.vd3d_depthpro_head(self._ctx, self.X3_MODES[mode], _ptr(x), B, h, w, Cin, _ptr(w_image), _ptr(table), _ptr(w3), float(b3), _ptr(out)))
+        return out
+
     def conv3x3_x2_pack(self, weight: torch.Tensor):
         """Split + pack a float32 3 x 3 convolution weight [Cout, Cin, 3, 3] for ``conv3x3_x2``; ``None`` when the shape is not built (Cin % 16, Cout in {32, 64, 128})."""
         return self._conv3x3_pack("x2", weight)
