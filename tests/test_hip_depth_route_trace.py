@@ -1,6 +1,8 @@
 """Launch-trace characterisation of DepthPipe's DPT neck / head rewrite (depth.py): per mode, the ORDERED list of Renderer methods one forward calls and the whole
 conv_routes dict, against tests/golden/depth_route_trace.json.  The golden was recorded from the tree before the rewrite was taken apart into route objects, so the
-test pins "the sequence of launches per forward stays what it was" for every mode the rewrite serves.  The trace holds method names only: no timings, no addresses,
+test pins "the sequence of launches per forward stays what it was" for every mode the rewrite serves; the cases behind the comment in CASES were recorded from the
+tree before the rewrites moved out of DepthPipe into depth_routes.py / depth_pro.py, and cover DPT in fp16x2, the self-contained DPT-Hybrid and metric head and DepthPro's
+encoder / decoder routes (whose decoder_routes and encoders_resize are pinned too).  The trace holds method names only: no timings, no addresses,
 nothing a ROCm release changes.  Each case builds its own pipe and runs two forwards: the first packs / composes what is cached per parameter version, the second
 must not.
 
@@ -20,6 +22,7 @@ RECORD = os.environ.get("VD3D_ROUTE_TRACE_RECORD")
 SWITCHES = ("VD3D_NECK_GLUE", "VD3D_HEAD_FUSED", "VD3D_HEAD_CONV2_GATHER", "VD3D_HEAD_UPCONV", "VD3D_NECK_POLY")
 DA = "depth-anything-v2-small"
 SMALL_DPT = "small-dpt-processor"   # the 128 x 128 image processor of tests/test_hip_self_contained_dpt.py
+MINI_PRO = "mini-depth-pro"         # depth_pro_cases.mini_config() / mini_processor(): these cases also pin decoder_routes and encoders_resize
 
 # id -> (model, seed, frame size, environment, DepthPipe keywords); "neck-alone" calls pipe.model.neck(hs, 5, 7) instead of a forward
 CASES = {
@@ -37,6 +40,14 @@ CASES = {
     "dpt-large-bf16x3": ("dpt-large", 5, (252, 476), {}, dict(gemm="bf16x3", processor=SMALL_DPT)),
     "dpt-large-self-contained-bf16x3": ("dpt-large", 5, (252, 476), {}, dict(gemm="bf16x3", conv="bf16x3", self_contained=True, processor=SMALL_DPT)),
     "dpt-hybrid-bf16x3": ("dpt-hybrid-midas", 7, (252, 476), {}, dict(gemm="bf16x3")),
+    # what the move of the rewrites into depth_routes.py / depth_pro.py touches and the matrix above does not reach
+    "dpt-large-fp16x2": ("dpt-large", 5, (252, 476), {}, dict(gemm="fp16x2", processor=SMALL_DPT)),
+    "dpt-large-self-contained-fp16x2": ("dpt-large", 5, (252, 476), {}, dict(gemm="fp16x2", conv="fp16x2", self_contained=True, processor=SMALL_DPT)),
+    "dpt-hybrid-self-contained-bf16x3": ("dpt-hybrid-midas", 7, (252, 476), {}, dict(gemm="bf16x3", conv="bf16x3", self_contained=True)),
+    "da-metric-self-contained-bf16x3": ("depth-anything-v2-metric-indoor-large", 0, (270, 480), {}, dict(gemm="bf16x3", conv="bf16x3", self_contained=True)),
+    "depth-pro-mini": (MINI_PRO, 4, (135, 241), {}, {}),
+    **{f"depth-pro-mini-encoders-{m}": (MINI_PRO, 4, (135, 241), {}, dict(encoders=m)) for m in ("bf16x3", "fp16x2")},
+    **{f"depth-pro-mini-encoders-decoder-{m}": (MINI_PRO, 4, (135, 241), {}, dict(encoders=m, decoder=m)) for m in ("bf16x3", "fp16x2")},
 }
 
 
@@ -75,6 +86,9 @@ def test_forward_calls_the_recorded_renderer_methods_and_routes(R, monkeypatch, 
     kw = dict(kw)
     if kw.get("processor") == SMALL_DPT:
         kw["processor"] = dict(PROCESSORS["dpt"], size=(128, 128))
+    if model == MINI_PRO:
+        import depth_pro_cases
+        kw.update(model=depth_pro_cases.build(depth_pro_cases.mini_config(), seed), processor=depth_pro_cases.mini_processor())
     dtype = getattr(torch, kw.pop("dtype", "float32"))
     pipe = DepthPipe(model, device="cuda", dtype=dtype, seed=seed, renderer=R, **kw)
     log = _trace_renderer(R, monkeypatch)
@@ -93,6 +107,8 @@ def test_forward_calls_the_recorded_renderer_methods_and_routes(R, monkeypatch, 
             got[which] = list(log)
     torch.cuda.synchronize()
     got["conv_routes"] = {k: list(v) for k, v in sorted(pipe.conv_routes.items())}
+    if model == MINI_PRO:
+        got["decoder_routes"], got["encoders_resize"] = dict(sorted(pipe.decoder_routes.items())), dict(sorted(pipe.encoders_resize.items()))
     if RECORD:
         data = {}
         if os.path.exists(RECORD):
@@ -107,3 +123,6 @@ def test_forward_calls_the_recorded_renderer_methods_and_routes(R, monkeypatch, 
     assert got["conv_routes"] == want["conv_routes"]
     assert got["first"] == want["first"]
     assert got["second"] == want["second"]
+    if model == MINI_PRO:
+        assert got["decoder_routes"] == want["decoder_routes"]
+        assert got["encoders_resize"] == want["encoders_resize"]

@@ -2,7 +2,7 @@
 in torch (what the two kernels of csrc/vd3d_depthpro.hip are held to, and what runs where there is no renderer); and the model's patch order and merge geometry
 stated in NumPy: ``patches_statement`` and ``merge_statement`` are what the two kernels of csrc/vd3d_depthpro_pyramid.hip (``vd3d_depthpro_patches_f32``,
 ``vd3d_depthpro_merge_f32``) give bit for bit (tests/test_hip_depth_pro_pyramid.py).  Those kernels run under ``DepthPipe(encoders="bf16x3" | "fp16x2")``, which
-routes the three encoders (``DepthPipe._route_depth_pro_encoders``); by default the network is the stock module graph and no kernel runs them.
+routes the three encoders (``encoders_scope``, ``EncoderRoutes``); by default the network is the stock module graph and no kernel runs them.
 ``DepthPipe(encoders=..., decoder="bf16x3" | "fp16x2")`` routes the neck, the fusion stage, the head and the field-of-view convolutions as well: the last sections
 hold the float64 statements of the two composed weights (``deconv_projection_compose``; ``head_poly_statement`` with ``head_poly_table``, what
 csrc/vd3d_depthpro_head.hip computes), the scope check ``decoder_scope`` and the routes themselves, ``DecoderRoutes``.
@@ -14,9 +14,15 @@ The geometry below is the published one AS FAR AS IT IS KNOWN HERE: no copy of t
 confirmed it against the file.  A checkpoint loads with whatever geometry its own config.json states (``DepthPipe.from_pretrained``)."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from .depth_compose import im2col_gemm_weight, neck_poly_compose, neck_poly_offsets, patch_embedding_conv_ok
+from .depth_routes import _ConvTransposeGemm, _head_tail_operands, patch_embedding_rows
+from .vit_blocks import dinov2_operands, encoder_blocks, head_geometry_ok
 
 # every encoder (image, patch, field of view): a Dinov2Model, ViT-L/16 at 384 x 384, no mask token
 ENCODER = dict(model_type="dinov2", hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, image_size=384, patch_size=16, use_mask_token=False)
@@ -205,7 +211,6 @@ def head_poly_statement(x: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor, w3:
     as the 16 composed blocks of ``neck_poly_compose(wt, None, w3, 2)`` on the coarse grid -- output phase (pa, pb), four taps at coarse offsets (pa - 1 | pa,
     pb - 1 | pb), pixels outside the map contributing nothing -- plus ``head_poly_table``'s border-class constant, ReLU, the 32-term dot product with ``w1``
     ([1, 32, 1, 1] or [32]), ``b3``, ReLU.  ``operands``: the dtype the blocks and the table are rounded to once (float32: the kernel's operands)."""
-    from .depth import neck_poly_compose, neck_poly_offsets
     Wc, _ = neck_poly_compose(wt, None, w3, 2, dtype=operands)
     T = head_poly_table(bt, w3, b2, dtype=operands).to(torch.float64)
     Wc, x = Wc.to(torch.float64), x.detach().to(torch.float64)
@@ -221,6 +226,162 @@ def head_poly_statement(x: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor, w3:
     return torch.relu(d + float(b3))
 
 
+# ---------------------------------------------------------------------------------------------------------------- the encoders on own kernels: DepthPipe(encoders=...)
+def encoders_scope(model, name: str, mode, processor) -> dict:
+    """``encoders=``: what the routing needs of the model and its processor, read from the module graph and the configuration only (nothing is moved or
+    launched); everything it does not cover is refused by name.  Returns the plan ``EncoderRoutes`` executes: the processor side, DepthPro's patch size, the
+    pyramid levels and the names of the encoders present."""
+    m, tag = model, f"encoders={mode!r}"
+    what = f"{name!r} ({type(m).__name__})"
+    if type(m).__name__ != "DepthProForDepthEstimation":
+        raise NotImplementedError(f"{tag}: {what} -- the keyword routes the three ViT encoders of DepthProForDepthEstimation; every other model takes gemm= / conv= / "
+                                  "self_contained=")
+    cfg = m.config
+    found = [("patch", m.depth_pro.encoder.patch_encoder), ("image", m.depth_pro.encoder.image_encoder)]
+    if m.fov_model is not None:
+        found.append(("fov", m.fov_model.fov_encoder))
+    for which, enc in found:
+        vit = enc.model
+        if type(vit).__name__ != "Dinov2Model":
+            raise NotImplementedError(f"{tag}: {what}: the {which} encoder is a {type(vit).__name__} -- _split_block is built for Dinov2Model encoders")
+        d, nh = int(vit.config.hidden_size), int(vit.config.num_attention_heads)
+        if not head_geometry_ok(d, nh):
+            raise NotImplementedError(f"{tag}: {what}: the {which} encoder has hidden size {d} with {nh} heads -- vd3d_attention_x3 and vd3d_add_layernorm are "
+                                      "built for 384 / 768 / 1024 with 64-wide heads")
+        if getattr(vit.config, "use_swiglu_ffn", False):
+            raise NotImplementedError(f"{tag}: {what}: the {which} encoder has a SwiGLU feed-forward -- _split_block is built for fc1 / activation / fc2")
+        if not patch_embedding_conv_ok(vit.embeddings.patch_embeddings.projection):
+            raise NotImplementedError(f"{tag}: {what}: the {which} encoder's patch embedding is not Conv2d(3, C, kernel_size=p, stride=p), p <= 64 -- "
+                                      "vd3d_patchify_f32 does not take it")
+    ratios = [float(r) for r in cfg.scaled_images_ratios]
+    if ratios != [0.25, 0.5, 1.0]:
+        raise NotImplementedError(f"{tag}: {what}: scaled_images_ratios={list(cfg.scaled_images_ratios)} -- vd3d_depthpro_patches_f32 builds the pyramid of [0.25, 0.5, 1]")
+    size = tuple(int(v) for v in (PROCESSOR if processor is None else processor)["size"])
+    if size[0] != size[1] or size[0] % 4:
+        raise NotImplementedError(f"{tag}: {what}: a processor size of {size} -- the pyramid kernel takes a square side that is a multiple of 4")
+    p = int(cfg.patch_size)
+    try:
+        levels = pyramid_levels(size[0], p, ratios, [float(o) for o in cfg.scaled_images_overlap_ratios])
+    except ValueError as e:
+        raise NotImplementedError(f"{tag}: {what}: a pyramid vd3d_depthpro_patches_f32 is not built for -- {e}") from None
+    if any(stride < 1 for _, _, stride, _ in levels):
+        raise NotImplementedError(f"{tag}: {what}: a pyramid vd3d_depthpro_patches_f32 is not built for -- scaled_images_overlap_ratios="
+                                  f"{list(cfg.scaled_images_overlap_ratios)} leave a stride below 1")
+    return dict(size=size[0], patch=p, ratios=ratios, overlaps=[float(o) for o in cfg.scaled_images_overlap_ratios], which=[w for w, _ in found])
+
+
+class EncoderRoutes:
+    """``DepthPipe(encoders=mode)``: the forwards of DepthProPatchEncoder, DepthProImageEncoder and DepthProFovEncoder replaced (``encoders_scope`` has accepted the
+    model; ``plan`` is what it returned), so that between ``pixel_values`` and the inputs of DepthProNeck / ``fov_model.conv`` every launch is one of this
+    project's kernels or an ATen element-wise one (the class-token concatenation, the position-embedding add, the last block's residual add) -- no hipBLASLt,
+    MIOpen or AOTriton call:
+      * the patch pyramid: one launch of vd3d_depthpro_patches_f32, written in the memory patchify reads;
+      * per encoder (``make_encoder``): vd3d_patchify_f32 + vd3d_gemm_x3 for the patch embedding, the class token and the (memoised) position embedding added, every
+        Dinov2Layer a _split_block in ``mode`` (vit_blocks.encoder_blocks: one weight split / pack per encoder, here), the hook layers' residual streams kept, the
+        final LayerNorm as add_layernorm(x, None, ln);
+      * every reconstruct_feature_maps (``merge``): vd3d_depthpro_merge_f32, handed on as the [B, C, oh, ow] view of its NHWC storage (channels_last, what the
+        library convolutions behind it read);
+      * the field-of-view encoder's ``neck`` Linear: vd3d_gemm_x3.
+    Where floor(S / 4) is DepthPro's patch size and the image / field-of-view encoder's image_size, that encoder reads the pyramid's quarter level (the last
+    patch of the stack: F.interpolate(size=) and F.interpolate(scale_factor=0.25) give the same bits there); otherwise its resize stays an ATen call (``own_input``;
+    ``pipe.encoders_resize`` says which).  ``pixel_values`` / ``quarter``: the forward in flight and its quarter level, from the patch encoder's call to the last reader's."""
+
+    def __init__(self, pipe, mode: str, plan: dict):
+        from transformers.models.depth_pro.modeling_depth_pro import DepthProOutput
+        self.pipe, self.R, self.mode, self.plan, self.Out = pipe, pipe.renderer, mode, plan, DepthProOutput
+        self.pixel_values = self.quarter = None
+        m = pipe.model
+        self.pe_mod, self.ie_mod = m.depth_pro.encoder.patch_encoder, m.depth_pro.encoder.image_encoder
+        self.run_patch, self.run_image = self.make_encoder(self.pe_mod.model), self.make_encoder(self.ie_mod.model)
+        self.hook_ids = [int(i) for i in self.pe_mod.intermediate_hook_ids]
+        self.pe_mod.forward, self.ie_mod.forward = self.patch_forward, self.image_forward
+        if m.fov_model is not None:
+            self.fe_mod = m.fov_model.fov_encoder
+            self.run_fov = self.make_encoder(self.fe_mod.model)
+            self.neck_img = self.R.gemm_x3_pack(self.fe_mod.neck.weight, mode)
+            self.fe_mod.forward = self.fov_forward
+
+    def make_encoder(self, vit):
+        R, emb = self.R, vit.embeddings
+        rows = patch_embedding_rows(R, emb.patch_embeddings.projection, self.mode)
+        blocks = encoder_blocks(R, [dinov2_operands(lay) for lay in vit.encoder.layer], self.mode, keyword="encoders")
+        pos = {}
+
+        def run(x, hooks=()):
+            """[N, 3, h, w] in channels_last memory -> (LayerNorm(last hidden state), {hook: that layer's residual stream})."""
+            N, _, h, w = x.shape
+            t = torch.cat((emb.cls_token.expand(N, -1, -1), rows(x)), dim=1)
+            if (h, w) not in pos:   # a constant of the input size (the parameter itself where the grid is the trained one)
+                pos[(h, w)] = emb.interpolate_pos_encoding(t, h, w).detach()
+            t = t + pos[(h, w)]
+            kept = {}
+            for li, blk in enumerate(blocks):
+                t = blk(t)
+                if li in hooks:
+                    kept[li] = t
+            return R.add_layernorm(t, None, vit.layernorm)[1], kept
+        return run
+
+    @staticmethod
+    def base_size(enc, height, width):   # the lowest-resolution feature size, as the stock forwards compute it
+        e = int(math.log2(width / enc.out_size))
+        return height // 2 ** e, width // 2 ** e
+
+    def merge(self, rows, B, padding, oh, ow):
+        return self.R.depthpro_merge(rows.contiguous(), B, int(rows.shape[1] ** 0.5), padding, oh, ow).permute(0, 3, 1, 2)
+
+    def own_input(self, which, enc_cfg, pixel_values):
+        """The [B, 3, size, size] input of the image / field-of-view encoder in channels_last memory."""
+        size = int(enc_cfg.image_size)
+        q = self.quarter if self.pixel_values is pixel_values else None
+        if q is not None and pixel_values.shape[-1] // 4 == size == self.plan["patch"] and tuple(q.shape[-2:]) == (size, size):
+            self.pipe.encoders_resize[which] = "pyramid"
+            return q
+        self.pipe.encoders_resize[which] = "aten"
+        return F.interpolate(pixel_values, size=(size, size), mode="bilinear", align_corners=False).contiguous(memory_format=torch.channels_last)
+
+    def check(self, pixel_values):
+        if pixel_values.dtype != torch.float32 or pixel_values.dim() != 4 or pixel_values.shape[1] != 3:
+            raise NotImplementedError(f"encoders={self.mode!r}: float32 [B, 3, S, S] pixel values expected -- refusing to fall back silently")
+
+    def patch_forward(self, pixel_values):
+        self.check(pixel_values)
+        pe_mod, p, ratios = self.pe_mod, self.plan["patch"], self.plan["ratios"]
+        B, _, H, W = pixel_values.shape
+        if H != W or H % 4:
+            raise NotImplementedError(f"encoders={self.mode!r}: a {H} x {W} input -- the pyramid kernel takes a square side that is a multiple of 4")
+        lv = pyramid_levels(H, p, ratios, self.plan["overlaps"])   # low resolution first
+        patches = self.R.depthpro_patches(pixel_values.contiguous(), p, [lv[2][2], lv[1][2], lv[0][2]])
+        self.pixel_values, self.quarter = pixel_values, (patches[-B:] if lv[0][3] == 1 else None)
+        last, kept = self.run_patch(patches, set(self.hook_ids))
+        bh, bw = self.base_size(pe_mod, H, W)
+        feats, start = [None] * 3, 0
+        for i in (2, 1, 0):   # the stack holds the high-resolution patches first, the features are listed low resolution first
+            cnt = lv[i][3] ** 2 * B
+            feats[i] = self.merge(last[start:start + cnt], B, int(pe_mod.merge_padding_value * (1 / ratios[i])), bh * 2 ** i, bw * 2 ** i)
+            start += cnt
+        for i in self.hook_ids:
+            feats.append(self.merge(kept[i], B, int(pe_mod.merge_padding_value * (1 / ratios[-1])), bh * 4, bw * 4))
+        return feats
+
+    def image_forward(self, pixel_values, output_attentions=False, output_hidden_states=False, return_dict=True):
+        self.check(pixel_values)
+        if output_attentions or output_hidden_states:
+            raise NotImplementedError(f"encoders={self.mode!r}: the routed image encoder keeps no attentions or hidden states")
+        B, _, H, W = pixel_values.shape
+        last, _ = self.run_image(self.own_input("image", self.pipe.model.config.image_model_config, pixel_values))
+        feats = self.merge(last, B, 0, *self.base_size(self.ie_mod, H, W))
+        return self.Out(last_hidden_state=last, features=feats) if return_dict else (last, feats)
+
+    def fov_forward(self, pixel_values):
+        self.check(pixel_values)
+        B, _, H, W = pixel_values.shape
+        neck = self.fe_mod.neck
+        last, _ = self.run_fov(self.own_input("fov", self.pipe.model.config.fov_model_config, pixel_values))
+        self.pixel_values = self.quarter = None   # the last reader of the forward in flight
+        return self.merge(self.R.linear_x3(last, self.neck_img, neck.out_features, neck.bias, mode=self.mode), B, 0, *self.base_size(self.fe_mod, H, W))
+
+
 # ---------------------------------------------------------------------------------------------------------------- the decoder on own kernels: DepthPipe(decoder=...)
 # The argument sets of vd3d_conv3x3_epi the decoder uses: a residual unit's first convolution (ReLU in front, bias + ReLU behind), its second one (bias + the
 # unit's input, and in residual_layer1 the fusion layer's running state as well), and head.layers.0 (bias alone).
@@ -233,7 +394,7 @@ DECODER_HEAD_POLY_BUILT = ("bf16x3", "fp16x2")     # modes of vd3d_depthpro_head
 DECODER_HEAD_POLY_ROUTED = DECODER_HEAD_POLY_BUILT   # ... routed by default (the same profile); VD3D_DEPTHPRO_HEAD_POLY=1 / =0 as above
 
 
-# The A/B switches of the two new kernels (environment variables, read per forward; depth._SWITCHES' convention): unset, the ROUTED tables above decide; "1"
+# The A/B switches of the two new kernels (environment variables, read per forward; depth_routes._SWITCHES' convention): unset, the ROUTED tables above decide; "1"
 # routes every built form; "0" puts the residual units back on bias-free convolution + vd3d_nhwc_bias_act_f32 | the head on GEMM + depth-to-space + tile
 # convolution + vd3d_dpt_head_tail_f32.
 IM2COL_KERNELS = (1, 3, 7)   # the window sizes vd3d_im2col_nhwc_f32 builds
@@ -347,7 +508,7 @@ class DecoderRoutes:
     ``predicted_depth`` / ``field_of_view`` is one of this project's kernels in ``mode``; what is left to ATen is element-wise (ReLU, add), ``cat``, views and
     copies.  All maps are float32 NHWC (channels_last [B, C, h, w] tensors); every weight is packed once, here.
       * 1 x 1 convolutions: vd3d_gemm_x3 over the pixel rows (the NHWC storage is the row matrix); ``fuse_image_with_low_res`` over the concatenated rows.
-      * kernel = stride = 2 transposed convolutions: depth._ConvTransposeGemm (GEMM + vd3d_depth_to_space_bias_nhwc_f32).
+      * kernel = stride = 2 transposed convolutions: depth_routes._ConvTransposeGemm (GEMM + vd3d_depth_to_space_bias_nhwc_f32).
       * ``feature_projection.projections``: the tile convolution, bare.
       * residual units: vd3d_conv3x3_epi per argument set (DECODER_EPI_ROUTED, VD3D_DEPTHPRO_RES_EPI), else bias-free tile convolution + vd3d_nhwc_bias_act_f32 --
         the same bits either way.
@@ -361,7 +522,6 @@ class DecoderRoutes:
 
     def __init__(self, pipe, mode: str):
         import types
-        from .depth import _ConvTransposeGemm, _head_tail_operands, im2col_gemm_weight, neck_poly_compose
         self.pipe, self.R, self.mode, self.names = pipe, pipe.renderer, mode, pipe._names
         R, m = self.R, pipe.model
         self.routes = pipe.decoder_routes
