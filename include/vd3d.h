@@ -47,7 +47,8 @@ extern "C" {
  *    vd3d_head_conv_gather_f32 (the float32 head's up-sampling + second convolution + tail as coarse GEMM + fine gather in one launch),
  *    vd3d_depthpro_patches_count, vd3d_depthpro_patches_f32 and vd3d_depthpro_merge_f32 (DepthPro's patch pyramid and patch merge: DepthPipe(encoders=...)),
  *    vd3d_conv3x3_epi (the stride-1 tile convolution with a residual unit's glue in its epilogue), vd3d_depthpro_head_weight_bytes,
- *    vd3d_depthpro_head_pack_weights and vd3d_depthpro_head (DepthPro's head behind its first convolution in one launch: DepthPipe(decoder=...)). */
+ *    vd3d_depthpro_head_pack_weights and vd3d_depthpro_head (DepthPro's head behind its first convolution in one launch: DepthPipe(decoder=...)),
+ *    vd3d_zoedepth_preprocess_u8, vd3d_zoedepth_post_f32, vd3d_zoedepth_attractor_f32 and vd3d_zoedepth_bins_f32 (ZoeDepth's image-processor ends and metric bin head). */
 #define VD3D_ABI_VERSION 6
 
 typedef enum vd3d_status {
@@ -862,6 +863,39 @@ int vd3d_depthpro_patches_f32(vd3d_ctx* ctx, const float* pixel_values, int B, i
  * another patch: merged size M = side g - 2 pad (side - 1); then ATen's bilinear from M x M to oh x ow, skipped (exact copies) for oh == ow == M.  T >= g^2,
  * g <= 4096, sides up to 2^20, 4-byte aligned pointers; 16-byte loads and stores where C is a multiple of 4 and both pointers are 16-byte aligned. */
 int vd3d_depthpro_merge_f32(vd3d_ctx* ctx, const float* rows, int n, int B, int T, int C, int g, int padding, int oh, int ow, float* out);
+
+/* ---- ZoeDepth (transformers' ZoeDepthForDepthEstimation; visiondepth3d_amd/zoedepth.py states all four in torch).  Every map is float32 NHWC.  "Bilinear" below is
+ * F.interpolate(mode="bilinear", align_corners=True): scale = float(in - 1) / float(out - 1) (0 for out == 1), src = scale d, i0 = min(int(src), in - 1),
+ * i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1, out = l0y (l0x v00 + l1x v01) + l1y (l0x v10 + l1x v11), every operation rounded to float32 on its own; a
+ * zero-weight tap is still multiplied in.  Every refusal (shape, alignment, an output that overlaps an input) is VD3D_E_UNSUPPORTED with a message, and nothing is
+ * launched.
+ *
+ * ZoeDepthImageProcessor: frames_bgr uint8 [B][H][W][3] -> out [B][th][tw][3] in R, G, B order (a channels_last pixel_values tensor).  table_dev: 256 floats in
+ * DEVICE memory, the processor's rescale of every byte (the caller builds it with the class's own rescale: float32(float64(v) * (1 / 255)), which is not
+ * float32(v) * float32(1 / 255)); then the reflect padding by pad_h / pad_w (np.pad mode="reflect", folded into the gather index), the bilinear resize of the
+ * (H + 2 pad_h) x (W + 2 pad_w) image to th x tw, and (v - mean[c]) / std[c] last.  0 <= pad < its side; sides 1 .. 2^20; std non-zero; 4-byte aligned pointers. */
+int vd3d_zoedepth_preprocess_u8(vd3d_ctx* ctx, const uint8_t* frames_bgr, const float* table_dev, int B, int H, int W, int pad_h, int pad_w, int th, int tw,
+                                const float* mean_host, const float* std_host, float* out);
+/* ZoeDepthImageProcessor.post_process_depth_estimation with source_sizes and no target_sizes: pred [B][th][tw] -> out [B][H][W] = the bicubic resize (ATen's:
+ * A = -0.75, align_corners=False, no antialias, src = scale (d + 0.5) - 0.5 with scale = float(in) / out, tap indices clamped) of pred to
+ * (H + 2 pad_h) x (W + 2 pad_w) with the padding cut off -- evaluated at the surviving rows and columns only.  NaN reaches exactly the pixels that tap it. */
+int vd3d_zoedepth_post_f32(vd3d_ctx* ctx, const float* pred, int B, int th, int tw, int H, int W, int pad_h, int pad_w, float* out);
+/* ZoeDepthAttractorLayerUnnormed behind its MLP: attractors [B][h][w][nA] (after softplus), prev_bins [B][hp][wp][nb] -> out [B][h][w][nb] =
+ * c + (sum_i dx_i / (1 + 300 dx_i dx_i)) [/ nA for mean != 0], c = bilinear(prev_bins), dx_i = a_i - c; the sum runs in ascending i from zero in the module's
+ * operation order (dx dx, times 300, plus 1, the division, the accumulation), so the result is the module's float32 loop bit for bit given the same c.
+ * nA 1 .. 16; nb a multiple of 4 up to 256; sides up to 2^15; bins 16-byte aligned. */
+int vd3d_zoedepth_attractor_f32(vd3d_ctx* ctx, const float* attractors, const float* prev_bins, int B, int h, int w, int hp, int wp, int nA, int nb, int mean, float* out);
+/* ZoeDepthConditionalLogBinomialSoftmax and the expectation behind it, per pixel of last [B][H][W][32]: hidden = w1_last [Ch][32] . last (+ wrel [Ch] times the
+ * relative-depth plane rel [B][H][W]; both NULL or both given) + bilinear(P [B][hc][wc][Ch]) + b1; exact (erf) GELU; the four outputs w2 [4][Ch] . g + b2; torch's softplus (threshold 20)
+ * + 1e-4; p = s0 / (s0 + s1), temperature = (max_temp - min_temp) t0 / (t0 + t1) + min_temp; p and 1 - p clamped to [1e-4, 1]; logits
+ * (table[k] + k log p + (nb - 1 - k) log(1 - p)) / temperature; a max-subtracted softmax over the nb bins; out [B][H][W] = its expectation against
+ * bilinear(bins [B][hc][wc][nb]).  table: the module's float32 log_binom(nb - 1, k), nb floats.  Every pointer is device memory.  Ch a multiple of 4 up to 128; nb a
+ * multiple of 4 up to 256; sides up to 2^15; last, P and bins 16-byte aligned.  The MLP is float32 with fused multiply-adds; softplus, p, the temperature and the
+ * logits are evaluated in float64 (a logit reaches (nb - 1) |log 1e-4| and is divided by a temperature as small as min_temp), the exponential of the max-subtracted
+ * logit and the two sums in float32. */
+int vd3d_zoedepth_bins_f32(vd3d_ctx* ctx, const float* last, const float* rel_or_null, const float* wrel_or_null, const float* P, const float* bins, const float* w1_last,
+                           const float* b1, const float* w2, const float* b2, const float* table, double min_temp, double max_temp, int B, int H, int W, int hc, int wc,
+                           int Ch, int nb, float* out);
 
 /* ---- preview visualisers: generate_preview_image, core/preview_utils.py:23-84, the exactly defined types.
  * left / right: uint8 BGR [h][w][3] eyes (outputs of vd3d_pixel_shift).  out: [h][w][3], except HSBS: [h][2*(w/2)][3].

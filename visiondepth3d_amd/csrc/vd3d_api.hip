@@ -2244,6 +2244,90 @@ VD3D_EXPORT int vd3d_depthpro_merge_f32(vd3d_ctx* c, const float* rows, int n, i
   return 0;
 }
 
+// ---- ZoeDepth (vd3d_zoedepth.hip): every refusal below returns before anything is launched
+#define ZOE_ALIGN(p, n) ((reinterpret_cast<uintptr_t>(p) & ((n) - 1)) == 0)
+static bool zoe_overlap(const void* a, long long a_bytes, const void* b, long long b_bytes) {   // b may be NULL
+  if (!b) return false;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+VD3D_EXPORT int vd3d_zoedepth_preprocess_u8(vd3d_ctx* c, const uint8_t* frames_bgr, const float* table_dev, int B, int H, int W, int pad_h, int pad_w, int th, int tw,
+                                            const float* mean_host, const float* std_host, float* out) {
+  if (!c || !frames_bgr || !table_dev || !mean_host || !std_host || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || H < 1 || W < 1 || th < 1 || tw < 1 || H > (1 << 20) || W > (1 << 20) || th > (1 << 20) || tw > (1 << 20))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_preprocess: empty shape or a side past 2^20: batch %d, frame %d x %d, output %d x %d", B, H, W, th, tw);
+  if (pad_h < 0 || pad_w < 0 || pad_h >= H || pad_w >= W)
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_preprocess: a reflect pad of %d x %d on a %d x %d frame: the pad must be smaller than its side", pad_h, pad_w, H, W);
+  for (int i = 0; i < 3; ++i)
+    if (!(std_host[i] != 0.f)) return set_err(VD3D_E_UNSUPPORTED, "zoedepth_preprocess: std[%d] is zero or NaN", i);
+  if (!ZOE_ALIGN(table_dev, 4) || !ZOE_ALIGN(out, 4)) return set_err(VD3D_E_UNSUPPORTED, "zoedepth_preprocess: the table and the output must be 4-byte aligned");
+  const long long out_bytes = (long long)B * th * tw * 12;
+  if (zoe_overlap(out, out_bytes, frames_bgr, (long long)B * H * W * 3) || zoe_overlap(out, out_bytes, table_dev, 1024))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_preprocess: the output overlaps an input");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_zoedepth_preprocess_u8(c->stream, frames_bgr, table_dev, B, H, W, pad_h, pad_w, th, tw, mean_host, std_host, out))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_preprocess: too many pixels for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_zoedepth_post_f32(vd3d_ctx* c, const float* pred, int B, int th, int tw, int H, int W, int pad_h, int pad_w, float* out) {
+  if (!c || !pred || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || H < 1 || W < 1 || th < 1 || tw < 1 || H > (1 << 20) || W > (1 << 20) || th > (1 << 20) || tw > (1 << 20) || pad_h < 0 || pad_w < 0 || pad_h > (1 << 20) || pad_w > (1 << 20))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_post: empty shape, a negative pad or a side past 2^20: batch %d, prediction %d x %d, output %d x %d, pad %d x %d", B, th, tw, H, W,
+                   pad_h, pad_w);
+  if (!ZOE_ALIGN(pred, 4) || !ZOE_ALIGN(out, 4)) return set_err(VD3D_E_UNSUPPORTED, "zoedepth_post: the prediction and the output must be 4-byte aligned");
+  if (zoe_overlap(out, (long long)B * H * W * 4, pred, (long long)B * th * tw * 4)) return set_err(VD3D_E_UNSUPPORTED, "zoedepth_post: the output overlaps the prediction");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_zoedepth_post_f32(c->stream, pred, B, th, tw, H, W, pad_h, pad_w, out)) return set_err(VD3D_E_UNSUPPORTED, "zoedepth_post: too many pixels for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_zoedepth_attractor_f32(vd3d_ctx* c, const float* attractors, const float* prev_bins, int B, int h, int w, int hp, int wp, int nA, int nb, int mean,
+                                            float* out) {
+  if (!c || !attractors || !prev_bins || !out) return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || h < 1 || w < 1 || hp < 1 || wp < 1 || h > (1 << 15) || w > (1 << 15) || hp > (1 << 15) || wp > (1 << 15))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_attractor: empty shape or a side past 2^15: batch %d, map %d x %d, previous map %d x %d", B, h, w, hp, wp);
+  if (nA < 1 || nA > 16 || nb < 4 || nb > 256 || nb % 4)
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_attractor: %d attractors and %d bins: built for 1 .. 16 attractors and a multiple of 4 up to 256 bins", nA, nb);
+  if (!ZOE_ALIGN(attractors, 4) || !ZOE_ALIGN(prev_bins, 16) || !ZOE_ALIGN(out, 16))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_attractor: the bins (in and out) must be 16-byte aligned, the attractors 4-byte aligned");
+  const long long out_bytes = (long long)B * h * w * nb * 4;
+  if (zoe_overlap(out, out_bytes, prev_bins, (long long)B * hp * wp * nb * 4) || zoe_overlap(out, out_bytes, attractors, (long long)B * h * w * nA * 4))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_attractor: the output overlaps an input");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_zoedepth_attractor_f32(c->stream, attractors, prev_bins, B, h, w, hp, wp, nA, nb, mean != 0, out))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_attractor: too many elements for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+VD3D_EXPORT int vd3d_zoedepth_bins_f32(vd3d_ctx* c, const float* last, const float* rel_or_null, const float* wrel_or_null, const float* P, const float* bins,
+                                       const float* w1_last, const float* b1, const float* w2, const float* b2, const float* table, double min_temp, double max_temp, int B,
+                                       int H, int W, int hc, int wc, int Ch, int nb, float* out) {
+  if (!c || !last || !P || !bins || !w1_last || !b1 || !w2 || !b2 || !table || !out || (rel_or_null == nullptr) != (wrel_or_null == nullptr))
+    return set_err(VD3D_E_INVALID, "bad argument");
+  if (B < 1 || H < 1 || W < 1 || hc < 1 || wc < 1 || H > (1 << 15) || W > (1 << 15) || hc > (1 << 15) || wc > (1 << 15))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: empty shape or a side past 2^15: batch %d, map %d x %d, coarse map %d x %d", B, H, W, hc, wc);
+  if (Ch < 4 || Ch > 128 || Ch % 4 || nb < 4 || nb > 256 || nb % 4)
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: %d hidden channels and %d bins: built for a multiple of 4 up to 128 hidden channels and a multiple of 4 up to 256 bins "
+                   "(the feature map has 32 channels)", Ch, nb);
+  if (!(min_temp > 0.0) || !(max_temp >= min_temp)) return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: temperatures %g .. %g: 0 < min_temp <= max_temp", min_temp, max_temp);
+  if (!ZOE_ALIGN(last, 16) || !ZOE_ALIGN(P, 16) || !ZOE_ALIGN(bins, 16))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: the feature map, the projected embedding and the bins must be 16-byte aligned");
+  if (!ZOE_ALIGN(rel_or_null, 4) || !ZOE_ALIGN(wrel_or_null, 4) || !ZOE_ALIGN(w1_last, 4) || !ZOE_ALIGN(b1, 4) || !ZOE_ALIGN(w2, 4) || !ZOE_ALIGN(b2, 4) || !ZOE_ALIGN(table, 4) ||
+      !ZOE_ALIGN(out, 4))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: the plane, the weights, the table and the output must be 4-byte aligned");
+  const long long out_bytes = (long long)B * H * W * 4, coarse = (long long)B * hc * wc * 4;
+  if (zoe_overlap(out, out_bytes, last, out_bytes * 32) || zoe_overlap(out, out_bytes, rel_or_null, out_bytes) || zoe_overlap(out, out_bytes, P, coarse * Ch) ||
+      zoe_overlap(out, out_bytes, bins, coarse * nb))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: the output overlaps an input");
+  HIPCHK(hipSetDevice(c->device));
+  if (!vd_launch_zoedepth_bins_f32(c->stream, last, rel_or_null, wrel_or_null, P, bins, w1_last, b1, w2, b2, table, min_temp, max_temp - min_temp, B, H, W, hc,
+                                   wc, Ch, nb, out))
+    return set_err(VD3D_E_UNSUPPORTED, "zoedepth_bins: too many pixels for one grid");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 VD3D_EXPORT int vd3d_preview_image(vd3d_ctx* c, int type, const uint8_t* left_bgr, const uint8_t* right_bgr, int h, int w, uint8_t* out_bgr) {
   if (!c || !left_bgr || !right_bgr || !out_bgr || h < 1 || w < 1) return set_err(VD3D_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->device));

@@ -338,6 +338,15 @@ long long vd_depthpro_patches_count(int S, int p, int stride_full, int stride_ha
 bool vd_launch_depthpro_patches_f32(hipStream_t s, const float* x, int B, int S, int p, int stride_full, int stride_half, int stride_quarter, float* out);
 int vd_depthpro_merge_geometry(int n, int g, int padding, int* side, int* pad);   // the merged size
 bool vd_launch_depthpro_merge_f32(hipStream_t s, const float* rows, int n, int B, int T, int C, int g, int padding, int oh, int ow, float* out);
+// ---- vd3d_zoedepth.hip: ZoeDepth's padded front end, un-padding post-process and the two kernels of the metric bin head (the C entry points check shapes, alignment
+// and overlap; false = a grid too large)
+bool vd_launch_zoedepth_preprocess_u8(hipStream_t s, const uint8_t* frames, const float* table, int B, int H, int W, int ph, int pw, int th, int tw, const float mean[3],
+                                      const float std[3], float* out);
+bool vd_launch_zoedepth_post_f32(hipStream_t s, const float* pred, int B, int th, int tw, int H, int W, int ph, int pw, float* out);
+bool vd_launch_zoedepth_attractor_f32(hipStream_t s, const float* att, const float* prev, int B, int h, int w, int hp, int wp, int nA, int nb, int mean, float* out);
+bool vd_launch_zoedepth_bins_f32(hipStream_t s, const float* last, const float* rel, const float* wrel, const float* P, const float* bins, const float* w1, const float* b1,
+                                 const float* w2, const float* b2, const float* table, double min_temp, double temp_range, int B, int H, int W, int hc, int wc, int Ch, int nb,
+                                 float* out);
 // ---- vd3d_handoff.hip
 // form: 0 = the library's choice (the separable kernel for up-scaling), 1 = the general kernel, 2 = the separable kernel (false where it does not apply)
 bool vd_launch_depth_handoff(hipStream_t s, const float* pred, int B, int ph, int pw, int H, int W, int invert, uint32_t* mm,

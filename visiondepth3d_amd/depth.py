@@ -30,7 +30,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import depth_pro
+from . import depth_pro, zoedepth
 # the names below that this module does not use itself are re-exported: tests, tools and bench.py import them from here (tests/test_depth_layout.py lists them)
 from .depth_compose import (HEAD_CONV2_GATHER_BUILT, HEAD_CONV2_GATHER_ROUTED, HEAD_UPCONV_BUILT, bit_standardized_weight, conv_transpose_gemm_weight,  # noqa: F401
                             depth_to_u8, dpt_resize_target, head_conv2_compose, head_upconv_compose, im2col_gemm_weight, neck_poly_compose, neck_poly_offsets,
@@ -63,6 +63,9 @@ MODEL_ZOO = {
     # apple/DepthPro-hf (DepthProForDepthEstimation): three DINOv2 ViT-L/16 encoders (image, patch, field of view) at 384 x 384 over a 1 + 9 + 25 patch pyramid of
     # the 1536 x 1536 input; depth_pro.py states the geometry (as far as it is known here) and the processor
     "depth-pro": dict(arch="depth_pro", hidden=1024, layers=24, heads=16, fusion=256),
+    # Intel/zoedepth-nyu-kitti (ZoeDepthForDepthEstimation): BEiT-L/16 at 384 behind a DPT neck, a relative head and the two-domain metric bin head; zoedepth.py states
+    # the geometry (as far as it is known here), the processor and the composed head
+    "zoedepth-nyu-kitti": dict(arch="zoedepth", hidden=1024, layers=24, heads=16, fusion=256),
 }
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -73,6 +76,9 @@ PROCESSORS = {
     "dpt": dict(size=(384, 384), keep_aspect_ratio=False, multiple=1, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)),
     # DepthProImageProcessor: 1536 x 1536, no aspect keeping, BILINEAR (PIL resample 2) without antialias AFTER rescale + normalise, mean = std = 0.5
     "depth_pro": dict(size=(1536, 1536), keep_aspect_ratio=False, multiple=1, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5), resample=2),
+    # ZoeDepthImageProcessor: rescale, REFLECT padding by int(sqrt(side / 2) * 3), BILINEAR (PIL resample 2) with align_corners=True to 384 x 512 keeping the aspect
+    # ratio, normalise last, mean = std = 0.5.  multiple 32: the checkpoint's value as far as it is known here, unconfirmed (the class default is 1 / 32)
+    "zoedepth": dict(zoedepth.PROCESSOR),
 }
 
 
@@ -81,6 +87,8 @@ def build_config(name: str):
     z = MODEL_ZOO[name]
     if z["arch"] == "depth_pro":
         return depth_pro.config()
+    if z["arch"] == "zoedepth":
+        return zoedepth.config(name)
     if z["arch"] == "dpt":
         from transformers import DPTConfig
         if z.get("hybrid"):   # the published config.json of Intel/dpt-hybrid-midas
@@ -172,6 +180,19 @@ class DepthPipe:
         no resize) -- a deviation: the pipeline resizes before the reciprocal.  A model without the field-of-view branch is not scaled.  The network itself runs its
         stock float32 graph: ``gemm="bf16x3"`` / ``"fp16x2"`` and ``self_contained=True`` refuse DepthPro by name (the rewrite is not built), and so does tiled depth
         (its blend evaluates a bicubic post-process); ``bars=`` consumes the uint8 planes and works unchanged.
+        ZoeDepth (``"zoedepth-nyu-kitti"``, ``ZoeDepthForDepthEstimation``: Intel/zoedepth-nyu-kitti; ``zoedepth.py`` states the geometry as far as it is known here):
+        ``__call__``, ``infer_bgr_u8``, ``depth_frames_u8`` and ``at_inference_size`` give what ``pipeline("depth-estimation")`` gives -- ZoeDepthImageProcessor's own order
+        (rescale, REFLECT padding by int(sqrt(side / 2) * 3), a bilinear resize with align_corners=True to 384 x 512 keeping the aspect ratio at a multiple of 32, normalise
+        last: ``front_end="float"``; ``"pil"`` is refused by name), the model, and the processor's post-process at the size the pipeline saw: the bicubic resize to that
+        size plus its padding, with the padding cut off.  With a renderer both ends are one launch each (``vd3d_zoedepth_preprocess_u8`` for uint8 frames without an
+        ``inference_size`` -- otherwise ATen operators, ``front_end_route`` reads "statement"; ``vd3d_zoedepth_post_f32``); on the CPU the same arithmetic runs in ATen.
+        ``raw=True`` returns the model-resolution prediction, padding included.  The BEiT backbone, the neck and the relative head run their stock float32 graph
+        (``gemm=`` / ``conv=`` / ``self_contained=True`` / ``encoders=`` / ``decoder=``, tiled depth and ``flops_per_frame`` refuse the model by name).  The metric bin
+        head runs on two own kernels in float32 with a renderer (``zoedepth.MetricHeadRoute``: ``vd3d_zoedepth_attractor_f32`` per attractor layer and
+        ``vd3d_zoedepth_bins_f32`` for the log-binomial tail, no [B, 64, H, W] tensor, no ``.item()`` on the multi-head model's domain vote); ``pipe.zoe_routes`` says
+        which form runs, ``pipe.zoe_domain`` holds the vote's device index of the last forward, ``VD3D_ZOE_HEAD=0`` puts the stock head back, and whatever
+        ``zoedepth.head_scope`` does not take (``bin_centers_type="normed"``, ...) keeps the stock head with the reason in ``zoe_routes``.  The multi-head model votes
+        over the BATCH (``domain_logits.sum(0)``), as the module does: a frame's prediction depends on the batch it is in, by the model's design.
         ``encoders`` (DepthPro only; float32 + ``renderer``): ``None`` (default) -- the stock graph, as above.  ``"bf16x3"`` / ``"fp16x2"`` -- OPT-IN: from ``pixel_values``
         to the inputs of ``DepthProNeck`` (and to the input of the field-of-view model's convolution) no vendor-library call is made: the patch pyramid is one launch
         (``vd3d_depthpro_patches_f32``), the patch embeddings are ``vd3d_patchify_f32`` + ``vd3d_gemm_x3``, every ``Dinov2Layer`` of the patch, image and
@@ -273,6 +294,8 @@ class DepthPipe:
             cfg = build_config(name)
             if MODEL_ZOO[name]["arch"] == "depth_pro":
                 from transformers import DepthProForDepthEstimation as Net
+            elif MODEL_ZOO[name]["arch"] == "zoedepth":
+                from transformers import ZoeDepthForDepthEstimation as Net
             elif MODEL_ZOO[name]["arch"] == "dpt":
                 from transformers import DPTForDepthEstimation as Net
             else:
@@ -281,7 +304,7 @@ class DepthPipe:
             synthetic_weights_(model, seed)
             processor = processor or PROCESSORS[MODEL_ZOO[name]["arch"]]
         self.model = model
-        self.arch = {"DepthAnythingForDepthEstimation": "da", "DepthProForDepthEstimation": "depth_pro"}.get(type(model).__name__, "generic")
+        self.arch = {"DepthAnythingForDepthEstimation": "da", "DepthProForDepthEstimation": "depth_pro", "ZoeDepthForDepthEstimation": "zoedepth"}.get(type(model).__name__, "generic")
         if self.arch == "depth_pro":
             if front_end == "pil":   # the processor is no Pillow resize: it normalises first and resizes the FLOAT image (torchvision, no antialias)
                 raise NotImplementedError(f"front_end='pil': {name!r} (DepthProForDepthEstimation) -- DepthProImageProcessor rescales and normalises first and resizes the float "
@@ -290,6 +313,14 @@ class DepthPipe:
                 self._split_scope(fuse_backbone)
             if processor is None:
                 processor = PROCESSORS["depth_pro"]
+        if self.arch == "zoedepth":
+            if front_end == "pil":   # the processor pads and resizes the rescaled FLOAT image (F.interpolate, align_corners=True)
+                raise NotImplementedError(f"front_end='pil': {name!r} (ZoeDepthForDepthEstimation) -- ZoeDepthImageProcessor rescales, pads by reflection and resizes the float "
+                                          "tensor bilinearly with align_corners=True; there is no 8-bit Pillow pass to reproduce, front_end='float' IS the processor's own order")
+            if gemm != "f32" or self_contained:
+                self._split_scope(fuse_backbone)
+            if processor is None:
+                processor = PROCESSORS["zoedepth"]
         if encoders is not None:
             enc_plan = depth_pro.encoders_scope(model, name, encoders, processor)
         if decoder is not None:
@@ -340,6 +371,10 @@ class DepthPipe:
                 self._patch_dpt_upsampling()
             if self.self_contained:
                 _PatchEmbedding(self, self.model.backbone.embeddings.patch_embeddings)
+        if self.arch == "zoedepth":
+            self._zoe_table = zoedepth.rescale_table().to(self.device)
+            with torch.no_grad():
+                zoedepth.route_head(self)
         if encoders is not None:
             with torch.no_grad():
                 depth_pro.EncoderRoutes(self, encoders, enc_plan)
@@ -380,13 +415,22 @@ class DepthPipe:
         local-model branch, ``AutoModelForDepthEstimation.from_pretrained(checkpoint)`` + ``AutoProcessor.from_pretrained(checkpoint)``
         (core/render_depth.py:756-760).  DepthAnything / DINOv2 checkpoints (Depth-Anything V1 / V2, Distill-Any-Depth) then get the
         fused-weight rewrites (one QKV GEMM, LayerScale folded into the projections); any other depth architecture
-        (DPT / MiDaS 3.0, ZoeDepth ...) runs its stock module graph behind the same protocol -- except that a plain-ViT DPT checkpoint
+        (DPT / MiDaS 3.0 ...) runs its stock module graph behind the same protocol; a ZoeDepth checkpoint runs behind ITS processor (``resample: 2`` is accepted for
+        that class -- and DepthPro -- only; ``zoedepth.preprocessor_from_json`` reads do_pad, keep_aspect_ratio, ensure_multiple_of, size, mean and std and refuses
+        any other ZoeDepth processor by name) -- except that a plain-ViT DPT checkpoint
         (Intel/dpt-large) with ``gemm="bf16x3" / "fp16x2"`` and a renderer in ``kw`` gets the split-mode rewrite (``__init__``)."""
         from transformers import AutoModelForDepthEstimation
         if not os.path.isdir(path):
             raise FileNotFoundError(f"{path}: not a local checkpoint folder (this build environment has no network)")
         model = AutoModelForDepthEstimation.from_pretrained(path, local_files_only=True)
         pro = type(model).__name__ == "DepthProForDepthEstimation"
+        if type(model).__name__ == "ZoeDepthForDepthEstimation":   # the one class whose processor is bilinear with align_corners=True behind a reflect padding
+            pc = os.path.join(path, "preprocessor_config.json")
+            proc = dict(PROCESSORS["zoedepth"])
+            if os.path.exists(pc):
+                with open(pc) as f:
+                    proc = zoedepth.preprocessor_from_json(json.load(f))
+            return cls(os.path.basename(os.path.normpath(path)), device=device, dtype=dtype, model=model, processor=proc, **kw)
         proc = dict(PROCESSORS["da" if type(model).__name__ == "DepthAnythingForDepthEstimation" else "depth_pro" if pro else "dpt"])
         pc = os.path.join(path, "preprocessor_config.json")
         if os.path.exists(pc):
@@ -411,6 +455,8 @@ class DepthPipe:
         return cls(os.path.basename(os.path.normpath(path)), device=device, dtype=dtype, model=model, processor=proc, **kw)
 
     def resize_target(self, h: int, w: int):
+        if self.arch == "zoedepth":   # (of the image the resize sees: the frame plus its reflect padding)
+            return zoedepth.resize_target(h, w, self.proc["size"], self.proc["multiple"], self.proc["keep_aspect_ratio"])
         return dpt_resize_target(h, w, self.proc["size"], self.proc["multiple"], self.proc["keep_aspect_ratio"])
 
     def _count_conv(self, m, y):
@@ -456,6 +502,10 @@ class DepthPipe:
             raise NotImplementedError(f"{tag}: {what} -- DepthPro runs its stock float32 graph between the own front end and post-process (gemm='f32'); the split-mode "
                                       "rewrite of its three encoders, neck, fusion stage, head and field-of-view branch is not built -- nothing is substituted "
                                       "silently")
+        if type(m).__name__ == "ZoeDepthForDepthEstimation":
+            raise NotImplementedError(f"{tag}: {what} -- ZoeDepth runs its stock float32 graph between the own front end, metric bin head and post-process (gemm='f32'): "
+                                      "BEiT's relative position bias has no input in vd3d_attention_x3 and the split-mode rewrite of its backbone, neck and relative head "
+                                      "is not built -- nothing is substituted silently")
         if type(m).__name__ != "DPTForDepthEstimation" or not fuse_backbone:
             raise NotImplementedError(f"{tag}: {what} -- the split modes rewrite the fused DINOv2 backbone (Depth-Anything V1 / V2, Distill-Any-Depth) and the "
                                       "plain-ViT DPT (DPT-Large), with fuse_backbone=True; this model runs its stock float32 graph -- nothing is substituted silently")
@@ -543,6 +593,8 @@ class DepthPipe:
             oH, oW = H, W
         if self.arch == "depth_pro":
             return self._infer_depth_pro(frames_bgr, inference_size, raw, oH, oW)
+        if self.arch == "zoedepth":
+            return self._infer_zoedepth(frames_bgr, inference_size, raw, oH, oW)
         if self.front_end == "pil":
             pred = self.model(pixel_values=self._pil_pixel_values(frames_bgr, inference_size)).predicted_depth
             if raw:
@@ -607,6 +659,36 @@ class DepthPipe:
             return self.renderer.depthpro_post(pred, fov, oH, oW)
         return depth_pro.post_statement(pred, fov, oH, oW, resize=not raw)
 
+    def _infer_zoedepth(self, frames_bgr, inference_size, raw, oH, oW):
+        """infer_bgr_u8 for ZoeDepthForDepthEstimation: the processor (rescale, reflect padding, the align_corners=True bilinear resize, normalise), the model, and
+        ZoeDepthImageProcessor.post_process_depth_estimation as the pipeline calls it, with the size it saw as ``source_sizes``: the bicubic resize of the prediction to
+        that size plus its padding, with the padding cut off.  With a renderer the post-process is one launch (vd3d_zoedepth_post_f32) and, for uint8 frames without an
+        inference size, so is the front end (vd3d_zoedepth_preprocess_u8: no padded image exists).  With an ``inference_size`` (the pre-resize hands the processor
+        non-integer pixels) or non-uint8 frames the front end is zoedepth.preprocess_statement, the same arithmetic as ATen operators, and without a renderer so is
+        the post-process (post_statement).  ``front_end_route`` ("kernel" | "statement") says which front end ran last.  ``raw``: the model-resolution prediction,
+        padding included."""
+        f, proc = frames_bgr.to(self.device), self.proc
+        if self.renderer is not None and inference_size is None and f.dtype == torch.uint8:
+            H, W = f.shape[1:3]
+            ph, pw = zoedepth.pad_amounts(H, W) if proc.get("pad", True) else (0, 0)
+            target = zoedepth.resize_target(H + 2 * ph, W + 2 * pw, proc["size"], proc["multiple"], proc["keep_aspect_ratio"])
+            x = self.renderer.zoedepth_preprocess(f, (ph, pw), target, proc["mean"], proc["std"], self._zoe_table)
+            self.front_end_route = "kernel"
+        else:
+            self.front_end_route = "statement"
+            if inference_size is not None:   # hf_batch_safe_pipe: img.resize(inference_size, BICUBIC) first (:1113-1116), in its float statement as for every model
+                f = F.interpolate(f.flip(-1).permute(0, 3, 1, 2).float(), size=(int(inference_size[1]), int(inference_size[0])), mode="bicubic", antialias=True,
+                                  align_corners=False).clamp_(0, 255).permute(0, 2, 3, 1).flip(-1)
+            x = zoedepth.preprocess_statement(f, proc)
+            if self.device.type == "cuda":
+                x = x.contiguous(memory_format=torch.channels_last)
+        pred = self.model(pixel_values=x.to(self.dtype)).predicted_depth.float().contiguous()
+        if raw:
+            return pred
+        if self.renderer is not None:
+            return self.renderer.zoedepth_post(pred, oH, oW, zoedepth.pad_amounts(oH, oW) if proc.get("pad", True) else (0, 0))
+        return zoedepth.post_statement(pred, oH, oW, proc.get("pad", True))
+
     @torch.no_grad()
     def depth_frames_u8(self, frames_bgr: torch.Tensor, inference_size=None, invert: bool = False, tiled: bool = False, tile: int = 512,
                         pad: int = 32, tile_batch: int = 16, bars=None) -> torch.Tensor:
@@ -669,6 +751,9 @@ class DepthPipe:
         replaces the network."""
         if self.renderer is None:
             raise RuntimeError("infer_tiled_bgr_u8 needs DepthPipe(renderer=...): the tile gather and blend are HIP kernels")
+        if self.arch == "zoedepth" and model_call is None:
+            raise NotImplementedError(f"tiled depth: {self.name!r} (ZoeDepthForDepthEstimation) -- the tile blend evaluates the pipeline's plain bicubic post-process of every "
+                                      "tile; ZoeDepth's removes the processor's reflect padding -- not built")
         if self.arch == "depth_pro" and model_call is None:
             raise NotImplementedError(f"tiled depth: {self.name!r} (DepthProForDepthEstimation) -- the tile blend evaluates the pipeline's BICUBIC post-process of every tile; "
                                       "DepthPro's is a bilinear resize followed by a reciprocal -- not built")
@@ -740,6 +825,8 @@ class DepthPipe:
         for the backbone, the EXECUTED convolution flops of the DPT neck / head counted during one forward."""
         if self.arch == "depth_pro":
             raise NotImplementedError(f"flops_per_frame: {self.name!r} (DepthProForDepthEstimation) -- the estimate is not built for the three-encoder patch pyramid")
+        if self.arch == "zoedepth":
+            raise NotImplementedError(f"flops_per_frame: {self.name!r} (ZoeDepthForDepthEstimation) -- the estimate is not built for the padded front end and the bin head")
         th, tw = self.resize_target(h, w)
         bcfg = getattr(self.model.config, "backbone_config", None) or self.model.config
         if not hasattr(bcfg, "patch_size"):   # DPT-Hybrid: the backbone configuration is the BiT prefix's; the transformer is the model's own

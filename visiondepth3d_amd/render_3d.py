@@ -1440,6 +1440,78 @@ class Renderer:
         _lib.check(self._L.vd3d_depthpro_post_f32(self._ctx, _ptr(pred), _ptr(fov) if fov is not None else None, B, S, int(oH), int(oW), _ptr(out)))
         return out
 
+    # ---- ZoeDepth (vd3d_zoedepth.hip; zoedepth.py holds the statements)
+    def zoedepth_preprocess(self, frames_bgr: torch.Tensor, pads, target, mean, std, table: torch.Tensor) -> torch.Tensor:
+        """ZoeDepthImageProcessor in one launch: uint8 BGR [B, H, W, 3] -> float32 pixel_values [B, 3, th, tw] in channels_last memory -- the rescale as the
+        256-entry ``table`` of the byte (``zoedepth.rescale_table``, on the device), the reflect padding by ``pads`` = (pad_h, pad_w) folded into the gather, the
+        align_corners=True bilinear resize to ``target`` = (th, tw), then (v - mean) / std (include/vd3d.h vd3d_zoedepth_preprocess_u8;
+        ``zoedepth.preprocess_statement``)."""
+        f = frames_bgr.to(self.device)
+        if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3:
+            raise TypeError("zoedepth_preprocess takes uint8 [B,H,W,3] BGR frames")
+        if table.dtype != torch.float32 or table.numel() != 256 or not table.is_contiguous() or table.device != f.device:
+            raise ValueError("zoedepth_preprocess: the rescale table is 256 contiguous float32 values on the frames' device")
+        f = f.contiguous()
+        B, H, W, _ = f.shape
+        th, tw = int(target[0]), int(target[1])
+        out = torch.empty((B, th, tw, 3), dtype=torch.float32, device=self.device)
+        m = (C.c_float * 3)(*[float(v) for v in mean]); s = (C.c_float * 3)(*[float(v) for v in std])
+        self._enter(f, table, out)
+        _lib.check(self._L.vd3d_zoedepth_preprocess_u8(self._ctx, _ptr(f), _ptr(table), B, H, W, int(pads[0]), int(pads[1]), th, tw, m, s, _ptr(out)))
+        return out.permute(0, 3, 1, 2)
+
+    def zoedepth_post(self, pred: torch.Tensor, H: int, W: int, pads, out=None) -> torch.Tensor:
+        """ZoeDepth's post-process in one launch: float32 [B, th, tw] -> [B, H, W], the bicubic resize to (H + 2 pad_h, W + 2 pad_w) evaluated inside the crop only
+        (include/vd3d.h vd3d_zoedepth_post_f32; ``zoedepth.post_statement``)."""
+        if pred.dtype != torch.float32 or pred.dim() != 3 or not pred.is_contiguous():
+            raise ValueError("zoedepth_post: a contiguous float32 [B, th, tw] prediction expected")
+        B, th, tw = pred.shape
+        if out is None:
+            out = torch.empty((B, int(H), int(W)), dtype=torch.float32, device=pred.device)
+        self._enter(pred, out)
+        _lib.check(self._L.vd3d_zoedepth_post_f32(self._ctx, _ptr(pred), B, th, tw, int(H), int(W), int(pads[0]), int(pads[1]), _ptr(out)))
+        return out
+
+    def zoedepth_attractor(self, attractors: torch.Tensor, prev_bins: torch.Tensor, kind: str = "mean") -> torch.Tensor:
+        """ZoeDepthAttractorLayerUnnormed behind its MLP in one launch: contiguous float32 NHWC attractor points [B, h, w, nA] (after softplus) and previous bins
+        [B, hp, wp, nb] -> new bins [B, h, w, nb] (include/vd3d.h vd3d_zoedepth_attractor_f32; ``zoedepth.attractor_statement``)."""
+        if kind not in ("mean", "sum"):
+            raise ValueError("zoedepth_attractor: kind is 'mean' or 'sum'")
+        for t in (attractors, prev_bins):
+            if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+                raise ValueError("zoedepth_attractor: contiguous float32 [B, h, w, C] maps expected")
+        B, h, w, nA = attractors.shape
+        if prev_bins.shape[0] != B:
+            raise ValueError("zoedepth_attractor: one batch size expected")
+        _, hp, wp, nb = prev_bins.shape
+        out = torch.empty((B, h, w, nb), dtype=torch.float32, device=attractors.device)
+        self._enter(attractors, prev_bins, out)
+        _lib.check(self._L.vd3d_zoedepth_attractor_f32(self._ctx, _ptr(attractors), _ptr(prev_bins), B, h, w, hp, wp, nA, nb, int(kind == "mean"), _ptr(out)))
+        return out
+
+    def zoedepth_bins(self, last: torch.Tensor, rel, wrel, P: torch.Tensor, bins: torch.Tensor, w1_last: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+                      b2: torch.Tensor, table: torch.Tensor, min_temp: float, max_temp: float) -> torch.Tensor:
+        """The conditional log-binomial tail of ZoeDepth's metric head in one launch: contiguous float32 NHWC ``last`` [B, H, W, 32], the optional relative-depth
+        plane ``rel`` [B, H, W] with its weight column ``wrel`` [Ch], ``P`` = W1_e . e [B, hc, wc, Ch], ``bins`` [B, hc, wc, nb], ``w1_last`` [Ch, 32], ``b1`` [Ch],
+        ``w2`` [4, Ch], ``b2`` [4] and the module's float32 log-binomial ``table`` [nb] -> metric depth [B, H, W] (include/vd3d.h vd3d_zoedepth_bins_f32;
+        ``zoedepth.bins_statement``)."""
+        ts = [last, P, bins, w1_last, b1, w2, b2, table] + ([rel, wrel] if rel is not None else [])
+        if (rel is None) != (wrel is None) or any(t.dtype != torch.float32 or not t.is_contiguous() for t in ts) or last.dim() != 4 or P.dim() != 4 or bins.dim() != 4:
+            raise ValueError("zoedepth_bins: contiguous float32 tensors expected, the plane and its weight column together or not at all")
+        B, H, W, cl = last.shape
+        _, hc, wc, Ch = P.shape
+        nb = bins.shape[3]
+        if cl != 32 or tuple(bins.shape[:3]) != (B, hc, wc) or P.shape[0] != B or tuple(w1_last.shape) != (Ch, 32) or b1.numel() != Ch or tuple(w2.shape) != (4, Ch) \
+                or b2.numel() != 4 or table.numel() != nb or (rel is not None and (tuple(rel.shape) != (B, H, W) or wrel.numel() != Ch)):
+            raise ValueError(f"zoedepth_bins: shapes {tuple(last.shape)} / {tuple(P.shape)} / {tuple(bins.shape)} / {tuple(w1_last.shape)} / {tuple(w2.shape)} do not fit "
+                             "[B,H,W,32] / [B,hc,wc,Ch] / [B,hc,wc,nb] / [Ch,32] / [4,Ch]")
+        out = torch.empty((B, H, W), dtype=torch.float32, device=last.device)
+        self._enter(*ts, out)
+        p = lambda t: _ptr(t) if t is not None else None   # noqa: E731
+        _lib.check(self._L.vd3d_zoedepth_bins_f32(self._ctx, _ptr(last), p(rel), p(wrel), _ptr(P), _ptr(bins), _ptr(w1_last), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(table),
+                                                  float(min_temp), float(max_temp), B, H, W, hc, wc, Ch, nb, _ptr(out)))
+        return out
+
     def depthpro_patches(self, pixel_values: torch.Tensor, p: int, strides) -> torch.Tensor:
         """DepthProPatchEncoder's patch pyramid in one launch: contiguous float32 pixel_values [B, 3, S, S] (S a multiple of 4) -> the stack its ViT sees,
         logical shape [(n1 + n2 + n4) B, 3, p, p] in channels_last memory (what ``patchify`` takes): full-resolution patches first, then the half level, then the
