@@ -252,6 +252,10 @@ class DepthPipe:
             raise ValueError("gemm must be 'f32', 'bf16x3' or 'fp16x2'")
         if conv not in (None, "bf16x3", "fp16x2"):
             raise ValueError("conv must be None, 'bf16x3' or 'fp16x2'")
+        if getattr(renderer, "_private", False):
+            # nothing here calls ordered_after(): the renderer's launches and the network's ATen operators are ordered by sharing one stream
+            raise ValueError("DepthPipe needs a renderer on the SAME stream as the network: Renderer(private_stream=True) enqueues on a stream of its own, "
+                             "pass a default Renderer (it follows torch's current stream)")
         if self_contained:
             # the two pairs of the mode; the bf16x3 pair leads the wording, a half-given bf16x3 pair names its missing half alone
             pair = (gemm, conv) in (("bf16x3", "bf16x3"), ("fp16x2", "fp16x2"))

@@ -396,7 +396,7 @@ class Renderer:
             out = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
         if lo_hi is not None and (lo_hi.dtype != torch.float32 or lo_hi.numel() < 2 * B or not lo_hi.is_contiguous() or lo_hi.device != self.device):
             raise AssertionError("depth_normalize_pclip: lo_hi is a contiguous float32 [B,2] tensor on the renderer's device")
-        self._enter(p, out)
+        self._enter(p, out, lo_hi)
         _lib.check(self._L.vd3d_depth_normalize_pclip_u8(self._ctx, _ptr(p), B, H, W, float(pclip[0]), float(pclip[1]), int(bool(invert)),
                                                          _ptr(out), None if lo_hi is None else _ptr(lo_hi)))
         return out
